@@ -2,8 +2,12 @@
 """Headline benchmark of the imagination hot path (BASELINE.json): imagined latent steps / second
 (whole job) + actor/critic step ms, dim=512 depth=6 H=15, on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N = 1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the result line; nothing else.  --dump-outputs DIR writes what the
+last timed step computed (`timed_outputs`) as DIR/<name>.npy.  Everything below the headline (roofline, glue kernels, CPU baselines, parity
+with the oracle, measured peaks, the secondary cfg4 / cfg5 / training-step / fp16x2 keys) runs only with --full, after the timed steps.
 
 One "step" = one DreamTrainer iteration (dreamer4/trainers.py:1422-1452) on synthetic inputs:
 generate(H+1 frames, B=256 trajectories per GPU, 4 denoising steps + 1 clean step per frame)
@@ -13,9 +17,9 @@ Weights: default init of that architecture under torch.manual_seed(0) with non-t
 the timed region.  Rank 0 prints ONE JSON line.
 
   value        = N * B * (H+1) * K / wall     imagined steps per second over the WHOLE step (rollout + learner)
-  roofline     = the dominant kernel (the GEMM class with the largest share of GPU time, found in an extra event-timed step before the
+  roofline     = the dominant kernel (the GEMM class with the largest share of GPU time, found in an extra event-timed step after the
                  timed region): algorithmic flops of its launches / their summed HIP-event durations in an event-timed REPEAT of the timed
-                 steps right after the timed region (events cannot ride inside replayed hipGraphs; the timed region is the default path),
+                 steps right after that step (events cannot ride inside replayed hipGraphs; the timed region is the default path),
                  against the 157.3 TFLOP/s fp32 matrix peak (2500 / 6 for a split-operand class)
   glue_kernels_hbm = the non-GEMM kernel classes of the rollout (attention cores, KV append, pool mix, ...): ALGORITHMIC bytes of
                  their launches in the extra event-timed step / their HIP-event durations, against the 8 TB/s HBM peak — measured live
@@ -31,8 +35,12 @@ import argparse
 import ctypes as C
 import json
 import os
+import subprocess
 import sys
 import time
+import zlib
+
+import numpy as np
 
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')      # dmabuf IPC: RCCL between processes fails with hipIpcGetMemHandle otherwise (must precede HIP init)
 
@@ -56,6 +64,43 @@ def build_model(device):
     m = DynamicsWorldModel(**CFG2)
     randomize_weights(m, seed=0, terminal_bias=-10.)     # heads non-trivial; terminal head ~never fires so all H+1 frames count
     return m.to(device)
+
+
+DUMP_BUDGET_BYTES = 63 * 10 ** 6          # --dump-outputs: 64 MB at most, .npy headers included
+
+
+def timed_outputs(model, dreams, losses):
+    """What a caller of the timed step receives from its last call, as host arrays: every tensor of the Experience trainer.generate()
+    returned (Actions fields as <field>_discrete / <field>_continuous), the [policy, value] losses trainer.learn() returned and the weights of
+    both heads after its clip + AdamW step.  Floating tensors as float32, integer / bool ones as float64 (exact)."""
+    from dataclasses import fields
+    out = {}
+    for f in fields(dreams):
+        v = getattr(dreams, f.name)
+        if torch.is_tensor(v):
+            out[f.name] = v
+        elif isinstance(v, tuple) and hasattr(v, '_fields'):
+            out.update({f'{f.name}_{k}': t for k, t in zip(v._fields, v) if torch.is_tensor(t)})
+    out['losses'] = losses
+    out['policy_head_weights'] = torch.cat([p.detach().reshape(-1) for p in model.policy_head_parameters() if p.numel()])
+    out['value_head_weights'] = torch.cat([p.detach().reshape(-1) for p in model.value_head_parameters() if p.numel()])
+    return {k: v.detach().to('cpu', torch.float32 if v.is_floating_point() else torch.float64).numpy() for k, v in out.items()}
+
+
+def write_outputs(arrays, path):
+    """DIR/<name>.npy per array, DUMP_BUDGET_BYTES in all.  Smallest first, each array may take an equal share of what the ones before it left;
+    an array larger than its share is written as a fixed sample of its flattened elements (sorted positions drawn from a generator seeded by
+    its name), so runs with the same arguments write the same positions.  At cfg 2 only the two heads' weights (72 + 57 MB) are sampled."""
+    os.makedirs(path, exist_ok=True)
+    left, order = DUMP_BUDGET_BYTES, sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def cpu_baseline(max_threads=16, full_budget_s=150.0, keep=None):
@@ -134,22 +179,24 @@ def _cpu_shard_worker(args):
     return batch * exp['latents'].shape[1], time.perf_counter() - t0
 
 
-def cpu_baseline_sharded(procs=16, threads=4):
+def cpu_baseline_sharded(procs=15, threads=4):
     """The same full workload (B = 256, H + 1 = 16 frames + learn) sharded by dream trajectory over `procs` processes x `threads`
     intra-op threads each (the path shards by trajectory, north_star; measured on the MI355X host, tools/cpu_shard_tune.py: 16 x 4 -> 128
-    steps/s, 32 x 4 -> 86, 32 x 8 -> 33, 16 x 16 -> 29: small per-shard matrices do not feed more threads).  Wall time = the slowest shard, model construction excluded
-    (each worker times its own generate + learn).  Per-shard advantage statistics (no cross-process reduce): baseline only."""
+    steps/s, 32 x 4 -> 86, 32 x 8 -> 33, 16 x 16 -> 29: small per-shard matrices do not feed more threads).  15 workers, not 16: each worker's
+    torch opens the GPU as well, and this process holds it already, so at most 16 processes have it open.  Shards of 17 or 18 trajectories cover
+    all 256.  Wall time = the slowest shard, model construction excluded (each worker times its own generate + learn).  Per-shard advantage
+    statistics (no cross-process reduce): baseline only."""
     import multiprocessing as mp
     host = os.cpu_count() or 1
     procs = max(1, min(procs, host // max(threads, 1)) or 1)
-    per = B_LOCAL // procs
+    sizes = [B_LOCAL // procs + (i < B_LOCAL % procs) for i in range(procs)]
     ctx = mp.get_context('spawn')
     with ctx.Pool(procs) as pool:
-        res = pool.map(_cpu_shard_worker, [(i, per, threads, HORIZON + 1) for i in range(procs)])
+        res = pool.map(_cpu_shard_worker, [(i, sizes[i], threads, HORIZON + 1) for i in range(procs)])
     steps = sum(r[0] for r in res)
     dt = max(r[1] for r in res)
     return dict(value=steps / dt, unit='imagined steps/s', cores=procs * threads, host_cores=host, kind='port',
-                sample=f'oracle/restate.py, the full workload sharded by trajectory: {procs} processes x {threads} threads, each generate(B={per}, '
+                sample=f'oracle/restate.py, the full workload sharded by trajectory: {procs} processes x {threads} threads, each generate(B={min(sizes)}-{max(sizes)}, '
                        f'frames={HORIZON + 1}, num_steps={NUM_STEPS}) + learn(ppo): {steps} imagined steps, slowest shard {dt:.1f} s')
 
 
@@ -360,9 +407,12 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true', help='skip the per-launch HIP-event timing of the GEMMs')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary cfg4 (decode latency) / cfg5 (bf16) measurements')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps also measure the roofline / glue kernels, the CPU baselines, the parity with '
+                                                        'the oracle, the measured peaks and the secondary cfg4 / cfg5 / training-step / fp16x2 keys')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines and the parity with the oracle')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: skip the per-launch HIP-event timing of the GEMMs')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary cfg4 (decode latency) / cfg5 (bf16) measurements')
     ap.add_argument('--allow-experiment-env', action='store_true', help='run although an experiment switch (dreamer4_amd/knobs.py) is set; it is reported in the JSON')
     args = ap.parse_args()
 
@@ -373,14 +423,15 @@ def main():
                                                       'run under); unset them or pass --allow-experiment-env')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher — one process per GPU under torch.distributed.run (trainers.py:1388-1396 leaves
-        # this to `accelerate launch`); rank 0 of the children prints the one JSON line on this process's stdout
+        # this to `accelerate launch`); rank 0 of the children prints the one JSON line on this process's stdout, and this process exits with
+        # the launcher's status
         import socket
         with socket.socket() as sk:
             sk.bind(('127.0.0.1', 0))
             port = sk.getsockname()[1]
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
-                                  '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]])
+        sys.exit(subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
+                                 '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]]).returncode)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     assert world == args.gpus, f'--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}'
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -403,7 +454,7 @@ def main():
     lib = _lib.load()
 
     gpu_headline, headline_error = None, None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # parity at the headline size: the SAME rollout (B = 256, 16 frames) under injected draws with the INITIAL weights (before any optimiser step
         # moves the heads), compared at the end with the oracle run that `cpu_baseline` times anyway (outside the timed region; the oracle is the
         # checker here, never the thing measured)
@@ -414,7 +465,7 @@ def main():
             gpu_headline = model.generate(HORIZON + 1, batch_size=B_LOCAL, return_for_policy_optimization=True, num_steps=NUM_STEPS, noise=nz).cpu()
         except Exception as exc:                          # noqa: BLE001
             gpu_headline, headline_error = None, repr(exc)
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     ncls = lib.d4_profile_classes()
     raw_names = [lib.d4_profile_class_name(i).decode() for i in range(ncls)]
     is_split = [n.startswith(('gemm_x3_kernel', 'gemm_x3sk_kernel')) for n in raw_names]     # fp32 GEMM on the bf16 matrix cores: split operands, 6 bf16 MFMA products per fp32 product
@@ -424,8 +475,33 @@ def main():
     dom, dom2, warm_classes, warm_exec, glue_measured, fused_flops = None, None, None, (0., 0.), None, 0.
     for w in range(args.warmup):
         trainer.train_step()                             # the default path: tile autotuning at first use, the decode frames' hipGraphs captured
+    torch.cuda.synchronize()
+
+    # ---- the timed region: the DEFAULT product path (no per-launch events; decode frames replayed from hipGraphs where the engine's rule says so)
+    gen_ms, learn_ms = [], []
+    frames_total = 0
+    parallel.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3 * args.steps)]
+    for k in range(args.steps):
+        ev[3 * k].record()
+        dreams = trainer.generate()
+        ev[3 * k + 1].record()
+        losses = trainer.learn(dreams)
+        ev[3 * k + 2].record()
+        frames_total += dreams.latents.shape[1]
+    parallel.barrier()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    for k in range(args.steps):
+        gen_ms.append(ev[3 * k].elapsed_time(ev[3 * k + 1]))
+        learn_ms.append(ev[3 * k + 1].elapsed_time(ev[3 * k + 2]))
+    if args.dump_outputs and rank == 0:
+        write_outputs(timed_outputs(model, dreams, losses), args.dump_outputs)
+
     if timing:
-        # one EXTRA untimed step with every GEMM / glue class event-timed: finds the dominant class and measures the glue kernels.  Per-launch
+        # one EXTRA step after the timed ones, every GEMM / glue class event-timed: finds the dominant class and measures the glue kernels.  Per-launch
         # events cannot ride inside a replayed hipGraph, so this step enqueues its frames eagerly — the same kernels by the same rules
         # (tests/test_gpu_generate.py::test_eager_and_graph_replayed_frames_run_the_same_kernels_bitwise), a different launch mechanism.
         torch.cuda.synchronize()
@@ -455,30 +531,8 @@ def main():
         warm_classes = {names[i]: dict(ms=round(ms[i], 2), tflops=round(fl[i] / max(ms[i], 1e-9) / 1e9, 2), launches=int(cnt[i]))
                         for i in range(ncls) if cnt[i]}
         warm_exec = (sum(fl[i] for i in range(ncls)), sum(ms[i] for i in range(ncls)))      # EXECUTED flops / GEMM time of one step
-    torch.cuda.synchronize()
 
-    # ---- the timed region: the DEFAULT product path (no per-launch events; decode frames replayed from hipGraphs where the engine's rule says so)
-    gen_ms, learn_ms = [], []
-    frames_total = 0
-    parallel.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3 * args.steps)]
-    for k in range(args.steps):
-        ev[3 * k].record()
-        dreams = trainer.generate()
-        ev[3 * k + 1].record()
-        trainer.learn(dreams)
-        ev[3 * k + 2].record()
-        frames_total += dreams.latents.shape[1]
-    parallel.barrier()
-    torch.cuda.synchronize()
-    wall = time.perf_counter() - t0
-    for k in range(args.steps):
-        gen_ms.append(ev[3 * k].elapsed_time(ev[3 * k + 1]))
-        learn_ms.append(ev[3 * k + 1].elapsed_time(ev[3 * k + 2]))
-
-    # ---- roofline pass: the SAME steps repeated right after the timed region with a HIP-event pair on every EVENT_STRIDE-th launch of the dominant
+    # ---- roofline pass: the SAME steps repeated right after that step with a HIP-event pair on every EVENT_STRIDE-th launch of the dominant
     # GEMM class (and of the largest class of the other instruction family).  Outside `value`: events force the eager launch mechanism.
     ev_ms_per_step = None
     if timing:
@@ -571,7 +625,7 @@ def main():
         rollout_steps_per_sec=round(world * B_LOCAL * (HORIZON + 1) / (sum(gen_ms) / len(gen_ms) * 1e-3), 1),
         roofline=roofline,
     )
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         del trainer, model
         torch.cuda.empty_cache()
         try:
@@ -584,7 +638,7 @@ def main():
                 out[key] = fn()
             except Exception as exc:                  # noqa: BLE001
                 out[key + '_error'] = repr(exc)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         kept = {}
         out['cpu_baseline'] = cpu_baseline(keep=kept)
         out['speedup_vs_cpu_baseline'] = round(value / out['cpu_baseline']['value'], 1)

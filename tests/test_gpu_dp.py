@@ -60,17 +60,20 @@ def test_two_ranks_over_rccl_equal_one_process_at_the_global_batch():
 
 
 @pytest.mark.parametrize('launch', ['torch.distributed.run', 'bare', 'bare8'])
-def test_bench_runs_its_multi_rank_path_with_two_ranks(launch):
+def test_bench_runs_its_multi_rank_path_with_two_ranks(launch, tmp_path):
     """bench.py launched as the driver launches it for N = 2 (torch.distributed.run, one rank per process): strict tile table (no rank times GEMM
     tiles on its own clock), barrier + max-over-ranks timing, per-rank skew, value = the units ALL ranks processed / that time.  Two ranks share
     the test box's one GPU over gloo (D4_BENCH_BACKEND; RCCL wants a device per rank) - the collective calls and the control flow are the N-rank ones.
-    'bare': `python bench.py --gpus 2` with no launcher and no WORLD_SIZE — bench.py re-executes itself under torch.distributed.run (one process per
+    'bare': `python bench.py --gpus 2` with no launcher and no WORLD_SIZE — bench.py starts torch.distributed.run as a child (one process per
     GPU) and still prints exactly one JSON line.  'bare8': the same with EIGHT ranks, the 8-GPU lease's shape rehearsed on one device: eight engines,
-    eight strict tile-table loads, the rank-0-only line with n_gpus 8, global batch 2048, dp8."""
+    eight strict tile-table loads, the rank-0-only line with n_gpus 8, global batch 2048, dp8.  --dump-outputs: rank 0 writes its last timed
+    step's rollout, losses and head weights."""
     import json
+    import numpy as np
     n = 8 if launch == 'bare8' else 2
     env = dict(os.environ, D4_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    tail = [os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '1', '--warmup', '1']
+    dump = tmp_path / 'outputs'
+    tail = [os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '1', '--warmup', '1', '--dump-outputs', str(dump)]
     if launch.startswith('bare'):
         cmd = [sys.executable, *tail]
         for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
@@ -85,3 +88,9 @@ def test_bench_runs_its_multi_rank_path_with_two_ranks(launch):
     assert d['n_gpus'] == n and d['config']['global_batch'] == 256 * n and d['scaling'] == 'weak' and d['config']['parallelism'] == f'dp{n}'
     assert abs(d['value'] - n * 256 * 16 / (d['ms_per_step'] * 1e-3)) < 0.01 * d['value']
     assert d['per_rank']['generate_ms_max'] >= d['per_rank']['generate_ms_min'] > 0 and 'cpu_baseline' not in d and 'cfg5_bf16' not in d
+    files = sorted(p.name for p in dump.iterdir())
+    assert {'latents.npy', 'values.npy', 'actions_discrete.npy', 'losses.npy', 'policy_head_weights.npy', 'value_head_weights.npy'} <= set(files), files
+    arrays = {f: np.load(dump / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays['latents.npy'].shape == (256, 16, 32, 32) and arrays['losses.npy'].shape == (2,)

@@ -362,6 +362,33 @@ def test_bench_launches_itself_for_several_gpus():
     assert 'needs an MI355X' in out.stderr and 'WORLD_SIZE=1' not in out.stderr, out.stderr[-2000:]
 
 
+def test_bench_dumps_what_the_timed_step_returned_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: every tensor of the Experience (Actions per field), the losses and both heads' weights, floating as float32 and
+    integer / bool as float64; arrays that do not fit the 64 MB budget are written as a fixed sample, the same positions on every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    m = small_model()
+    B, T = 3, 4
+    exp = Experience(latents=torch.randn(B, T, 6, 8), rewards=torch.randn(B, T), values=torch.randn(B, T), lens=torch.full((B,), T),
+                     terminals=torch.zeros(B, dtype=torch.bool), actions=Actions(torch.randint(0, 4, (B, T, 1)), None),
+                     log_probs=Actions(torch.randn(B, T, 1), None), step_size=4)
+    out = bench.timed_outputs(m, exp, torch.tensor([0.5, 1.5]))
+    assert {'latents', 'rewards', 'values', 'lens', 'terminals', 'actions_discrete', 'log_probs_discrete', 'losses', 'policy_head_weights',
+            'value_head_weights'} == set(out)
+    assert out['latents'].dtype == np.float32 and out['actions_discrete'].dtype == np.float64 and out['terminals'].dtype == np.float64
+    assert np.array_equal(out['actions_discrete'], exp.actions.discrete.numpy())
+    assert out['policy_head_weights'].size == sum(p.numel() for p in m.policy_head_parameters())
+    arrays = {'small': np.arange(10, dtype=np.float64), 'mid': np.ones(4 << 20, np.float32), 'big': np.arange(24 << 20, dtype=np.float32)}
+    for d in ('a', 'b'):
+        bench.write_outputs(arrays, str(tmp_path / d))
+    sizes = {f.name: f.stat().st_size for f in (tmp_path / 'a').iterdir()}
+    assert sum(sizes.values()) <= 64 * 10 ** 6 and set(sizes) == {'small.npy', 'mid.npy', 'big.npy'}
+    assert np.array_equal(np.load(tmp_path / 'a' / 'small.npy'), arrays['small']) and np.load(tmp_path / 'a' / 'mid.npy').size == 4 << 20
+    big = np.load(tmp_path / 'a' / 'big.npy')
+    assert 0 < big.size < arrays['big'].size and np.all(np.diff(big) >= 0) and np.array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))
+
+
 def test_state_dict_without_tokenizer_keys_needs_an_explicit_opt_in():
     """The tokenizer is a registered submodule (reference: dreamer4.py:4787-4794): a strict load of a checkpoint without `video_tokenizer.*` keys raises, as
     the reference's does.  A checkpoint from before the tokenizer was registered loads with allow_missing_tokenizer=True: the constructor's tokenizer keeps
