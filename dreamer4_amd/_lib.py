@@ -91,6 +91,12 @@ SYMBOLS = {
     'd4_wm_forward': (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     'd4_decoder_forward': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'd4_ff_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
+    'd4_train_arith_set': (_I, [_I]),
+    'd4_train_arith_get': (_I, []),
+    'd4_train_scratch_bind': (_I, [_P, C.c_size_t]),
+    'd4_ff_bf16_scratch_bytes': (C.c_size_t, [_I] * 3),
+    'd4_attn_bf16_scratch_bytes': (C.c_size_t, [_I] * 4),
+    'd4_cross_attn_bf16_scratch_bytes': (C.c_size_t, [_I] * 7),
     'd4_ff_forward': (_I, [_P] * 6 + [_I, _I, _I, _P, _P, C.c_size_t, _P]),
     'd4_ff_backward': (_I, [_P] * 6 + [_I, _I, _I] + [_P] * 6 + [_P, C.c_size_t, _P]),
     'd4_ff_backward_saved': (_I, [_P] * 6 + [_I, _I, _I] + [_P] * 6 + [_P, C.c_size_t, _P]),
@@ -129,6 +135,7 @@ SYMBOLS = {
     'd4_debug_buffer': (_I, [_P, C.c_char_p, C.POINTER(_P)]),
     'd4_gemm': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     'd4_gemm_tn': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, C.c_int64, _I, _I, _P]),
+    'd4_gemm_tn_bf16': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, C.c_int64, _I, _P]),
     'd4_gemm_pair': (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     'd4_gemm_batched': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _L, _L, _L, _P]),
     'd4_gemm_bf16': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P]),

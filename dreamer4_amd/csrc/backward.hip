@@ -13,6 +13,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "../../include/d4hip.h"
+#include <atomic>
 #include <float.h>
 
 namespace d4 {
@@ -48,16 +49,108 @@ __global__ void swiglu_bwd_kernel(const float* h, const float* du, float* dh, in
 }
 static dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)); }
 
-static int gemm_b(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, int M, int N, int K, int flags, hipStream_t s) {
+static int gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, int M, int N, int K, int flags, hipStream_t s) {
     GemmArgs g{A, lda, W, ldw, C, ldc, bias, nullptr, 0, M, N, K, flags, 0.f};
     return gemm(g, s);
+}
+
+// ------------------------------------------------------------------------------------------------ bf16 training arithmetic
+// d4_train_arith_set(1): the three products of every Linear of the blocks (forward, input gradient, weight gradient) take bf16 images of their
+// operands (round to nearest even, built into a scratch the caller binds for the call: d4_train_scratch_bind) on the bf16 matrix pipe, fp32 accumulate and
+// fp32 results; everything else of a block is the fp32 path unchanged.  Which products: a rule on the Linear's shape only —
+// out features >= 16 and in features >= 16 (so the forward / input-gradient product has N >= 16, K >= 16 and the weight-gradient product M >= 16,
+// N >= 16), any number of rows; the heads-wide gate and mix projections are separate fp32 products by construction.
+static std::atomic<int> g_train_arith{0};
+struct Bf16Ctx {
+    uint16_t *a = nullptr, *b = nullptr, *w = nullptr; size_t act = 0, wgt = 0;      // images: two activation-sized, one weight-sized (elements)
+    const float* a_src = nullptr; int a_ld = 0, a_rows = 0, a_cols = 0;               // what image `a` holds: a dY feeds two products of one call
+};
+static thread_local Bf16Ctx t_bf;
+struct Bf16Scratch { void* p = nullptr; size_t bytes = 0; };
+static thread_local Bf16Scratch t_scratch;       // d4_train_scratch_bind: this thread's scratch for the bf16 images of its next block calls
+// image `a` = bf16 of rows x cols of src at row stride r64(cols), pad columns zero; converted once per call and source (no buffer of a block
+// is rewritten between the two products that read it; the kernels that WRITE such a buffer call image_a_written on it all the same, so
+// that a reordered backward cannot meet a stale image)
+static inline void image_a_written(const float* buf) { if (t_bf.a_src == buf) t_bf.a_src = nullptr; }
+static int image_a(const float* src, int ld, int rows, int cols, hipStream_t s) {
+    Bf16Ctx& c = t_bf;
+    if (c.a_src == src && c.a_ld == ld && c.a_rows == rows && c.a_cols == cols) return 0;
+    const int cp = (cols + 63) / 64 * 64;
+    if (int rc = cvt_pad_bf16(src, ld, c.a, cp, rows, cols, cp, s)) return rc;
+    c.a_src = src; c.a_ld = ld; c.a_rows = rows; c.a_cols = cols;
+    return 0;
+}
+static inline size_t r64(size_t n) { return (n + 63) / 64 * 64; }
+static inline bool bf16_rule(int out_features, int in_features) { return out_features >= 16 && in_features >= 16; }
+// scratch (bytes) of a block with `rows` token rows, activations up to `width` columns, weights up to wn x wk
+static size_t bf16_extra_bytes(size_t rows, size_t width, size_t wn, size_t wk) {
+    return 2 * (2 * r64(rows * r64(width)) + r64(r64(wn) * r64(wk)));
+}
+struct Bf16Scope {           // carves this thread's bound scratch for the helpers of one entry-point call
+    Bf16Scope() {}
+    ~Bf16Scope() { t_bf = Bf16Ctx{}; }
+    int enter(const char* who, size_t rows, size_t width, size_t wn, size_t wk) {
+        if (!g_train_arith.load(std::memory_order_relaxed)) {
+            D4_REQUIRE(!t_scratch.p, "%s: a bf16 scratch is bound on this thread but the training arithmetic is fp32 (another thread changed d4_train_arith_set?)", who);
+            return 0;
+        }
+        D4_REQUIRE(t_scratch.p && ((uintptr_t)t_scratch.p % 256) == 0 && t_scratch.bytes >= bf16_extra_bytes(rows, width, wn, wk),
+                   "%s: the bf16 training arithmetic needs a 256-byte aligned scratch of the block's *_bf16_scratch_bytes bound on this thread (d4_train_scratch_bind)", who);
+        Bf16Ctx c;
+        c.act = r64(rows * r64(width)); c.wgt = r64(r64(wn) * r64(wk));
+        c.a = reinterpret_cast<uint16_t*>(t_scratch.p); c.b = c.a + c.act; c.w = c.b + c.act;
+        t_bf = c;
+        return 0;
+    }
+};
+
+// Y = A W^T (+ bias): the forward product of a Linear
+static int gemm_b(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, int M, int N, int K, int flags, hipStream_t s) {
+    if (!t_bf.a || (flags & (GEMM_TRANS_A | GEMM_TRANS_B)) || !bf16_rule(N, K)) return gemm_f32(A, lda, W, ldw, C, ldc, bias, M, N, K, flags, s);
+    const int Kp = (int)r64(K);
+    D4_REQUIRE((size_t)M * Kp <= t_bf.act && (size_t)N * Kp <= t_bf.wgt, "bf16 training arithmetic: operand image larger than the scratch (%d x %d x %d)", M, N, K);
+    int rc;
+    if ((rc = image_a(A, lda, M, K, s))) return rc;
+    if ((rc = cvt_pad_bf16(W, ldw, t_bf.w, Kp, N, K, Kp, s))) return rc;
+    GemmArgs g{nullptr, Kp, nullptr, Kp, C, ldc, bias, nullptr, 0, M, N, Kp, flags, 0.f};
+    g.Ab = t_bf.a; g.Wb = t_bf.w;
+    return gemm_bf16a(g, s);
+}
+
+// dX[M][N] (+)= dY[M][K] W[K][N]: the input gradient of a Linear (W [out = K][in = N])
+static int lin_dx(const float* dY, int ldy, const float* W, int ldw, float* dX, int ldx, int M, int N, int K, float* wt, hipStream_t s, bool accumulate = false) {
+    if (!t_bf.a || !bf16_rule(K, N)) {
+        if (!accumulate) return gemm_dx(dY, ldy, W, ldw, dX, ldx, M, N, K, wt, s);
+        return gemm_f32(dY, ldy, W, ldw, dX, ldx, nullptr, M, N, K, GEMM_TRANS_B | GEMM_ACCUMULATE, s);
+    }
+    const int Kp = (int)r64(K);
+    D4_REQUIRE((size_t)M * Kp <= t_bf.act && (size_t)N * Kp <= t_bf.wgt, "bf16 training arithmetic: operand image larger than the scratch (%d x %d x %d)", M, N, K);
+    int rc;
+    if ((rc = image_a(dY, ldy, M, K, s))) return rc;
+    if ((rc = cvt_transpose_bf16(W, ldw, t_bf.w, Kp, K, N, Kp, s))) return rc;
+    GemmArgs g{nullptr, Kp, nullptr, Kp, dX, ldx, nullptr, nullptr, 0, M, N, Kp, accumulate ? GEMM_ACCUMULATE : 0, 0.f};
+    g.Ab = t_bf.a; g.Wb = t_bf.w;
+    return gemm_bf16a(g, s);
 }
 
 // Weight gradient dW[M][N] = A^T B with A [K][M], B [K][N] row-major and K = token rows (thousands to tens of thousands) while M x N is one
 // weight matrix (often only 64 tiles): split K over the grid's batch dimension into partial products, then one fixed-order reduce —
 // without it these GEMMs run on a quarter of the CUs and were half of a training step (tools/train_step_time.py).
 constexpr size_t DW_PART_FLOATS = (size_t)8 << 20;          // partial-product scratch per workspace (32 MB)
+static int gemm_dw_f32(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, hipStream_t s);
 static int gemm_dw(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, hipStream_t s) {
+    if (t_bf.a && bf16_rule(M, N)) {
+        // bf16 training arithmetic: images of dY and X as they lie (rows = the contraction), transposed by the LDS read (gemm_tn_bf16.hip)
+        const int Mp = (int)r64(M), Np = (N + 7) & ~7;          // (dY's image at the stride the input-gradient product reads it with)
+        D4_REQUIRE((size_t)K * Mp <= t_bf.act && (size_t)K * Np <= t_bf.act, "bf16 training arithmetic: operand image larger than the scratch (%d x %d x %d)", M, N, K);
+        int rc;
+        if ((rc = image_a(A, lda, K, M, s))) return rc;
+        if ((rc = cvt_pad_bf16(B, ldb, t_bf.b, Np, K, N, Np, s))) return rc;
+        return gemm_tn_bf16(t_bf.a, Mp, t_bf.b, Np, C, ldc, M, N, K, part, part ? DW_PART_FLOATS : 0, s);
+    }
+    return gemm_dw_f32(A, lda, B, ldb, C, ldc, M, N, K, part, s);
+}
+static int gemm_dw_f32(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, hipStream_t s) {
     // operands read straight into the MFMA layout, k split inside the workgroup and over slices (gemm_tn.hip); the transposed-operand form of
     // the general GEMM below remains for leading dimensions that are not multiples of 4
     if (gemm_tn_applicable(A, lda, B, ldb, C, ldc, M, N, K)) return gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, part, part ? DW_PART_FLOATS : 0, s);
@@ -65,14 +158,14 @@ static int gemm_dw(const float* A, int lda, const float* B, int ldb, float* C, i
     int S = (int)((1024 + tiles - 1) / tiles);
     if (S > K / 256) S = K / 256;
     if ((size_t)S * M * N > DW_PART_FLOATS) S = (int)(DW_PART_FLOATS / ((size_t)M * N));
-    if (S <= 1 || !part) return gemm_b(A, lda, B, ldb, C, ldc, nullptr, M, N, K, GEMM_TRANS_A | GEMM_TRANS_B, s);
+    if (S <= 1 || !part) return gemm_f32(A, lda, B, ldb, C, ldc, nullptr, M, N, K, GEMM_TRANS_A | GEMM_TRANS_B, s);
     const int ks = ((K + S - 1) / S + 31) / 32 * 32;        // k per slice
     const int full = K / ks, rem = K - full * ks;
     int rc;
     GemmArgs g{A, lda, B, ldb, part, N, nullptr, nullptr, 0, M, N, ks, GEMM_TRANS_A | GEMM_TRANS_B, 0.f};
     g.batch = full; g.strideA = (int64_t)ks * lda; g.strideW = (int64_t)ks * ldb; g.strideC = (int64_t)M * N;
     if ((rc = gemm(g, s))) return rc;
-    if (rem > 0 && (rc = gemm_b(A + (int64_t)full * ks * lda, lda, B + (int64_t)full * ks * ldb, ldb, part + (int64_t)full * M * N, N, nullptr, M, N, rem,
+    if (rem > 0 && (rc = gemm_f32(A + (int64_t)full * ks * lda, lda, B + (int64_t)full * ks * ldb, ldb, part + (int64_t)full * M * N, N, nullptr, M, N, rem,
                                 GEMM_TRANS_A | GEMM_TRANS_B, s))) return rc;
     return splitk_reduce(part, full + (rem > 0), M, N, nullptr, 0, C, ldc, s);
 }
@@ -503,6 +596,10 @@ static AttnWs attn_ws(float* base, int R, int F, int D, int heads, int dh) {
     return w;
 }
 
+// bf16-arithmetic scratch of a block (bytes): see bf16_extra_bytes
+static size_t ff_bf16_extra(int R, int D, int I) { const size_t w2 = 2 * (size_t)ff_ip(I); return bf16_extra_bytes(R, w2 > (size_t)D ? w2 : D, w2, D); }
+static size_t attn_bf16_extra(int R, int D, int hd) { return bf16_extra_bytes(R, 3 * hd > D ? 3 * hd : D, 3 * hd, D); }
+
 struct AttnParams { const float *norm_w, *wq, *wk, *wv, *wo, *wg, *wm, *bm, *gamma; };
 
 // concatenated projection [q | k | v | gates (hp4) | mix (hp4)] and the forward up to the projections
@@ -521,7 +618,10 @@ static int attn_project(const AttnWs& w, const float* x, const AttnParams& prm, 
         if ((rc = multi_copy(mc, s))) return rc;
     }
     if ((rc = rmsnorm_rows(x, D, prm.norm_w, w.xn, D, R, D, RMS_EPS, s))) return rc;
-    return gemm_b(w.xn, D, w.wcat, D, w.proj, w.P, w.bcat, R, w.P, D, 0, s);
+    if (!t_bf.a) return gemm_b(w.xn, D, w.wcat, D, w.proj, w.P, w.bcat, R, w.P, D, 0, s);
+    // bf16 training arithmetic: q | k | v (their bias rows are zero) on the bf16 pipe, the heads-wide gate and mix logits stay an fp32 product
+    if ((rc = gemm_b(w.xn, D, w.wcat, D, w.proj, w.P, nullptr, R, 3 * hd, D, 0, s))) return rc;
+    return gemm_f32(w.xn, D, w.wcat + (size_t)3 * hd * D, D, w.proj + 3 * hd, w.P, w.bcat + 3 * hd, R, w.P - 3 * hd, D, 0, s);
 }
 
 }  // namespace d4
@@ -531,6 +631,10 @@ using namespace d4;
 extern "C" {
 
 size_t d4_ff_workspace_bytes(int rows, int dim, int inner) { return ff_ws(nullptr, rows, dim, inner).total * sizeof(float); }
+size_t d4_ff_bf16_scratch_bytes(int rows, int dim, int inner) { return ff_bf16_extra(rows, dim, inner); }
+int d4_train_scratch_bind(void* scratch, size_t bytes) { t_scratch.p = scratch; t_scratch.bytes = scratch ? bytes : 0; return 0; }
+int d4_train_arith_set(int arith) { return g_train_arith.exchange(arith ? 1 : 0); }
+int d4_train_arith_get(void) { return g_train_arith.load(); }
 
 int d4_ff_forward(const float* x, const float* norm_w, const float* w_in, const float* b_in, const float* w_out, const float* b_out,
                   int rows, int dim, int inner, float* y, float* workspace, size_t workspace_bytes, void* stream) {
@@ -542,6 +646,8 @@ int d4_ff_forward(const float* x, const float* norm_w, const float* w_in, const 
     const FfWs w = ff_ws(workspace, rows, dim, inner);
     const int Ip = ff_ip(inner);
     int rc;
+    Bf16Scope bf;
+    if ((rc = bf.enter("d4_ff_forward", rows, Ip * 2 > dim ? Ip * 2 : dim, 2 * Ip, dim))) return rc;
     if ((rc = ff_recompute(w, x, norm_w, w_in, b_in, w_out, rows, dim, inner, s))) return rc;
     return gemm_b(w.u, Ip, w.w2p, Ip, y, dim, b_out, rows, dim, Ip, 0, s);
 }
@@ -559,13 +665,16 @@ static int ff_backward_impl(const float* x, const float* dy, const float* norm_w
     const int R = rows, D = dim, I = inner, Ip = ff_ip(inner);
     const FfWs w = ff_ws(workspace, R, D, I);
     int rc;
+    Bf16Scope bf;
+    if ((rc = bf.enter("d4_ff_backward", R, Ip * 2 > D ? Ip * 2 : D, 2 * Ip, D))) return rc;
     if (!reuse && (rc = ff_recompute(w, x, norm_w, w_in, b_in, w_out, R, D, I, s))) return rc;
     // y = u W2^T + b2
     if ((rc = gemm_dw(dy, D, w.u, Ip, w.dw2p, Ip, D, Ip, R, w.part, s))) return rc;                                    // dW2 = dy^T u
     if ((rc = copy_rows(w.dw2p, Ip, d_w_out, I, D, I, s))) return rc;
-    if ((rc = gemm_dx(dy, D, w.w2p, Ip, w.du, Ip, R, Ip, D, w.wt, s))) return rc;                                        // du = dy W2
+    if ((rc = lin_dx(dy, D, w.w2p, Ip, w.du, Ip, R, Ip, D, w.wt, s))) return rc;                                        // du = dy W2
     hipLaunchKernelGGL(swiglu_bwd_kernel, grid_for((int64_t)R * Ip), dim3(256), 0, s, w.h, w.du, w.dh, R, I, Ip);
     D4_LAUNCH_CHECK();
+    image_a_written(w.dh);
     // h = xn W1^T + b1
     if ((rc = gemm_dw(w.dh, 2 * Ip, w.xn, D, w.dw1p, D, 2 * Ip, D, R, w.part, s))) return rc;                          // dW1 = dh^T xn
     {
@@ -573,7 +682,7 @@ static int ff_backward_impl(const float* x, const float* dy, const float* norm_w
         mc.add(d_w_in, w.dw1p, (int64_t)I * D); mc.add(d_w_in + (size_t)I * D, w.dw1p + (size_t)Ip * D, (int64_t)I * D);
         if ((rc = multi_copy(mc, s))) return rc;
     }
-    if ((rc = gemm_dx(w.dh, 2 * Ip, w.w1p, D, w.dxn, D, R, D, 2 * Ip, w.wt, s))) return rc;                             // dxn = dh W1
+    if ((rc = lin_dx(w.dh, 2 * Ip, w.w1p, D, w.dxn, D, R, D, 2 * Ip, w.wt, s))) return rc;                             // dxn = dh W1
     // xn = rmsnorm(x) * gamma
     if ((rc = rmsnorm_bwd(x, w.dxn, norm_w, w.tg, dx, R, D, RMS_EPS, s))) return rc;
     // the four column sums of the block (both bias gradients, the norm gain's) in one launch: their operands are all still in place
@@ -596,6 +705,7 @@ int d4_ff_backward_saved(const float* x, const float* dy, const float* norm_w, c
 size_t d4_attn_workspace_bytes(int frames, int tokens, int dim, int heads, int dim_head) {
     return attn_ws(nullptr, frames * tokens, frames, dim, heads, dim_head).total * sizeof(float);
 }
+size_t d4_attn_bf16_scratch_bytes(int rows, int dim, int heads, int dim_head) { return attn_bf16_extra(rows, dim, heads * dim_head); }
 
 }  // extern "C"
 
@@ -627,6 +737,8 @@ int attn_block_forward(const float* x, const float* residual_values, const AttnP
     const int R = rows, hd = heads * dim_head;
     if (R == 0) return 0;
     const AttnWs w = attn_ws(workspace, R, g.groups, dim, heads, dim_head);
+    Bf16Scope bf;
+    if ((rc = bf.enter("attention forward", R, 3 * hd > dim ? 3 * hd : dim, 3 * hd, dim))) return rc;
     if ((rc = attn_project(w, x, prm, R, dim, heads, dim_head, residual_values != nullptr, s))) return rc;
     AttnBwdArgs a{w.proj, w.P, residual_values, prm.gamma, nullptr, w.o3, nullptr, nullptr, nullptr, g.groups, g.items, heads, w.hp4, softclamp, g.num_special, belief};
     set_geom(a, g);
@@ -648,12 +760,15 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
     const int R = rows, D = dim, hd = heads * dim_head;
     const bool has_rv = residual_values != nullptr;
     const AttnWs w = attn_ws(workspace, R, g.groups, D, heads, dim_head);
+    Bf16Scope bf;
+    if ((rc = bf.enter("attention backward", R, 3 * hd > D ? 3 * hd : D, 3 * hd, D))) return rc;
     if (!reuse && (rc = attn_project(w, x, prm, R, D, heads, dim_head, has_rv, s))) return rc;     // reuse: the forward's xn / wcat / proj are still there
     // out = o3 Wo^T
-    if ((rc = gemm_dx(dy, D, prm.wo, hd, w.d_o3, hd, R, hd, D, w.wt, s))) return rc;                                     // d_o3 = dy Wo
+    if ((rc = lin_dx(dy, D, prm.wo, hd, w.d_o3, hd, R, hd, D, w.wt, s))) return rc;                                     // d_o3 = dy Wo
     AttnBwdArgs a{w.proj, w.P, residual_values, prm.gamma, w.d_o3, w.o3, w.dproj, o.d_rv, w.gpart, g.groups, g.items, heads, w.hp4, softclamp, g.num_special, belief};
     set_geom(a, g);
     if ((rc = attn_core(a, dim_head, s))) return rc;
+    image_a_written(w.dproj);
     // the pad columns of the gate / mix logits and of the row carry no gradient
     if (w.hp4 > heads) hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)R * (w.hp4 - heads)), dim3(256), 0, s, w.dproj, R, w.P, 3 * hd + heads, 3 * hd + w.hp4);
     if (w.P > 3 * hd + w.hp4 + heads)
@@ -661,7 +776,11 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
     D4_LAUNCH_CHECK();
     if ((rc = gemm_dw(dy, D, w.o3, hd, o.d_wo, hd, D, hd, R, w.part, s))) return rc;                                     // dWo = dy^T o3
     // projections: dW = dproj^T xn, dxn = dproj Wcat
-    if ((rc = gemm_dw(w.dproj, w.P, w.xn, D, w.dwcat, D, w.P, D, R, w.part, s))) return rc;
+    if (!t_bf.a) { if ((rc = gemm_dw(w.dproj, w.P, w.xn, D, w.dwcat, D, w.P, D, R, w.part, s))) return rc; }
+    else {          // q | k | v rows on the bf16 pipe, the gate / mix rows in fp32
+        if ((rc = gemm_dw(w.dproj, w.P, w.xn, D, w.dwcat, D, 3 * hd, D, R, w.part, s))) return rc;
+        if ((rc = gemm_dw_f32(w.dproj + 3 * hd, w.P, w.xn, D, w.dwcat + (size_t)3 * hd * D, D, w.P - 3 * hd, D, R, w.part, s))) return rc;
+    }
     {
         const int64_t blk = (int64_t)hd * D;
         MultiCopy mc;
@@ -670,7 +789,11 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
         if (has_rv) mc.add(o.d_wm, w.dwcat + (size_t)(3 * hd + w.hp4) * D, (int64_t)heads * D);
         if ((rc = multi_copy(mc, s))) return rc;
     }
-    if ((rc = gemm_dx(w.dproj, w.P, w.wcat, D, w.dxn, D, R, D, w.P, w.wt, s))) return rc;
+    if (!t_bf.a) { if ((rc = lin_dx(w.dproj, w.P, w.wcat, D, w.dxn, D, R, D, w.P, w.wt, s))) return rc; }
+    else {          // the fp32 gate / mix part first, then the q | k | v part added on the bf16 pipe
+        if ((rc = gemm_dx(w.dproj + 3 * hd, w.P, w.wcat + (size_t)3 * hd * D, D, w.dxn, D, R, D, w.P - 3 * hd, w.wt, s))) return rc;
+        if ((rc = lin_dx(w.dproj, w.P, w.wcat, D, w.dxn, D, R, D, 3 * hd, w.wt, s, true))) return rc;
+    }
     if ((rc = rmsnorm_bwd(x, w.dxn, prm.norm_w, w.tg, o.dx, R, D, RMS_EPS, s))) return rc;
     ColsumBatch cb;                                    // key gain, mix bias, norm gain: one launch
     cb.add(w.gpart, hd, g.groups, hd, o.d_gamma);
@@ -714,8 +837,17 @@ int x_project(const XWs& w, const float* q_tokens, const float* ctx, const XPara
     if ((rc = rmsnorm_rows(q_tokens, D, prm.norm_w, w.qn, D, Rq, D, RMS_EPS, s))) return rc;
     if (prm.norm_ctx_w) { if ((rc = rmsnorm_rows(ctx, Dc, prm.norm_ctx_w, w.cn, Dc, Rk, Dc, RMS_EPS, s))) return rc; }
     else if ((rc = copy_rows(ctx, Dc, w.cn, Dc, Rk, Dc, s))) return rc;
-    if ((rc = gemm_b(w.qn, D, w.wqg, D, w.projq, w.Pq, nullptr, Rq, w.Pq, D, 0, s))) return rc;
+    if (!t_bf.a) { if ((rc = gemm_b(w.qn, D, w.wqg, D, w.projq, w.Pq, nullptr, Rq, w.Pq, D, 0, s))) return rc; }
+    else {          // bf16 training arithmetic: the queries on the bf16 pipe, the heads-wide gate logits an fp32 product
+        if ((rc = gemm_b(w.qn, D, w.wqg, D, w.projq, w.Pq, nullptr, Rq, hd, D, 0, s))) return rc;
+        if ((rc = gemm_f32(w.qn, D, w.wqg + (size_t)hd * D, D, w.projq + hd, w.Pq, nullptr, Rq, w.Pq - hd, D, 0, s))) return rc;
+    }
     return gemm_b(w.cn, Dc, w.wkv, Dc, w.projk, w.Pk, nullptr, Rk, w.Pk, Dc, 0, s);
+}
+
+size_t x_bf16_extra(int Rq, int Rk, int D, int Dc, int hd) {
+    const int dm = D > Dc ? D : Dc;
+    return bf16_extra_bytes(Rq > Rk ? Rq : Rk, 2 * hd > dm ? 2 * hd : dm, 2 * hd > dm ? 2 * hd : dm, 2 * hd > dm ? 2 * hd : dm);
 }
 
 int x_check(int G, int nq, int nk, int D, int Dc, int heads, int dh, const float* workspace, size_t workspace_bytes) {
@@ -733,6 +865,9 @@ extern "C" {
 size_t d4_cross_attn_workspace_bytes(int groups, int nq, int nk, int dim, int dim_ctx, int heads, int dim_head) {
     return x_ws(nullptr, groups * nq, groups * nk, groups, dim, dim_ctx, heads, dim_head).total * sizeof(float);
 }
+size_t d4_cross_attn_bf16_scratch_bytes(int groups, int nq, int nk, int dim, int dim_ctx, int heads, int dim_head) {
+    return x_bf16_extra(groups * nq, groups * nk, dim, dim_ctx, heads * dim_head);
+}
 
 int d4_cross_attn_forward(const float* q_tokens, const float* ctx, const float* norm_w, const float* norm_ctx_w, const float* wq, const float* wk,
                           const float* wv, const float* wo, const float* w_gates, const float* k_gamma, int groups, int nq, int nk, int ctx_item_major,
@@ -745,6 +880,11 @@ int d4_cross_attn_forward(const float* q_tokens, const float* ctx, const float* 
     if (Rq == 0) return 0;
     const XWs w = x_ws(workspace, Rq, Rk, groups, dim, dim_ctx, heads, dim_head);
     const XParams prm{norm_w, norm_ctx_w, wq, wk, wv, wo, w_gates, k_gamma};
+    Bf16Scope bf;
+    {
+        const int dm = dim > dim_ctx ? dim : dim_ctx, wd = 2 * hd > dm ? 2 * hd : dm;
+        if ((rc = bf.enter("d4_cross_attn_forward", Rq > Rk ? Rq : Rk, wd, wd, wd))) return rc;
+    }
     if ((rc = x_project(w, q_tokens, ctx, prm, Rq, Rk, dim, dim_ctx, heads, dim_head, s))) return rc;
     XAttnArgs a{w.projq, w.Pq, w.projk, w.Pk, k_gamma, nullptr, w.o3, nullptr, nullptr, nullptr, groups, nq, nk, heads, ctx_item_major, softclamp};
     if ((rc = xattn_core(a, dim_head, s))) return rc;
@@ -766,18 +906,31 @@ static int cross_attn_backward_impl(const float* q_tokens, const float* ctx, con
     const int Rq = groups * nq, Rk = groups * nk, D = dim, Dc = dim_ctx, hd = heads * dim_head;
     const XWs w = x_ws(workspace, Rq, Rk, groups, D, Dc, heads, dim_head);
     const XParams prm{norm_w, norm_ctx_w, wq, wk, wv, wo, w_gates, k_gamma};
+    Bf16Scope bf;
+    {
+        const int dm = D > Dc ? D : Dc, wd = 2 * hd > dm ? 2 * hd : dm;
+        if ((rc = bf.enter("d4_cross_attn_backward", Rq > Rk ? Rq : Rk, wd, wd, wd))) return rc;
+    }
     if (!reuse && (rc = x_project(w, q_tokens, ctx, prm, Rq, Rk, D, Dc, heads, dim_head, s))) return rc;
-    if ((rc = gemm_dx(dy, D, wo, hd, w.d_o3, hd, Rq, hd, D, w.wt, s))) return rc;
+    if ((rc = lin_dx(dy, D, wo, hd, w.d_o3, hd, Rq, hd, D, w.wt, s))) return rc;
     XAttnArgs a{w.projq, w.Pq, w.projk, w.Pk, k_gamma, w.d_o3, w.o3, w.dprojq, w.dprojk, w.gpart, groups, nq, nk, heads, ctx_item_major, softclamp};
     if ((rc = xattn_core(a, dim_head, s))) return rc;
+    image_a_written(w.dprojq); image_a_written(w.dprojk);
     if (w.hp4 > heads) {
         hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)Rq * (w.hp4 - heads)), dim3(256), 0, s, w.dprojq, Rq, w.Pq, hd + heads, w.Pq);
         D4_LAUNCH_CHECK();
     }
     if ((rc = gemm_dw(dy, D, w.o3, hd, d_wo, hd, D, hd, Rq, w.part, s))) return rc;
     // query side
-    if ((rc = gemm_dw(w.dprojq, w.Pq, w.qn, D, w.dwqg, D, w.Pq, D, Rq, w.part, s))) return rc;
-    if ((rc = gemm_dx(w.dprojq, w.Pq, w.wqg, D, w.dqn, D, Rq, D, w.Pq, w.wt, s))) return rc;
+    if (!t_bf.a) {
+        if ((rc = gemm_dw(w.dprojq, w.Pq, w.qn, D, w.dwqg, D, w.Pq, D, Rq, w.part, s))) return rc;
+        if ((rc = lin_dx(w.dprojq, w.Pq, w.wqg, D, w.dqn, D, Rq, D, w.Pq, w.wt, s))) return rc;
+    } else {        // query rows on the bf16 pipe, gate rows in fp32 (as in x_project)
+        if ((rc = gemm_dw(w.dprojq, w.Pq, w.qn, D, w.dwqg, D, hd, D, Rq, w.part, s))) return rc;
+        if ((rc = gemm_dw_f32(w.dprojq + hd, w.Pq, w.qn, D, w.dwqg + (size_t)hd * D, D, w.Pq - hd, D, Rq, w.part, s))) return rc;
+        if ((rc = gemm_dx(w.dprojq + hd, w.Pq, w.wqg + (size_t)hd * D, D, w.dqn, D, Rq, D, w.Pq - hd, w.wt, s))) return rc;
+        if ((rc = lin_dx(w.dprojq, w.Pq, w.wqg, D, w.dqn, D, Rq, D, hd, w.wt, s, true))) return rc;
+    }
     if ((rc = rmsnorm_bwd(q_tokens, w.dqn, norm_w, w.tg, d_q_tokens, Rq, D, RMS_EPS, s))) return rc;
     {
         ColsumBatch cb;                                // key gain and the query norm's gain: one launch
@@ -793,11 +946,11 @@ static int cross_attn_backward_impl(const float* q_tokens, const float* ctx, con
         if ((rc = multi_copy(mc, s))) return rc;
     }
     if (norm_ctx_w) {
-        if ((rc = gemm_dx(w.dprojk, w.Pk, w.wkv, Dc, w.dcn, Dc, Rk, Dc, w.Pk, w.wt, s))) return rc;
+        if ((rc = lin_dx(w.dprojk, w.Pk, w.wkv, Dc, w.dcn, Dc, Rk, Dc, w.Pk, w.wt, s))) return rc;
         if ((rc = rmsnorm_bwd(ctx, w.dcn, norm_ctx_w, w.tgc, d_ctx, Rk, Dc, RMS_EPS, s))) return rc;
         return colsum(w.tgc, Dc, Rk, Dc, d_norm_ctx_w, s, w.part, DW_PART_FLOATS);
     }
-    return gemm_dx(w.dprojk, w.Pk, w.wkv, Dc, d_ctx, Dc, Rk, Dc, w.Pk, w.wt, s);
+    return lin_dx(w.dprojk, w.Pk, w.wkv, Dc, d_ctx, Dc, Rk, Dc, w.Pk, w.wt, s);
 }
 
 #define D4_XBWD_PARAMS const float* q_tokens, const float* ctx, const float* dy, const float* norm_w, const float* norm_ctx_w, const float* wq,          \

@@ -270,6 +270,16 @@ int gemm_dx(const float* dY, int ldy, const float* W, int ldw, float* dX, int ld
 bool gemm_tn_applicable(const float* A, int lda, const float* B, int ldb, const float* C, int ldc, int M, int N, int K);
 int gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, size_t part_floats, hipStream_t s,
             int forced_tn = 0, int forced_slices = 0);
+// weight-gradient GEMM on the bf16 matrix pipe (gemm_tn_bf16.hip): A [K][lda], B [K][ldb] bf16 images (lda, ldb % 8 == 0 and >= M, N rounded up
+// to 8), C fp32; transposed LDS reads feed the MFMA; slices by a shape rule (forced_slices = 0), partial products summed in slice order
+bool gemm_tn_bf16_applicable(const uint16_t* A, int lda, const uint16_t* B, int ldb, const float* C, int ldc, int M, int N, int K);
+int gemm_tn_bf16_slices(int M, int N, int K, size_t part_floats);
+int gemm_tn_bf16(const uint16_t* A, int lda, const uint16_t* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, size_t part_floats, hipStream_t s,
+                 int forced_slices = 0);
+// bf16 operand images of the training arithmetic: rows x cols fp32 -> bf16 (RNE) with columns [cols, cols_pad) zero; and the transposed form
+// dst[c][r] = bf16(src[r][c]), r < rows_pad (zeros past rows)
+int cvt_pad_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int rows, int cols, int cols_pad, hipStream_t s);
+int cvt_transpose_bf16(const float* src, int lds, uint16_t* dst, int ldd, int rows, int cols, int rows_pad, hipStream_t s);
 int prep_eval_inputs(int32_t* sig, int64_t* pact, const int64_t* actions_hist, int B, int Tq, int na, int frame_base,
                      int hist_stride, int sig_val, int ctx_sig, hipStream_t s, float* pcont = nullptr, const float* cont_hist = nullptr, int nc = 0);
 int fill_sig(int32_t* sig, int n, int value, hipStream_t s);

@@ -56,6 +56,44 @@ def via_dispatcher():
     return os.environ.get('D4_TRUNK_DISPATCHER', '0') == '1'
 
 
+ARITHS = ('fp32', 'bf16')
+
+
+def arith_id(arith):
+    """'fp32' -> 0, 'bf16' -> 1 (the `arith` argument of d4_train_arith_set); anything else is a ValueError."""
+    if arith not in ARITHS:
+        raise ValueError(f"training arithmetic must be one of {ARITHS}, got {arith!r}")
+    return ARITHS.index(arith)
+
+
+class _arith_mode:
+    """The block arithmetic of libd4hip is process-wide: every forward / backward call of a block sets its own immediately before the C call
+    (autograd runs the backward on another thread, and a saved workspace must meet the arithmetic it was written in) and puts the previous
+    one back.  In bf16 mode the call also gets a scratch for its bf16 operand images (`scratch_bytes`), bound to this thread for the call and
+    released with it: nothing of it is kept between the forward and the backward."""
+    def __init__(self, lib, a, scratch_bytes=0, device=None):
+        self.lib, self.a = lib, a
+        self.scratch = _workspace(scratch_bytes, device) if a else None
+
+    def __enter__(self):
+        self.prev = self.lib.d4_train_arith_set(self.a)
+        if self.scratch is not None:
+            self.lib.d4_train_scratch_bind(self.scratch[1], self.scratch[0].numel() - 256)
+
+    def __exit__(self, *exc):
+        if self.scratch is not None:
+            self.lib.d4_train_scratch_bind(None, 0)
+        self.lib.d4_train_arith_set(self.prev)
+        return False
+
+
+def _no_dispatcher(arith):
+    if arith != 'fp32':
+        arith_id(arith)
+        raise NotImplementedError(f"D4_TRUNK_DISPATCHER=1 does not carry arith={arith!r}: the torch.ops.d4hip block registrations are fp32 only "
+                                  "(run the bf16 training arithmetic on the default autograd.Function route)")
+
+
 def _workspace(nbytes, device):
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
     base = ws.data_ptr()
@@ -64,7 +102,7 @@ def _workspace(nbytes, device):
 
 class _FeedForward(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, norm_w, w_in, b_in, w_out, b_out):
+    def forward(ctx, x, norm_w, w_in, b_in, w_out, b_out, arith=0):
         x, norm_w, w_in, b_in, w_out, b_out = _prep(x, norm_w, w_in, b_in, w_out, b_out)
         D, inner = x.shape[-1], w_out.shape[1]
         assert w_in.shape == (2 * inner, D) and w_out.shape == (D, inner) and b_in.shape == (2 * inner,) and b_out.shape == (D,)
@@ -73,9 +111,11 @@ class _FeedForward(torch.autograd.Function):
         nbytes = lib.d4_ff_workspace_bytes(rows, D, inner)
         ws, wp = _workspace(nbytes, x.device)
         y = torch.empty_like(x)
-        _lib.check(lib.d4_ff_forward(_lib.ptr(x), _lib.ptr(norm_w), _lib.ptr(w_in), _lib.ptr(b_in), _lib.ptr(w_out), _lib.ptr(b_out),
-                                     rows, D, inner, _lib.ptr(y), wp, nbytes, _stream(x)))
+        with _arith_mode(lib, arith, lib.d4_ff_bf16_scratch_bytes(rows, D, inner) if arith else 0, x.device):
+            _lib.check(lib.d4_ff_forward(_lib.ptr(x), _lib.ptr(norm_w), _lib.ptr(w_in), _lib.ptr(b_in), _lib.ptr(w_out), _lib.ptr(b_out),
+                                         rows, D, inner, _lib.ptr(y), wp, nbytes, _stream(x)))
         ctx.save_for_backward(x, norm_w, w_in, b_in, w_out)
+        ctx.arith = arith
         ctx.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx.needs_input_grad) else None
         return y
 
@@ -93,14 +133,15 @@ class _FeedForward(torch.autograd.Function):
             (ws, wp), fn = _workspace(nbytes, x.device), lib.d4_ff_backward
         dx, dn, dwi, dbi, dwo = torch.empty_like(x), torch.empty_like(norm_w), torch.empty_like(w_in), torch.empty_like(b_in), torch.empty_like(w_out)
         dbo = torch.empty(D, device=x.device)
-        _lib.check(fn(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(w_in), _lib.ptr(b_in), _lib.ptr(w_out), rows, D, inner,
-                                      _lib.ptr(dx), _lib.ptr(dn), _lib.ptr(dwi), _lib.ptr(dbi), _lib.ptr(dwo), _lib.ptr(dbo), wp, nbytes, _stream(x)))
-        return dx, dn, dwi, dbi, dwo, dbo
+        with _arith_mode(lib, ctx.arith, lib.d4_ff_bf16_scratch_bytes(rows, D, inner) if ctx.arith else 0, x.device):
+            _lib.check(fn(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(w_in), _lib.ptr(b_in), _lib.ptr(w_out), rows, D, inner,
+                          _lib.ptr(dx), _lib.ptr(dn), _lib.ptr(dwi), _lib.ptr(dbi), _lib.ptr(dwo), _lib.ptr(dbo), wp, nbytes, _stream(x)))
+        return dx, dn, dwi, dbi, dwo, dbo, None
 
 
 class _SpaceAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, softclamp, num_special, belief):
+    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, softclamp, num_special, belief, arith=0):
         x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma = _prep(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma)
         assert x.ndim == 3, 'x must be (frames, tokens, dim)'
         F_, S, D = x.shape
@@ -111,9 +152,11 @@ class _SpaceAttention(torch.autograd.Function):
         nbytes = lib.d4_attn_workspace_bytes(F_, S, D, heads, dh)
         ws, wp = _workspace(nbytes, x.device)
         y = torch.empty_like(x)
-        _lib.check(lib.d4_space_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
-                                             _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh,
-                                             float(softclamp or 0.), int(num_special), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
+        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if arith else 0, x.device):
+            _lib.check(lib.d4_space_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
+                                                 _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh,
+                                                 float(softclamp or 0.), int(num_special), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
+        ctx.arith = arith
         ctx.save_for_backward(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma)
         ctx.cfg = (float(softclamp or 0.), int(num_special), int(bool(belief)))
         ctx.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx.needs_input_grad) else None
@@ -134,17 +177,18 @@ class _SpaceAttention(torch.autograd.Function):
         e = torch.empty_like
         dx, dn, dq, dk, dv, do, dg, dgam = e(x), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         drv, dwm, dbm = (e(rv), e(wm), e(bm)) if rv is not None else (None, None, None)
-        _lib.check(fn(
-            _lib.ptr(x), _lib.ptr(rv), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg),
-            _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh, *ctx.cfg,
-            _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
-            _lib.ptr(dgam), wp, nbytes, _stream(x)))
-        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None
+        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if ctx.arith else 0, x.device):
+            _lib.check(fn(
+                _lib.ptr(x), _lib.ptr(rv), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg),
+                _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh, *ctx.cfg,
+                _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
+                _lib.ptr(dgam), wp, nbytes, _stream(x)))
+        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None
 
 
 class _TimeAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq, softclamp, belief):
+    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq, softclamp, belief, arith=0):
         x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq = _prep(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq)
         assert x.ndim == 4, 'x must be (batch, frames, tokens, dim)'
         B, T, S, D = x.shape
@@ -155,9 +199,11 @@ class _TimeAttention(torch.autograd.Function):
         nbytes = lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
         ws, wp = _workspace(nbytes, x.device)
         y = torch.empty_like(x)
-        _lib.check(lib.d4_time_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
-                                            _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), _lib.ptr(inv_freq), B, T, S, D, heads, dh,
-                                            float(softclamp or 0.), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
+        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(B * T * S, D, heads, dh) if arith else 0, x.device):
+            _lib.check(lib.d4_time_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
+                                                _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), _lib.ptr(inv_freq), B, T, S, D, heads, dh,
+                                                float(softclamp or 0.), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
+        ctx.arith = arith
         ctx.save_for_backward(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq)
         ctx.cfg = (float(softclamp or 0.), int(bool(belief)))
         ctx.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx.needs_input_grad) else None
@@ -178,17 +224,18 @@ class _TimeAttention(torch.autograd.Function):
         e = torch.empty_like
         dx, dn, dq, dk, dv, do, dg, dgam = e(x), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         drv, dwm, dbm = (e(rv), e(wm), e(bm)) if rv is not None else (None, None, None)
-        _lib.check(fn(
-            _lib.ptr(x), _lib.ptr(rv), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg),
-            _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), _lib.ptr(inv_freq), B, T, S, D, heads, dh, *ctx.cfg,
-            _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
-            _lib.ptr(dgam), wp, nbytes, _stream(x)))
-        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None
+        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(B * T * S, D, heads, dh) if ctx.arith else 0, x.device):
+            _lib.check(fn(
+                _lib.ptr(x), _lib.ptr(rv), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg),
+                _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), _lib.ptr(inv_freq), B, T, S, D, heads, dh, *ctx.cfg,
+                _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
+                _lib.ptr(dgam), wp, nbytes, _stream(x)))
+        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None
 
 
 class _CrossAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx_, q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma, item_major, softclamp):
+    def forward(ctx_, q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma, item_major, softclamp, arith=0):
         q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma = _prep(q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma)
         assert q_tokens.ndim == 3 and context.ndim == 3
         G, nq, D = q_tokens.shape
@@ -200,9 +247,11 @@ class _CrossAttention(torch.autograd.Function):
         nbytes = lib.d4_cross_attn_workspace_bytes(G, nq, nk, D, Dc, heads, dh)
         ws, wp = _workspace(nbytes, q_tokens.device)
         y = torch.empty_like(q_tokens)
-        _lib.check(lib.d4_cross_attn_forward(_lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk),
-                                             _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, int(bool(item_major)), D, Dc, heads, dh,
-                                             float(softclamp or 0.), _lib.ptr(y), wp, nbytes, _stream(q_tokens)))
+        with _arith_mode(lib, arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if arith else 0, q_tokens.device):
+            _lib.check(lib.d4_cross_attn_forward(_lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk),
+                                                 _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, int(bool(item_major)), D, Dc, heads, dh,
+                                                 float(softclamp or 0.), _lib.ptr(y), wp, nbytes, _stream(q_tokens)))
+        ctx_.arith = arith
         ctx_.save_for_backward(q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma)
         ctx_.cfg = (G, nq, nk, int(bool(item_major)), D, Dc, heads, dh, float(softclamp or 0.))
         ctx_.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx_.needs_input_grad) else None
@@ -222,12 +271,13 @@ class _CrossAttention(torch.autograd.Function):
         e = torch.empty_like
         dq_t, dc, dn, dq, dk, dv, do, dg, dgam = e(q_tokens), e(context), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         dnc = e(norm_ctx_w) if norm_ctx_w is not None else None
-        _lib.check(fn(
-            _lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv),
-            _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, item_major, D, Dc, heads, dh, softclamp,
-            _lib.ptr(dq_t), _lib.ptr(dc), _lib.ptr(dn), _lib.ptr(dnc), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dgam),
-            wp, nbytes, _stream(q_tokens)))
-        return dq_t, dc, dn, dnc, dq, dk, dv, do, dg, dgam, None, None
+        with _arith_mode(lib, ctx_.arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if ctx_.arith else 0, q_tokens.device):
+            _lib.check(fn(
+                _lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv),
+                _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, item_major, D, Dc, heads, dh, softclamp,
+                _lib.ptr(dq_t), _lib.ptr(dc), _lib.ptr(dn), _lib.ptr(dnc), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dgam),
+                wp, nbytes, _stream(q_tokens)))
+        return dq_t, dc, dn, dnc, dq, dk, dv, do, dg, dgam, None, None, None
 
 
 def _dev(*ts):
@@ -236,17 +286,18 @@ def _dev(*ts):
             raise _lib.D4Error('trunk_ops run only on an MI355X (HIP) device: there is no CPU fallback')
 
 
-def feedforward(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, proj_out_bias):
+def feedforward(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, proj_out_bias, *, arith='fp32'):
     """FeedForward.forward (dreamer4.py:2105-2116): proj_out(a * silu(g)), [a | g] = proj_in(RMSNorm(x)).  x (..., dim).
     With D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.swiglu_ff (dreamer4_amd/ops.py: dispatcher-visible, autograd registered); default: the autograd.Function above."""
     _dev(x)
     if not via_dispatcher():
-        return _FeedForward.apply(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, proj_out_bias)
+        return _FeedForward.apply(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, proj_out_bias, arith_id(arith))
+    _no_dispatcher(arith)
     return torch.ops.d4hip.swiglu_ff(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, proj_out_bias)[0]
 
 
 def space_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, *, residual_values=None, mix_weight=None, mix_bias=None,
-                    softclamp_value=50., num_special=1, belief=True):
+                    softclamp_value=50., num_special=1, belief=True, arith='fp32'):
     """Attention.forward (dreamer4.py:1968-2075), self attention within each frame: x (frames, tokens, dim) -> (frames, tokens, dim).
     `residual_values` (frames, tokens, heads, dim_head) with `mix_weight` / `mix_bias` = to_learned_value_residual_mix.0 (every layer
     but the first); `num_special` trailing tokens are hidden from ordinary queries (dreamer4.py:1769-1783).  (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_space.)"""
@@ -254,13 +305,14 @@ def space_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
     assert x.ndim == 3, 'x must be (frames, tokens, dim)'
     if not via_dispatcher():
         return _SpaceAttention.apply(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma,
-                                     softclamp_value, num_special, belief)
+                                     softclamp_value, num_special, belief, arith_id(arith))
+    _no_dispatcher(arith)
     return torch.ops.d4hip.attn_block_space(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma,
                                             float(softclamp_value or 0.), int(num_special), bool(belief))[0]
 
 
 def time_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, inv_freq, *, residual_values=None, mix_weight=None,
-                   mix_bias=None, softclamp_value=50., belief=True):
+                   mix_bias=None, softclamp_value=50., belief=True, arith='fp32'):
     """The trunk's time layers (dreamer4.py:3176-3215): causal attention along time for every token column, rotary positions
     (`inv_freq` = time_rotary.inv_freq), no KV cache (the training form).  x (batch, frames, tokens, dim), frames <= 64;
     `residual_values` (batch, frames, tokens, heads, dim_head).  (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_time.)"""
@@ -268,13 +320,14 @@ def time_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, 
     assert x.ndim == 4, 'x must be (batch, frames, tokens, dim)'
     if not via_dispatcher():
         return _TimeAttention.apply(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma, inv_freq,
-                                    softclamp_value, belief)
+                                    softclamp_value, belief, arith_id(arith))
+    _no_dispatcher(arith)
     return torch.ops.d4hip.attn_block_time(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma, inv_freq,
                                            float(softclamp_value or 0.), bool(belief))[0]
 
 
 def cross_attention(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, *,
-                    context_item_major=False, softclamp_value=None):
+                    context_item_major=False, softclamp_value=None, arith='fp32'):
     """Attention.forward with a context (dreamer4.py:1968-2075): q_tokens (groups, nq, dim); context (groups, nk, dim_ctx), or
     (nk, groups, dim_ctx) with `context_item_major` (the stack of layer hiddens of the AttentionPool).  nq, nk <= 64.
     (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_cross.)"""
@@ -282,7 +335,8 @@ def cross_attention(q_tokens, context, norm_weight, norm_context_weight, to_q, t
     assert q_tokens.ndim == 3 and context.ndim == 3
     if not via_dispatcher():
         return _CrossAttention.apply(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
-                                     context_item_major, softclamp_value)
+                                     context_item_major, softclamp_value, arith_id(arith))
+    _no_dispatcher(arith)
     return torch.ops.d4hip.attn_block_cross(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
                                             bool(context_item_major), float(softclamp_value or 0.))[0]
 
@@ -299,11 +353,12 @@ def _attn_w(W, pre):
             W[pre + 'to_gates.0.weight'], W[pre + 'k_heads_rmsnorm.gamma'])
 
 
-def _ff(W, pre, x):
-    return feedforward(x, W[pre + 'norm.weight'], W[pre + 'proj_in.weight'], W[pre + 'proj_in.bias'], W[pre + 'proj_out.weight'], W[pre + 'proj_out.bias'])
+def _ff(W, pre, x, arith='fp32'):
+    return feedforward(x, W[pre + 'norm.weight'], W[pre + 'proj_in.weight'], W[pre + 'proj_in.bias'], W[pre + 'proj_out.weight'], W[pre + 'proj_out.bias'],
+                       arith=arith)
 
 
-def _pool(W, pre, x, hiddens):
+def _pool(W, pre, x, hiddens, arith='fp32'):
     """Residual(AttentionPool) (dreamer4.py:2143-2177 + 1869): one query per token over the stack of layer hiddens.
     hiddens: a list of layer hiddens, or the stack itself (L, rows, D) — `transformer` grows ONE stack by concatenation, so that in the
     backward every pool's context gradient meets the previous pools' as one (L, rows, D) sum instead of L per-hidden sums per pool."""
@@ -311,11 +366,11 @@ def _pool(W, pre, x, hiddens):
     ctx = hiddens if torch.is_tensor(hiddens) else torch.stack([h.reshape(-1, shape[-1]) for h in hiddens], dim=0)     # (L, rows, D): item major
     p = pre + 'fn.attn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, p)
-    out = cross_attention(x.reshape(-1, 1, shape[-1]), ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, context_item_major=True)
+    out = cross_attention(x.reshape(-1, 1, shape[-1]), ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, context_item_major=True, arith=arith)
     return x + out.reshape(shape)
 
 
-def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='transformer.'):
+def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='transformer.', arith='fp32'):
     """AxialSpaceTimeTransformer.forward (dreamer4.py:2927-3267, defaults: value residual, attention pools, final special cross
     attention; final RMSNorm when the weights hold one) for training: no KV cache, every block a HIP forward + backward operator;
     only the residual adds, reshapes and the two bare RMSNorm + Linear pieces (value residual projection, final norm) are torch ops.
@@ -336,33 +391,33 @@ def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='
         mw, mb = W[ap + 'to_learned_value_residual_mix.0.weight'], W[ap + 'to_learned_value_residual_mix.0.bias']
         if tl:
             out = time_attention(tokens, nw, wq, wk, wv, wo, wg, gam, W[pre + 'time_rotary.inv_freq'], residual_values=vres, mix_weight=mw,
-                                 mix_bias=mb, softclamp_value=softclamp_value)
+                                 mix_bias=mb, softclamp_value=softclamp_value, arith=arith)
         else:
             out = space_attention(tokens.reshape(b * t, s, d), nw, wq, wk, wv, wo, wg, gam, residual_values=vres.reshape(b * t, s, h, dh),
-                                  mix_weight=mw, mix_bias=mb, softclamp_value=softclamp_value, num_special=num_special).reshape(b, t, s, d)
+                                  mix_weight=mw, mix_bias=mb, softclamp_value=softclamp_value, num_special=num_special, arith=arith).reshape(b, t, s, d)
         tokens = tokens + out
         after_attn = tokens
-        tokens = tokens + _ff(W, f'{pre}layers.{i}.3.fn.', tokens)
+        tokens = tokens + _ff(W, f'{pre}layers.{i}.3.fn.', tokens, arith)
         hiddens = torch.cat((hiddens, after_attn.reshape(1, -1, d), tokens.reshape(1, -1, d)), dim=0)
         if i != depth - 1:
-            tokens = _pool(W, f'{pre}attn_pools.{i}.', tokens, hiddens)
+            tokens = _pool(W, f'{pre}attn_pools.{i}.', tokens, hiddens, arith)
     # the special tokens cross-attend the ordinary tokens of their frame, then their own feedforward   dreamer4.py:3227-3238
     non_special, special = tokens[:, :, :-num_special], tokens[:, :, -num_special:]
     cp = pre + 'final_special_cross_attn.fn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, cp)
     out = cross_attention(special.reshape(b * t, num_special, d), non_special.reshape(b * t, s - num_special, d), nw, W[cp + 'norm_context.weight'],
-                          wq, wk, wv, wo, wg, gam)
+                          wq, wk, wv, wo, wg, gam, arith=arith)
     special = special + out.reshape(b, t, num_special, d)
-    special = special + _ff(W, pre + 'final_special_ff.fn.', special)
+    special = special + _ff(W, pre + 'final_special_ff.fn.', special, arith)
     tokens = torch.cat((non_special, special), dim=2)
-    tokens = _pool(W, pre + 'final_attn_pool.', tokens, hiddens)
+    tokens = _pool(W, pre + 'final_attn_pool.', tokens, hiddens, arith)
     if pre + 'final_norm.weight' in W:
         tokens = torch.ops.d4hip.rmsnorm(tokens, W[pre + 'final_norm.weight'], eps)
     return tokens
 
 
 # ------------------------------------------------------------------------------------------------ the dynamics model, training form
-def _lq_pool(W, pre, x):
+def _lq_pool(W, pre, x, arith='fp32'):
     """LearnedQueriesAttentionPool (dreamer4.py:2179-2210): x (..., n, d_ctx) -> (..., num_queries, dim)."""
     lead = x.shape[:-2]
     ctx = x.reshape(-1, *x.shape[-2:])
@@ -370,12 +425,12 @@ def _lq_pool(W, pre, x):
     q = queries[None].expand(ctx.shape[0], -1, -1)
     p = pre + 'attn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, p)
-    out = cross_attention(q, ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam)
+    out = cross_attention(q, ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, arith=arith)
     return out.reshape(*lead, *out.shape[-2:])
 
 
 def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *, is_time, num_spatial_tokens, num_register_tokens,
-                           num_discrete_actions=(), discrete_actions=None, continuous_actions=None, tasks=None, softclamp_value=50.):
+                           num_discrete_actions=(), discrete_actions=None, continuous_actions=None, tasks=None, softclamp_value=50., arith='fp32'):
     """DynamicsWorldModel's `get_prediction` (dreamer4.py:7156-7287) for training: noised latents (b, t, n, dl), signal_levels (b, t),
     step_sizes_log2 (b,) -> (latent prediction (b, t, n, dl), agent embedding (b, t, dim)).  Token packing, embeddings and the bare
     RMSNorm + Linear of the latent head are torch ops; the trunk and the learned-query pools are the HIP forward + backward blocks.
@@ -390,7 +445,7 @@ def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *,
     if num_spatial_tokens == n:
         space = torch.ops.d4hip.linear(noised_latents, W['latents_to_spatial_tokens.weight'], W['latents_to_spatial_tokens.bias'], None, 0, 0.)
     else:
-        space = _lq_pool(W, 'latents_to_spatial_tokens.', noised_latents)
+        space = _lq_pool(W, 'latents_to_spatial_tokens.', noised_latents, arith)
     sig = W['signal_levels_embed.weight'][signal_levels]
     stp = W['step_size_embed.weight'][step_sizes_log2][:, None].expand(b, t, -1)
     flow_tok = torch.cat((sig, stp), dim=-1)[:, :, None]
@@ -417,11 +472,11 @@ def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *,
             act = F.pad(emb, (0, 0, 1, 0), value=0.)
         parts.append(act[:, :, None])
     parts.append(agent)
-    tokens = transformer(W, torch.cat(parts, dim=2), is_time=is_time, softclamp_value=softclamp_value)
+    tokens = transformer(W, torch.cat(parts, dim=2), is_time=is_time, softclamp_value=softclamp_value, arith=arith)
     space_out, agent_embed = tokens[:, :, 1:1 + num_spatial_tokens], tokens[:, :, -1]
     x = torch.ops.d4hip.rmsnorm(space_out, W['to_latent_pred.0.weight'], eps)
     if num_spatial_tokens != n:
-        x = _lq_pool(W, 'to_latent_pred.1.', x)
+        x = _lq_pool(W, 'to_latent_pred.1.', x, arith)
     return torch.ops.d4hip.linear(x, W['to_latent_pred.2.weight'], None, None, 0, 0.), agent_embed
 
 
@@ -442,7 +497,7 @@ def _action_offsets(sizes, dev):
 def dynamics_flow_losses(W, latents, noise, signal_levels, step_sizes_log2, shortcut_train, *, max_steps, return_agent_embed=False, lens=None, **model):
     """The flow and shortcut-consistency losses of the dynamics training forward (dreamer4.py:6990-7003, 7335-7431; x-space prediction,
     ramp loss weight, no proprio / variable lengths / loss normalisers: the reference defaults).  `model`: the keyword arguments of
-    `world_model_prediction`.  Returns (flow_loss, shortcut_loss[, agent_embed of the main prediction]); backward runs through the HIP blocks."""
+    `world_model_prediction` (among them `arith='fp32' | 'bf16'`, the arithmetic of the blocks' Linears in all three predictions).  Returns (flow_loss, shortcut_loss[, agent_embed of the main prediction]); backward runs through the HIP blocks."""
     from torch.nn import functional as F
     times = signal_levels.float() / max_steps
     tt = times[:, :, None, None]

@@ -173,6 +173,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         head_mlp_recipe='pre_rms',
         continuous_beta_param='softplus_p1',
         matmul_dtype='fp32',
+        train_matmul_dtype='fp32',
         use_loss_normalization=False,
         latent_flow_loss_weight=1.,
         shortcut_loss_weight=1.,
@@ -209,6 +210,14 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         if matmul_dtype not in ('fp32', 'fp32_mfma', 'fp32_fp16x2', 'bf16'):
             raise ValueError("matmul_dtype must be 'fp32', 'fp32_mfma', 'fp32_fp16x2' or 'bf16'")
         self.matmul_dtype = matmul_dtype
+        # (not a reference argument) arithmetic of the TRAINING forward's trunk blocks, independent of `matmul_dtype` (the engine's, inference):
+        #   'fp32' (default)  every product in fp32
+        #   'bf16'            mixed precision: the forward, input-gradient and weight-gradient products of the blocks' Linears on bf16-rounded
+        #                     operands (bf16 MFMA, fp32 accumulate), everything else — norms, attention cores, losses, master weights and
+        #                     their .grad — in fp32
+        if train_matmul_dtype not in ('fp32', 'bf16'):
+            raise ValueError("train_matmul_dtype must be 'fp32' or 'bf16'")
+        self.train_matmul_dtype = train_matmul_dtype
         self.use_loss_normalization = bool(use_loss_normalization)
         # loss weights of the training forward's total (dreamer4.py:4719-4725, 5257-5267, 7708-7723): two plain floats and four persistent
         # buffers of 1 or multi_token_pred_len elements — a checkpoint's values are loaded and used
@@ -803,7 +812,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             num_register_tokens=self.num_register_tokens, num_discrete_actions=tuple(self.num_discrete_actions),
             discrete_actions=discrete_actions.to(dev).long() if discrete_actions is not None else None,
             continuous_actions=continuous_actions.to(dev).float() if continuous_actions is not None else None,
-            tasks=tasks.to(dev).long() if tasks is not None else None, softclamp_value=self.attn_softclamp_value)
+            tasks=tasks.to(dev).long() if tasks is not None else None, softclamp_value=self.attn_softclamp_value, arith=self.train_matmul_dtype)
         rew = rewards.to(dev).float() if rewards is not None else None
         if rew is not None and rew.shape[1] == T - 1:
             rew = torch.nn.functional.pad(rew, (1, 0), value=0.)                                           # dreamer4.py:6905-6907

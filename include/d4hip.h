@@ -293,6 +293,12 @@ int d4_gemm_pair(const float* A1, int lda1, const float* W1, float* C1, int ldc1
  * take the shape rule (csrc/gemm_tn.hip), other values force the 64 x (64 tile_n) tile and the slice count (benchmarks).  Deterministic. */
 int d4_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, int64_t part_floats,
                int tile_n, int slices, void* stream);
+/* The same product on the bf16 matrix pipe (the weight gradient of the bf16 training arithmetic, csrc/gemm_tn_bf16.hip): A [K][lda] and B [K][ldb]
+ * are bf16 images (round to nearest even) of the output gradient and the layer input, C [M][N] fp32 with fp32 accumulation.  lda, ldb multiples
+ * of 8 that cover M, N rounded up to 8; 16-byte aligned images; any M, N, K >= 1 (ragged edges are zero-padded inside the kernel, C outside
+ * M x N is not touched).  `part` as for d4_gemm_tn; slices = 0 takes the shape rule.  Deterministic. */
+int d4_gemm_tn_bf16(const uint16_t* A, int lda, const uint16_t* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, int64_t part_floats,
+                    int slices, void* stream);
 /* strided-batch form (the AttentionPool's per-head value projection, D4:2143-2177): problem b reads A + b*strideA,
  * W + b*strideW and writes C (and R) + b*strideC   (strides in elements). */
 int d4_gemm_batched(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
@@ -351,6 +357,29 @@ int d4_gemm_split2(const float* A, int lda, const uint16_t* W2, int64_t plane_st
  * `workspace` to be the very buffer the matching `*_forward` call ran in, untouched since: the forward intermediates it holds (normalised input,
  * concatenated weight images, projections) are used as they are and nothing is recomputed (one GEMM in four of a block's backward). */
 size_t d4_ff_workspace_bytes(int rows, int dim, int inner);
+/* Training arithmetic of the four blocks (FeedForward, space / time / cross attention): 0 = fp32 (default), 1 = bf16.
+ * bf16: the forward, input-gradient and weight-gradient products of every Linear with at least 16 input and 16 output features run on bf16
+ * images of their operands (fp32 accumulate, fp32 results); norms, attention cores, SiLU-GLU, the heads-wide gate / mix projections, biases
+ * and every gradient output stay fp32.
+ *
+ * d4_train_arith_set is process-wide and returns the previous value: a caller sets it immediately before EACH forward / backward call of a
+ * block (a `*_backward_saved` call must run in the arithmetic of its forward) and restores it after.
+ *
+ * Scratch: in bf16 mode a block call needs memory for the bf16 operand images.  d4_train_scratch_bind(scratch, bytes) binds 256-byte aligned
+ * device memory of at least the block's `*_bf16_scratch_bytes` to the CALLING thread (NULL unbinds).  Nothing in it outlives the call, so it
+ * can be freed (stream-ordered) right after.  d4_attn_bf16_scratch_bytes serves the space and the time block (rows = all token rows of the
+ * call).  The blocks' workspaces and their size queries are the same in both arithmetics.
+ *
+ * NOT thread-safe across concurrent training threads: two host threads that drive blocks in different arithmetics at the same time can see
+ * each other's setting.  Both mismatches are refused, neither computes silently in the wrong arithmetic: a call that finds the switch at bf16
+ * without a scratch bound on its thread fails, and so does a call that finds the switch at fp32 while its thread has a scratch bound.  One
+ * training loop per process, with autograd's single backward thread, is the supported use. */
+int d4_train_arith_set(int arith);
+int d4_train_arith_get(void);
+int d4_train_scratch_bind(void* scratch, size_t bytes);
+size_t d4_ff_bf16_scratch_bytes(int rows, int dim, int inner);
+size_t d4_attn_bf16_scratch_bytes(int rows, int dim, int heads, int dim_head);
+size_t d4_cross_attn_bf16_scratch_bytes(int groups, int nq, int nk, int dim, int dim_ctx, int heads, int dim_head);
 int d4_ff_forward(const float* x, const float* norm_w, const float* w_in, const float* b_in, const float* w_out, const float* b_out,
                   int rows, int dim, int inner, float* y, float* workspace, size_t workspace_bytes, void* stream);
 int d4_ff_backward(const float* x, const float* dy, const float* norm_w, const float* w_in, const float* b_in, const float* w_out,
