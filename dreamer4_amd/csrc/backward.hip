@@ -12,6 +12,7 @@
 // by the imagination path.
 #include "common.h"
 #include "kernels.h"
+#include "attn_tiled.h"
 #include "../../include/d4hip.h"
 #include <atomic>
 #include <float.h>
@@ -242,25 +243,7 @@ static int ff_recompute(const FfWs& w, const float* x, const float* norm_w, cons
 }
 
 // ------------------------------------------------------------------------------------------------ attention core backward
-// One block (4 waves) per (frame, head); S <= 32 tokens, head dim DH <= 64 (lanes >= DH idle).  Rows of proj: q @ 0, k @ hd, v @ 2hd,
-// gate logit @ 3hd + head, mix logit @ 3hd + hp4 + head  (hd = heads * DH, hp4 = heads rounded up to 4).
-struct AttnBwdArgs {
-    const float* proj; int ldp;        // [F*S][ldp] forward projections (mix logits include their bias)
-    const float* rv;                   // [F*S][hd] value residual or null
-    const float* gamma;                // [heads][DH]
-    const float* d_o3;                 // [F*S][hd] gradient of the gated attention output (before to_out); null: forward only
-    float* o3;                         // [F*S][hd] out: gated attention output (recomputed forward)
-    float* dproj;                      // [F*S][ldp] out: gradients of the projections (same columns)
-    float* d_rv;                       // [F*S][hd] out (when rv)
-    float* dgamma_part;                // [F][hd] out: per-frame partial of d gamma
-    int F, S, heads, hp4;              // F groups of S items
-    float softclamp; int num_special, belief;
-    // row of item j of group g = (g / g_inner) * g_outer_stride + (g % g_inner) + j * item_stride:
-    //   within-frame attention: g_inner 1, g_outer_stride S, item_stride 1;  time attention over [B][T][S] rows: g_inner S, g_outer_stride T * S, item_stride S
-    int g_inner = 1; int64_t g_outer_stride = 0, item_stride = 1;
-    int causal = 0;                    // item i sees items j <= i
-    const float* inv_freq = nullptr;   // [DH / 2] rotary frequencies applied to q and k at position j (time attention), or null
-};
+// (AttnBwdArgs, the argument block of the core: attn_tiled.h)
 
 constexpr int AB_S = 64, AB_LD = 65;           // items (tokens of a frame / frames of a trajectory) per group: <= 64 (a score row = one wavefront)
 // CAP: token capacity of the LDS arrays (16 or 32): at <= 16 tokens per group the block needs 27 KB instead of 60 KB of LDS, so five blocks
@@ -414,8 +397,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnBwdArgs p) {
     if (w == 0 && on) p.dgamma_part[(int64_t)f * hd + h * DH + lane] = (((gpart[0][lane] + gpart[1][lane]) + gpart[2][lane]) + gpart[3][lane]) * sqrtf((float)DH);
 }
 
-static int attn_core(const AttnBwdArgs& a, int dh, hipStream_t s) {
+// `tiled`: the per-row planes of the tiled core (attn_tiled.hip), given when the time geometry runs more than AB_S frames (or the test hook asks)
+static int attn_core(const AttnBwdArgs& a, int dh, hipStream_t s, float* tiled = nullptr) {
     if (a.F * a.heads == 0) return 0;
+    if (tiled) return attn_tiled_core(a, dh, tiled, s);
     auto lds_of = [](int cap) { return (size_t)(6 * cap * AB_LD + 2 * cap * (cap + 1) + 4 * cap) * sizeof(float); };
     static bool attr = false;
     if (!attr) {
@@ -577,10 +562,11 @@ __global__ void zero_pad_cols_kernel(float* x, int rows, int ld, int c0, int c1)
 
 struct AttnWs {
     float *xn, *wcat, *bcat, *proj, *dproj, *d_o3, *o3, *dwcat, *tg, *dxn, *gpart, *part, *wt;
+    float* tiled;                    // per-row planes of the tiled time core, last, so that every other offset is the same with and without them
     size_t total;
     int P, hp4;
 };
-static AttnWs attn_ws(float* base, int R, int F, int D, int heads, int dh) {
+static AttnWs attn_ws(float* base, int R, int F, int D, int heads, int dh, bool tiled = false) {
     AttnWs w{};
     const int hd = heads * dh;
     w.hp4 = (heads + 3) / 4 * 4;
@@ -592,6 +578,7 @@ static AttnWs attn_ws(float* base, int R, int F, int D, int heads, int dh) {
     w.gpart = take((size_t)F * hd);
     w.part = take(DW_PART_FLOATS);
     w.wt = take((size_t)w.P * D);
+    if (tiled) w.tiled = take(attn_tiled_floats(R, heads, dh));
     w.total = off;
     return w;
 }
@@ -716,11 +703,15 @@ struct AttnGeom {                  // how the rows of x group into attention pro
     int causal, num_special; const float* inv_freq;
 };
 
+// the time geometry (causal, rotary) takes the tiled core above AB_S frames, and at any length under the test hook
+bool attn_tiled(const AttnGeom& g) { return g.causal && g.inv_freq && (g.items > AB_S || g_time_attn_tiled != 0); }
+
 int attn_check(int rows, const AttnGeom& g, int dim, int heads, int dim_head, const float* workspace, size_t workspace_bytes) {
-    D4_REQUIRE(g.items >= 1 && g.items <= AB_S, "attention block: %d items per group (max %d)", g.items, AB_S);
+    if (g.causal && g.inv_freq) D4_REQUIRE(g.items >= 1 && g.items <= ATT_MAX_FRAMES, "time attention block: %d frames per trajectory (max %d)", g.items, ATT_MAX_FRAMES);
+    else D4_REQUIRE(g.items >= 1 && g.items <= AB_S, "attention block: %d items per group (max %d)", g.items, AB_S);
     D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "attention block: head dim %d (16, 32 or 64)", dim_head);
     D4_REQUIRE(dim % 4 == 0 && ((uintptr_t)workspace % 256) == 0, "attention block: dim must be a multiple of 4 and the workspace 256-byte aligned");
-    D4_REQUIRE(workspace_bytes >= attn_ws(nullptr, rows, g.groups, dim, heads, dim_head).total * sizeof(float), "attention block: workspace too small");
+    D4_REQUIRE(workspace_bytes >= attn_ws(nullptr, rows, g.groups, dim, heads, dim_head, attn_tiled(g)).total * sizeof(float), "attention block: workspace too small");
     return 0;
 }
 
@@ -736,13 +727,13 @@ int attn_block_forward(const float* x, const float* residual_values, const AttnP
     if ((rc = attn_check(rows, g, dim, heads, dim_head, workspace, workspace_bytes))) return rc;
     const int R = rows, hd = heads * dim_head;
     if (R == 0) return 0;
-    const AttnWs w = attn_ws(workspace, R, g.groups, dim, heads, dim_head);
+    const AttnWs w = attn_ws(workspace, R, g.groups, dim, heads, dim_head, attn_tiled(g));
     Bf16Scope bf;
     if ((rc = bf.enter("attention forward", R, 3 * hd > dim ? 3 * hd : dim, 3 * hd, dim))) return rc;
     if ((rc = attn_project(w, x, prm, R, dim, heads, dim_head, residual_values != nullptr, s))) return rc;
     AttnBwdArgs a{w.proj, w.P, residual_values, prm.gamma, nullptr, w.o3, nullptr, nullptr, nullptr, g.groups, g.items, heads, w.hp4, softclamp, g.num_special, belief};
     set_geom(a, g);
-    if ((rc = attn_core(a, dim_head, s))) return rc;
+    if ((rc = attn_core(a, dim_head, s, w.tiled))) return rc;
     return gemm_b(w.o3, hd, prm.wo, hd, y, dim, nullptr, R, dim, hd, 0, s);
 }
 
@@ -759,7 +750,7 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
     D4_REQUIRE(rows >= 1, "attention backward: no rows");
     const int R = rows, D = dim, hd = heads * dim_head;
     const bool has_rv = residual_values != nullptr;
-    const AttnWs w = attn_ws(workspace, R, g.groups, D, heads, dim_head);
+    const AttnWs w = attn_ws(workspace, R, g.groups, D, heads, dim_head, attn_tiled(g));
     Bf16Scope bf;
     if ((rc = bf.enter("attention backward", R, 3 * hd > D ? 3 * hd : D, 3 * hd, D))) return rc;
     if (!reuse && (rc = attn_project(w, x, prm, R, D, heads, dim_head, has_rv, s))) return rc;     // reuse: the forward's xn / wcat / proj are still there
@@ -767,7 +758,7 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
     if ((rc = lin_dx(dy, D, prm.wo, hd, w.d_o3, hd, R, hd, D, w.wt, s))) return rc;                                     // d_o3 = dy Wo
     AttnBwdArgs a{w.proj, w.P, residual_values, prm.gamma, w.d_o3, w.o3, w.dproj, o.d_rv, w.gpart, g.groups, g.items, heads, w.hp4, softclamp, g.num_special, belief};
     set_geom(a, g);
-    if ((rc = attn_core(a, dim_head, s))) return rc;
+    if ((rc = attn_core(a, dim_head, s, w.tiled))) return rc;
     image_a_written(w.dproj);
     // the pad columns of the gate / mix logits and of the row carry no gradient
     if (w.hp4 > heads) hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)R * (w.hp4 - heads)), dim3(256), 0, s, w.dproj, R, w.P, 3 * hd + heads, 3 * hd + w.hp4);
@@ -964,7 +955,8 @@ int d4_cross_attn_backward(D4_XBWD_PARAMS) { return cross_attn_backward_impl(D4_
 int d4_cross_attn_backward_saved(D4_XBWD_PARAMS) { return cross_attn_backward_impl(D4_XBWD_ARGS, true); }
 
 size_t d4_time_attn_workspace_bytes(int batch, int frames, int tokens, int dim, int heads, int dim_head) {
-    return attn_ws(nullptr, batch * frames * tokens, batch * tokens, dim, heads, dim_head).total * sizeof(float);
+    const bool tiled = frames > AB_S || g_time_attn_tiled != 0;       // the rule of attn_tiled(): at <= 64 frames the size is the LDS core's
+    return attn_ws(nullptr, batch * frames * tokens, batch * tokens, dim, heads, dim_head, tiled).total * sizeof(float);
 }
 
 int d4_space_attn_forward(const float* x, const float* residual_values, const float* norm_w, const float* wq, const float* wk, const float* wv,

@@ -1538,6 +1538,7 @@ int d4_debug_switch(const char* name, int value) {
     if (name && !strcmp(name, "time_attn_fused_append")) sw = &d4::g_time_attn_fused_append;
     else if (name && !strcmp(name, "attn_out_cols")) sw = &d4::g_attn_out_cols;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
+    else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
     if (!sw) return -1;
     const int old = *sw;
     *sw = value;

@@ -192,14 +192,17 @@ def _save_ws():
     return os.environ.get('D4_TRUNK_SAVE_FORWARD', '1') != '0'
 
 
+_WS_PAD = 256          # slack for aligning the workspace pointer (_ws_ptr)
+
+
 def _ws_new(nbytes, device):
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    ws = torch.empty(nbytes + _WS_PAD, dtype=torch.uint8, device=device)
     return ws
 
 
 def _ws_ptr(ws):
     base = ws.data_ptr()
-    return C.c_void_p(base + (-base) % 256)
+    return C.c_void_p(base + (-base) % _WS_PAD)
 
 
 def _f32c(*ts):
@@ -313,7 +316,8 @@ def _attn_self_backward(time_form, x, rv, dy, norm_w, wq, wk, wv, wo, wg, wm, bm
     saved = ws.numel() > 0
     if time_form:
         B, T, S, D = x.shape
-        nbytes = lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
+        # a saved workspace is claimed at the size it was allocated with (_ws_new), not at what the size rule says now
+        nbytes = ws.numel() - _WS_PAD if saved else lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
         if not saved:
             ws = _ws_new(nbytes, x.device)
         fn = lib.d4_time_attn_backward_saved if saved else lib.d4_time_attn_backward

@@ -272,7 +272,10 @@ int d4_frame_fused_set(int mode);
  * projection at <= 4 frames, csrc/frame_fused.hip); value 1 (default) fused, 0 two launches.  Returns the previous value, -1 for an unknown name.
  * "pool_wide_keys" (bf16 engine only; NOT bit-identical: the queries become bf16): 1 (default) a hidden is projected once, when produced, onto the key
  * weights of every later attention pool and the query weights of the pool it feeds; 0 a query launch + a key launch over the whole stack per pool.
- * Read when a frame is ENQUEUED: a captured hipGraph keeps the form it was captured with. */
+ * Read when a frame is ENQUEUED: a captured hipGraph keeps the form it was captured with.
+ * "time_attn_tiled" (training time attention, csrc/attn_tiled.hip; NOT bit-identical: another summation order): 0 (default) the tiled core
+ * runs above 64 frames only, 1 at any length, so that it can be checked at shapes the LDS core also handles.  Read by
+ * d4_time_attn_workspace_bytes too: size the workspace with the value the calls will run under. */
 int d4_debug_switch(const char* name, int value);
 int d4_gemm_force_config(int id);
 
@@ -410,8 +413,11 @@ int d4_space_attn_backward_saved(const float* x, const float* residual_values, c
                            float* d_w_gates, float* d_w_mix, float* d_b_mix, float* d_k_gamma,
                            float* workspace, size_t workspace_bytes, void* stream);
 /* Time attention block (the same Attention with rotary positions and a causal mask along time, one problem per token column,
- * dreamer4.py:3176-3215 / 1626-1659): x / y [batch][frames][tokens][dim] row-major, frames <= 64 (no KV cache: the training form);
- * inv_freq [dim_head / 2] = time_rotary.inv_freq. */
+ * dreamer4.py:3176-3215 / 1626-1659): x / y [batch][frames][tokens][dim] row-major, frames <= 1024 (no KV cache: the training form);
+ * inv_freq [dim_head / 2] = time_rotary.inv_freq.  Up to 64 frames the core keeps a whole (trajectory column, head) problem in LDS; above,
+ * a tiled core (csrc/attn_tiled.hip: online softmax forward, P recomputed from the saved log-sum-exp in the backward, all products on the
+ * f32-input MFMA) runs over per-row planes that d4_time_attn_workspace_bytes adds behind the block's workspace: memory linear in the
+ * frames, nothing of size frames x frames.  More than 1024 frames is an error. */
 size_t d4_time_attn_workspace_bytes(int batch, int frames, int tokens, int dim, int heads, int dim_head);
 int d4_time_attn_forward(const float* x, const float* residual_values, const float* norm_w, const float* wq, const float* wk, const float* wv,
                          const float* wo, const float* w_gates, const float* w_mix, const float* b_mix, const float* k_gamma, const float* inv_freq,
