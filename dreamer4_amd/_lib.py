@@ -150,6 +150,11 @@ SYMBOLS = {
     'd4_row_scale_exp': (_I, [_P, _L, _I, _I, _P, _P]),
     'd4_gemm_split2': (_I, [_P, _I, _P, _L, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
     'd4_rmsnorm': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P]),
+    'd4_small_attn': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
+    'd4_pool_mix': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    'd4_time_attn_decode': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P] + [_I] * 8 + [_P, _F, _I, _I, _P]),
+    'd4_debug_last_form': (C.c_char_p, [C.c_char_p]),
+    'd4_debug_forms': (_I, [C.c_char_p, _I, C.POINTER(C.c_char_p)]),
     'd4_rmsnorm_backward': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     'd4_hl_gauss_scalar': (_I, [_P, _I, _P, _P, _I, _I, _P]),
     'd4_ppo_policy_loss': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),

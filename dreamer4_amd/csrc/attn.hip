@@ -17,8 +17,49 @@
 #include "pool_mix_row.h"
 #include <float.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace d4 {
+
+// Which kernel form each launcher of this file picked last: a host-side record for the operator tests (d4_debug_last_form / d4_debug_forms in
+// engine.hip).  A plain store on the host; nothing on the device, no launch depends on it.
+enum { FAM_SMALL_ATTN, FAM_POOL_MIX, FAM_TIME_KV_APPEND, FAM_TIME_ATTN, FAM_N };
+static const char* const k_small_attn_forms[] = {
+    "attn_mfma_kernel<1,1>", "attn_mfma_kernel<1,2>", "attn_mfma_kernel<1,4,2>", "attn_mfma_kernel<2,1>", "attn_mfma_kernel<4,1>",
+    "space_attn_kernel<64>", "space_attn_kernel<32>", "space_attn_kernel<16>",
+    "small_attn_kernel<16,64>", "small_attn_kernel<16,32>", "small_attn_kernel<16,16>",
+    "small_attn_kernel<32,64>", "small_attn_kernel<32,32>", "small_attn_kernel<32,16>",
+    "small_attn_kernel<64,64>", "small_attn_kernel<64,32>", "small_attn_kernel<64,16>",
+    "attn_wide_kernel", nullptr};
+static const char* const k_pool_mix_forms[] = {
+    "pool_mix_rows_kernel<1>", "pool_mix_rows_kernel<1,bf16>", "pool_mix_rows_kernel<2>", "pool_mix_rows_kernel<2,bf16>",
+    "pool_mix_kernel<1>", "pool_mix_kernel<1,bf16>", "pool_mix_kernel<2>", "pool_mix_kernel<2,bf16>", "pool_mix_kernel<4>", "pool_mix_kernel<4,bf16>", nullptr};
+static const char* const k_time_kv_append_forms[] = {
+    "time_kv_append4_kernel", "time_kv_append_kernel<64>", "time_kv_append_kernel<32>", "time_kv_append_kernel<16>", nullptr};
+static const char* const k_time_attn_forms[] = {
+    "time_attn64_few_kernel<8>", "time_attn64_few_kernel<16>", "time_attn64_few_kernel<8,append>", "time_attn64_few_kernel<16,append>",
+    "time_attn64_kernel<false>", "time_attn64_kernel<false,append>", "time_attn64_kernel<true>",
+    "time_attn_kernel<64>", "time_attn_kernel<32>", "time_attn_kernel<16>", nullptr};
+static const char* const k_family_names[FAM_N] = {"small_attn", "pool_mix", "time_kv_append", "time_attn"};
+static const char* const* const k_family_forms[FAM_N] = {k_small_attn_forms, k_pool_mix_forms, k_time_kv_append_forms, k_time_attn_forms};
+static const char* g_last_form[FAM_N] = {nullptr, nullptr, nullptr, nullptr};
+static inline void note_form(int fam, const char* name) { g_last_form[fam] = name; }
+static int form_family(const char* family) {
+    for (int f = 0; f < FAM_N; ++f) if (family && !strcmp(family, k_family_names[f])) return f;
+    return -1;
+}
+const char* attn_last_form(const char* family) {
+    const int f = form_family(family);
+    return f < 0 ? nullptr : g_last_form[f];
+}
+int attn_form_name(const char* family, int i, const char** name) {      // returns the number of forms of the family (-1: unknown family)
+    const int f = form_family(family);
+    if (f < 0) return -1;
+    int n = 0;
+    while (k_family_forms[f][n]) ++n;
+    if (name) *name = (i >= 0 && i < n) ? k_family_forms[f][i] : nullptr;
+    return n;
+}
 
 // Generic form: one block (4 waves) per (group, head).  Wave w prepares keys w, w+4, ... (value-residual mix, key l2-norm)
 // into LDS, then owns queries w, w+4, ...; scores are wave reductions, so they live in SGPRs.
@@ -363,6 +404,8 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
         // wide form (tokenizer decoder): needs 16-byte aligned rows for the float4 q loads / out stores
         D4_REQUIRE(p.nk <= ATTN_MAXK && p.dh == 64, "attention: %d keys (max %d) / head dim %d (64) not supported by the wide kernel", p.nk, ATTN_MAXK, p.dh);
         D4_REQUIRE(p.q_lo == 0 && p.q_hi == 0, "attention: query restriction is not implemented in the wide kernel");
+        D4_REQUIRE(((uintptr_t)p.q % 16) == 0 && (p.q_group_stride % 4) == 0 && (p.q_item_stride % 4) == 0 && ((uintptr_t)p.out % 16) == 0 &&
+                   (p.o_group_stride % 4) == 0 && (p.o_item_stride % 4) == 0, "attention: the wide kernel needs 16-byte aligned query and output rows");
         const size_t lds = (size_t)(2 * p.nk * 64 + p.nk) * sizeof(float);
         static DeviceOnce attr_set;
         if (attr_set.need()) {
@@ -370,6 +413,7 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
             attr_set.done();
         }
         if (p.groups * p.heads == 0) return 0;
+        note_form(FAM_SMALL_ATTN, "attn_wide_kernel");
         const double wide_bytes = 4.0 * p.groups * p.heads * p.dh * ((double)p.nq * 2 + (double)p.nk * (p.vres ? 3 : 2));
         D4_GLUE_LAUNCH(GL_ATTN_WIDE, wide_bytes, attn_wide_kernel, dim3(p.groups * p.heads), dim3(256), lds, stream, p);
         D4_LAUNCH_CHECK();
@@ -391,6 +435,7 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
                              al4(p.v, p.v_group_stride, p.v_item_stride) && (!p.vres || al4(p.vres, p.r_group_stride, p.r_item_stride)) &&
                              ((uintptr_t)p.k_gamma % 16) == 0;
         *wrote_b = mfma_ok;
+        note_form(FAM_SMALL_ATTN, mfma_ok ? "attn_mfma_kernel<1,1>" : p.dh == 64 ? "space_attn_kernel<64>" : p.dh == 32 ? "space_attn_kernel<32>" : "space_attn_kernel<16>");
         if (mfma_ok) D4_GLUE_LAUNCH(GL_SPACE_ATTN, sp_bytes, (attn_mfma_kernel<1, 1>), dim3(cdiv(waves, 4)), block, 0, stream, p);
         else if (p.dh == 64) D4_GLUE_LAUNCH(GL_SPACE_ATTN, sp_bytes, space_attn_kernel<64>, dim3(waves), block, 0, stream, p);
         else if (p.dh == 32) hipLaunchKernelGGL(space_attn_kernel<32>, dim3(waves), block, 0, stream, p);
@@ -398,20 +443,26 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
         D4_LAUNCH_CHECK();
         return 0;
     }
+    // no form below implements the restricted query set: refuse it instead of writing every query row
+    D4_REQUIRE(p.q_lo == 0 && p.q_hi == 0, "small_attn: the query restriction (q_lo=%d, q_hi=%d) is implemented for self attention over 8..16 tokens only (nq=%d, nk=%d)",
+               p.q_lo, p.q_hi, p.nq, p.nk);
     // algorithmic bytes: a batch-independent operand (group stride 0) is counted once
     auto al4s = [](const void* q, int64_t a, int64_t b) { return ((uintptr_t)q % 16) == 0 && (a % 4) == 0 && (b % 4) == 0; };
-    const bool mfma_small = p.dh == 64 && p.nq <= 64 && p.nk <= 64 && (p.nq <= 16 || p.nk <= 16) && p.q_hi == 0 &&
+    const bool mfma_small = p.dh == 64 && p.nq <= 64 && p.nk <= 64 && (p.nq <= 16 || p.nk <= 16) &&
                             al4s(p.q, p.q_group_stride, p.q_item_stride) && al4s(p.k, p.k_group_stride, p.k_item_stride) &&
                             al4s(p.v, p.v_group_stride, p.v_item_stride) && (!p.vres || al4s(p.vres, p.r_group_stride, p.r_item_stride)) &&
                             ((uintptr_t)p.k_gamma % 16) == 0;
     const double sm_bytes = 4.0 * p.heads * p.dh * ((p.q_group_stride ? (double)p.groups : 1.0) * p.nq + (p.k_group_stride ? (double)p.groups : 1.0) * p.nk * 2 + (double)p.groups * p.nq);
 #define D4_SMALL_ATTN(NK)                                                                                       \
     do {                                                                                                          \
+        note_form(FAM_SMALL_ATTN, p.dh == 64 ? "small_attn_kernel<" #NK ",64>" : p.dh == 32 ? "small_attn_kernel<" #NK ",32>" : "small_attn_kernel<" #NK ",16>"); \
         if (p.dh == 64) D4_GLUE_LAUNCH(GL_SMALL_ATTN, sm_bytes, (small_attn_kernel<NK, 64>), dim3(waves), block, 0, stream, p);        \
         else if (p.dh == 32) hipLaunchKernelGGL((small_attn_kernel<NK, 32>), dim3(waves), block, 0, stream, p);   \
         else hipLaunchKernelGGL((small_attn_kernel<NK, 16>), dim3(waves), block, 0, stream, p);                   \
     } while (0)
     *wrote_b = mfma_small;
+    if (mfma_small) note_form(FAM_SMALL_ATTN, p.nq <= 16 ? (p.nk <= 16 ? "attn_mfma_kernel<1,1>" : p.nk <= 32 ? "attn_mfma_kernel<1,2>" : "attn_mfma_kernel<1,4,2>")
+                                                         : (p.nq <= 32 ? "attn_mfma_kernel<2,1>" : "attn_mfma_kernel<4,1>"));
     if (mfma_small) {         // one wave per (group, head) on the matrix pipe (attn_mfma_kernel): up to 32 x 16 or 16 x 32 (queries x keys)
         if (p.nq <= 16 && p.nk <= 16) D4_GLUE_LAUNCH(GL_SMALL_ATTN, sm_bytes, (attn_mfma_kernel<1, 1>), dim3(cdiv(waves, 4)), block, 0, stream, p);
         else if (p.nq <= 16 && p.nk <= 32) D4_GLUE_LAUNCH(GL_SMALL_ATTN, sm_bytes, (attn_mfma_kernel<1, 2>), dim3(cdiv(waves, 4)), block, 0, stream, p);
@@ -631,6 +682,7 @@ int pool_mix(const PoolMixArgs& p, hipStream_t stream) {
     constexpr int rows_max = 2048;
     const bool kb = p.k_b != nullptr;                // bf16 engine: keys from their bf16 image (template flag of both kernels)
     if (p.M <= rows_max && p.D <= 512) {
+        note_form(FAM_POOL_MIX, p.D <= 256 ? (kb ? "pool_mix_rows_kernel<1,bf16>" : "pool_mix_rows_kernel<1>") : (kb ? "pool_mix_rows_kernel<2,bf16>" : "pool_mix_rows_kernel<2>"));
         const double rb = 4.0 * p.M * ((double)p.L * (p.D + p.ldk) + p.ldq + p.D + (double)p.heads * p.D);
         if (p.D <= 256) { if (kb) hipLaunchKernelGGL((pool_mix_rows_kernel<1, true>), dim3(p.M), block, 0, stream, p); else hipLaunchKernelGGL(pool_mix_rows_kernel<1>, dim3(p.M), block, 0, stream, p); }
         else if (kb) hipLaunchKernelGGL((pool_mix_rows_kernel<2, true>), dim3(p.M), block, 0, stream, p);
@@ -639,6 +691,8 @@ int pool_mix(const PoolMixArgs& p, hipStream_t stream) {
         return 0;
     }
     // algorithmic bytes: L hiddens + L projected keys per token row, queries + the row itself, the per-head mixes written
+    note_form(FAM_POOL_MIX, p.D <= 256 ? (kb ? "pool_mix_kernel<1,bf16>" : "pool_mix_kernel<1>") : p.D <= 512 ? (kb ? "pool_mix_kernel<2,bf16>" : "pool_mix_kernel<2>")
+                                       : (kb ? "pool_mix_kernel<4,bf16>" : "pool_mix_kernel<4>"));
     const double pm_bytes = 4.0 * p.M * ((double)p.L * (p.D + p.ldk) + p.ldq + p.D + (double)p.heads * p.D);
     if (p.D <= 256) { if (kb) hipLaunchKernelGGL((pool_mix_kernel<1, false, true>), grid, block, 0, stream, p); else hipLaunchKernelGGL(pool_mix_kernel<1>, grid, block, 0, stream, p); }
     else if (p.D <= 512) { if (kb) hipLaunchKernelGGL((pool_mix_kernel<2, false, true>), grid, block, 0, stream, p); else D4_GLUE_LAUNCH(GL_POOL_MIX, pm_bytes, pool_mix_kernel<2>, grid, block, 0, stream, p); }
@@ -684,7 +738,16 @@ __global__ __launch_bounds__(256) void time_kv_append_kernel(TimeAttnArgs p) {
     const float vr = act ? p.vres[(int64_t)row * p.ldv + hl] : 0.f;
     const float w = sigmoidf(pr[3 * hd + p.H + h]);
     v = lerp_torch(v, vr, w);
-    const float nrm = sqrtf(wave_sum(k * k));
+    float ksq;
+    if constexpr (DH == 64) {
+        // |k|^2 summed in the order of time_new_kv (the appending decode kernels): four adjacent features in sequence, then a balanced tree over
+        // the 16 groups — so the cached decode leaves the same cache bits as one launch (time_attn_append) and as two, at any head count
+        const int l4 = lane & ~3;
+        const float k0 = __shfl(k, l4), k1 = __shfl(k, l4 + 1), k2 = __shfl(k, l4 + 2), k3 = __shfl(k, l4 + 3);
+        ksq = ((k0 * k0 + k1 * k1) + k2 * k2) + k3 * k3;
+        ksq += __shfl_xor(ksq, 4); ksq += __shfl_xor(ksq, 8); ksq += __shfl_xor(ksq, 16); ksq += __shfl_xor(ksq, 32);
+    } else ksq = wave_sum(k * k);
+    const float nrm = sqrtf(ksq);
     k = k / fmaxf(nrm, 1e-12f) * (act ? (p.k_gamma[hl] + 1.f) * sqrtf((float)dh) : 0.f);
     const int pos = (p.t0_dev ? *p.t0_dev : p.t0) + tq;
     k = rotate_half_lane(k, lane, (float)pos, p.inv_freq, dh);
@@ -1052,6 +1115,8 @@ int time_kv_append(const TimeAttnArgs& p, hipStream_t stream) {
     const double ka_bytes = 4.0 * waves * p.dh * 5.0;
     const bool al4 = (p.ldp % 4) == 0 && (p.ldv % 4) == 0 && ((uintptr_t)p.proj % 16) == 0 && ((uintptr_t)p.vres % 16) == 0 && ((uintptr_t)p.cache % 16) == 0 &&
                      ((uintptr_t)p.k_gamma % 16) == 0 && ((uintptr_t)p.inv_freq % 16) == 0 && (((int64_t)p.cache_batch * (p.cache_S > 0 ? p.cache_S : p.S) * p.H * p.Tcap) % 4) == 0;
+    note_form(FAM_TIME_KV_APPEND, p.dh == 64 ? ((p.H % 4) == 0 && al4 ? "time_kv_append4_kernel" : "time_kv_append_kernel<64>")
+                                             : p.dh == 32 ? "time_kv_append_kernel<32>" : "time_kv_append_kernel<16>");
     if (p.dh == 64 && (p.H % 4) == 0 && al4)               // four heads per wave; else the one-head-per-wave form
         D4_GLUE_LAUNCH(GL_TIME_KV_APPEND, ka_bytes, time_kv_append4_kernel, dim3(cdiv(waves / 4, 4)), dim3(256), 0, stream, p);
     else if (p.dh == 64) D4_GLUE_LAUNCH(GL_TIME_KV_APPEND, ka_bytes, time_kv_append_kernel<64>, dim3(cdiv(waves, 4)), dim3(256), 0, stream, p);
@@ -1080,6 +1145,8 @@ int time_attn_append(const TimeAttnArgs& p, hipStream_t stream) {
     // algorithmic bytes: the append's (k, v, value residual read; K, V written) + the attention's (history K / V, q read, out written)
     const double bytes = 4.0 * units * 64.0 * 5.0 + 4.0 * units * 64.0 * (2.0 * (p.t0 + 1) + 2.0);
     const int bucket = time_history_bucket(p.t0);
+    note_form(FAM_TIME_ATTN, (p.H % 4) == 0 && bucket == 0 ? "time_attn64_few_kernel<8,append>"
+                             : (p.H % 4) == 0 && bucket == 1 ? "time_attn64_few_kernel<16,append>" : "time_attn64_kernel<false,append>");
     if (bucket == 0 && (p.H % 4) == 0)
         D4_GLUE_LAUNCH(GL_TIME_ATTN, bytes, (time_attn64_few_kernel<8, true>), dim3(cdiv(units / 4, 4)), dim3(256), 0, stream, p);
     else if (bucket == 1 && (p.H % 4) == 0)
@@ -1092,16 +1159,20 @@ int time_attn_append(const TimeAttnArgs& p, hipStream_t stream) {
 int time_attn(const TimeAttnArgs& p, hipStream_t stream) {
     const int waves = p.B * p.Tq * p.S * p.H;
     if (waves == 0) return 0;
-    if (p.dh == 64 && (p.ldp % 4) == 0 && (p.ldo % 4) == 0) {         // (else the one-key-per-reduction form: head dims 16 / 32, unaligned rows)
+    // the head-dim-64 forms read q, K, V and write out as float4: 16-byte aligned operands and row strides
+    const bool al4 = (p.ldp % 4) == 0 && (p.ldo % 4) == 0 && ((uintptr_t)p.proj % 16) == 0 && ((uintptr_t)p.cache % 16) == 0 && ((uintptr_t)p.out % 16) == 0 &&
+                     ((uintptr_t)p.inv_freq % 16) == 0 && (!p.out_b || ((uintptr_t)p.out_b % 8) == 0) &&
+                     (((int64_t)p.cache_batch * (p.cache_S > 0 ? p.cache_S : p.S) * p.H * p.Tcap) % 4) == 0;
+    if (p.dh == 64 && al4) {                                          // (else the one-key-per-reduction form: head dims 16 / 32, unaligned rows)
         const int units = p.B * p.S * p.H;
         // algorithmic bytes (cached decode): the K and V of frames 0..t0 of every (column, head) read once + q read + out written
         const double ta_bytes = 4.0 * units * 64.0 * (2.0 * (p.t0 + 1) + 2.0);
-        const bool al4 = ((uintptr_t)p.proj % 16) == 0 && ((uintptr_t)p.cache % 16) == 0 && ((uintptr_t)p.out % 16) == 0 && ((uintptr_t)p.inv_freq % 16) == 0 &&
-                         (((int64_t)p.cache_batch * (p.cache_S > 0 ? p.cache_S : p.S) * p.H * p.Tcap) % 4) == 0;
         const int bucket = time_history_bucket(p.t0);                           // the same rule eagerly and under graph replay (graphs are keyed on it)
-        if (p.Tq == 1 && bucket == 0 && (p.H % 4) == 0 && al4)           // a short history: four heads per wave
+        note_form(FAM_TIME_ATTN, p.Tq != 1 ? "time_attn64_kernel<true>" : (p.H % 4) == 0 && bucket == 0 ? "time_attn64_few_kernel<8>"
+                                 : (p.H % 4) == 0 && bucket == 1 ? "time_attn64_few_kernel<16>" : "time_attn64_kernel<false>");
+        if (p.Tq == 1 && bucket == 0 && (p.H % 4) == 0)                  // a short history: four heads per wave
             D4_GLUE_LAUNCH(GL_TIME_ATTN, ta_bytes, time_attn64_few_kernel<8>, dim3(cdiv(units / 4, 4)), dim3(256), 0, stream, p);
-        else if (p.Tq == 1 && bucket == 1 && (p.H % 4) == 0 && al4)
+        else if (p.Tq == 1 && bucket == 1 && (p.H % 4) == 0)
             D4_GLUE_LAUNCH(GL_TIME_ATTN, ta_bytes, time_attn64_few_kernel<16>, dim3(cdiv(units / 4, 4)), dim3(256), 0, stream, p);
         else if (p.Tq == 1) D4_GLUE_LAUNCH(GL_TIME_ATTN, ta_bytes, time_attn64_kernel<false>, dim3(cdiv(units, 4)), dim3(256), 0, stream, p);
         else {
@@ -1111,6 +1182,7 @@ int time_attn(const TimeAttnArgs& p, hipStream_t stream) {
         }
     }
     else {
+        note_form(FAM_TIME_ATTN, p.dh == 64 ? "time_attn_kernel<64>" : p.dh == 32 ? "time_attn_kernel<32>" : "time_attn_kernel<16>");
         if (p.dh == 64) hipLaunchKernelGGL(time_attn_kernel<64>, dim3(cdiv(waves, 4)), dim3(256), 0, stream, p);
         else if (p.dh == 32) hipLaunchKernelGGL(time_attn_kernel<32>, dim3(cdiv(waves, 4)), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(time_attn_kernel<16>, dim3(cdiv(waves, 4)), dim3(256), 0, stream, p);

@@ -1688,6 +1688,51 @@ int d4_rmsnorm(const float* x, int ldx, const float* gamma, float* y, int ldy, i
     return d4::rmsnorm_rows(x, ldx, gamma, y, ldy, rows, dim, eps, static_cast<hipStream_t>(stream));
 }
 
+// Operator-level test entry points of the inference attention cores (attn.hip): each fills the launcher's argument struct and calls it.
+int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
+    d4::SmallAttnArgs sa{};
+    sa.q = q; sa.q_group_stride = q_group_stride; sa.q_item_stride = q_item_stride;
+    sa.k = k; sa.k_group_stride = k_group_stride; sa.k_item_stride = k_item_stride;
+    sa.v = v; sa.v_group_stride = v_group_stride; sa.v_item_stride = v_item_stride;
+    sa.gate = gate; sa.g_group_stride = g_group_stride; sa.g_item_stride = g_item_stride;
+    sa.k_gamma = k_gamma;
+    sa.vres = vres; sa.r_group_stride = r_group_stride; sa.r_item_stride = r_item_stride;
+    sa.mix = mix; sa.m_group_stride = m_group_stride; sa.m_item_stride = m_item_stride;
+    sa.out = out; sa.o_group_stride = o_group_stride; sa.o_item_stride = o_item_stride; sa.out_b = out_b;
+    sa.groups = groups; sa.heads = heads; sa.nq = nq; sa.nk = nk;
+    sa.softclamp = softclamp; sa.mask_special = mask_special; sa.belief = belief;
+    sa.q_lo = q_lo; sa.q_hi = q_hi; sa.q_last = q_last; sa.dh = dh;
+    return d4::small_attn(sa, static_cast<hipStream_t>(stream));
+}
+
+int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
+                const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
+                const uint16_t* hid_b, void* stream) {
+    d4::PoolMixArgs pm{};
+    pm.q = q; pm.ldq = ldq; pm.x = x; pm.ldx = ldx; pm.gate_w = gate_w; pm.k = k; pm.ldk = ldk; pm.hid = hid; pm.D = D; pm.k_gamma = k_gamma;
+    pm.u = u; pm.M = M; pm.L = L; pm.heads = heads; pm.eps = eps; pm.u_b = u_b; pm.k_b = k_b; pm.q_b = q_b; pm.hid_b = hid_b;
+    return d4::pool_mix(pm, static_cast<hipStream_t>(stream));
+}
+
+int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, const float* k_gamma, const float* inv_freq, float* cache, float* out,
+                        int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
+                        float softclamp, int dh, int mode, void* stream) {
+    D4_REQUIRE(mode >= 0 && mode <= 2, "d4_time_attn_decode: mode %d (0 append + attend, 1 append only, 2 attend only)", mode);
+    d4::TimeAttnArgs ta{};
+    ta.proj = proj; ta.ldp = ldp; ta.vres = vres; ta.ldv = ldv; ta.k_gamma = k_gamma; ta.inv_freq = inv_freq; ta.cache = cache;
+    ta.out = out; ta.ldo = ldo; ta.out_b = out_b; ta.B = B; ta.S = S; ta.H = H; ta.Tq = Tq; ta.t0 = t0; ta.Tcap = Tcap;
+    ta.cache_batch = cache_batch; ta.cache_S = cache_S; ta.t0_dev = t0_dev; ta.softclamp = softclamp; ta.dh = dh;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return mode == 0 ? d4::time_attn_append(ta, s) : mode == 1 ? d4::time_kv_append(ta, s) : d4::time_attn(ta, s);
+}
+
+const char* d4_debug_last_form(const char* family) { return d4::attn_last_form(family); }
+int d4_debug_forms(const char* family, int i, const char** name) { return d4::attn_form_name(family, i, name); }
+
 int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps, void* stream) {
     D4_REQUIRE(x && dy && gamma && dx && d_gamma && scratch, "d4_rmsnorm_backward: null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -211,6 +211,10 @@ inline int time_history_bucket(int t0) { return t0 < 8 ? 0 : (t0 < 16 ? 1 : 2); 
 int time_kv_append(const TimeAttnArgs& p, hipStream_t stream);   // normalise/rotate/mix new K,V -> cache[t0 .. t0+Tq)
 int time_attn(const TimeAttnArgs& p, hipStream_t stream);        // attend over cache[0 .. t0+i], belief + gates
 int time_attn_append(const TimeAttnArgs& p, hipStream_t stream); // both; ONE launch for the cached decode of one frame (head dim 64, aligned rows)
+// Host-side record of the kernel form each launcher above (families "small_attn", "pool_mix", "time_kv_append", "time_attn") picked last, and the
+// full list of a family's forms: for the operator tests (tests/test_gpu_attn_cores.py).
+const char* attn_last_form(const char* family);                  // nullptr: unknown family or nothing launched yet
+int attn_form_name(const char* family, int i, const char** name); // number of forms of the family (-1: unknown); *name = form i or nullptr
 
 // ------------------------------------------------------------------------------------ elementwise / glue
 int fold_rows(const float* W, const float* gamma, float* out, int rows, int K, int ld_out, hipStream_t s);

@@ -456,6 +456,29 @@ int d4_cross_attn_backward_saved(const float* q_tokens, const float* ctx, const 
 int d4_rmsnorm(const float* x, int ldx, const float* gamma, float* y, int ldy, int rows, int dim,
                float eps, void* stream);
 /* backward of nn.RMSNorm (autograd of y = x / rms(x) * gamma): dx [rows][dim], d_gamma [dim]; scratch = rows * dim floats. */
+/* Operator-level entry points of the inference attention cores (test / tooling use; the engine calls the same launchers).  Arguments are the
+ * fields of the launchers' argument structs (csrc/kernels.h: SmallAttnArgs, PoolMixArgs, TimeAttnArgs); strides and leading dimensions in floats.
+ *   d4_small_attn        attention of `groups` x `heads` units, nq queries over nk keys: value-residual mix, key norm, softclamp, special-token mask,
+ *                        belief projection, head gates; (q_lo, q_hi, q_last) restricts the query set (self attention over 8..16 tokens only).
+ *   d4_pool_mix          AttentionPool core: per-head softmax over L hiddens -> gated mix of the normalised hiddens, u [M][heads][D].
+ *   d4_time_attn_decode  time attention over the KV cache [2][cache_batch * cache_S][H][Tcap][dh]; mode 0: append + attend (the engine's call),
+ *                        1: append only, 2: attend only.  t0_dev (device int, may be null) overrides t0 on the device. */
+int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream);
+int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
+                const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
+                const uint16_t* hid_b, void* stream);
+int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, const float* k_gamma, const float* inv_freq, float* cache, float* out,
+                        int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
+                        float softclamp, int dh, int mode, void* stream);
+/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn") picked at their last call (NULL: unknown
+ * family or no call yet), and the family's full list: d4_debug_forms returns the number of forms (-1: unknown family), *name = form i or NULL. */
+const char* d4_debug_last_form(const char* family);
+int d4_debug_forms(const char* family, int i, const char** name);
+
 int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps,
                         void* stream);
 int d4_hl_gauss_scalar(const float* logits, int ld, const float* centers, float* out, int rows,
