@@ -92,6 +92,7 @@ SYMBOLS = {
     'd4_decoder_forward': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'd4_ff_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
     'd4_train_arith_set': (_I, [_I]),
+    'd4_train_wide_set': (_I, [_I]),
     'd4_train_arith_get': (_I, []),
     'd4_train_scratch_bind': (_I, [_P, C.c_size_t]),
     'd4_ff_bf16_scratch_bytes': (C.c_size_t, [_I] * 3),

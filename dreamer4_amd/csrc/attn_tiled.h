@@ -1,5 +1,6 @@
-// The attention core of the training path: the argument block shared by the whole-problem-in-LDS kernel (backward.hip: attn_bwd_kernel,
-// <= 64 items per group) and the tiled causal core of the time layers (attn_tiled.hip, up to ATT_MAX_FRAMES frames).
+// The attention cores of the training path: the argument blocks shared by the whole-problem-in-LDS kernels (backward.hip: attn_bwd_kernel,
+// xattn_bwd_kernel, <= 64 items per group and side) and the tiled core (attn_tiled.hip, up to ATT_MAX_FRAMES items: the time layers, and
+// with d4_train_wide_set(1) the within-frame and cross attentions).
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -27,11 +28,27 @@ struct AttnBwdArgs {
     const float* inv_freq = nullptr;   // [DH / 2] rotary frequencies applied to q and k at position j (time attention), or null
 };
 
-constexpr int ATT_MAX_FRAMES = 1024;   // cap of the tiled core (the per-row planes and the post-pass are sized for it)
+// Cross attention: G groups of nq queries over nk keys, one problem per (group, head).  projq rows: q @ 0, gate logit @ hd + head; projk rows: k @ 0, v @ hd.
+struct XAttnArgs {
+    const float* projq; int ldq;       // [G * nq][ldq], row g * nq + i
+    const float* projk; int ldk;       // key j of group g: row g * nk + j (group major) or j * G + g (item major: the stack of hiddens)
+    const float* gamma;
+    const float* d_o3;                 // [G * nq][hd] or null (forward only)
+    float* o3;                         // [G * nq][hd]
+    float* dprojq; float* dprojk;      // gradients, same layouts
+    float* dgamma_part;                // [G][hd]
+    int G, nq, nk, heads, item_major;
+    float softclamp;
+};
 
-// floats of per-row planes the tiled core needs behind the block's workspace (R rows in all)
+constexpr int ATT_MAX_FRAMES = 1024;   // cap of the tiled core, items per problem side (the per-row planes and the post-pass are sized for it)
+
+// floats of per-row planes the tiled core needs behind the block's workspace (R rows in all; cross: Rq query rows, Rk key rows)
 size_t attn_tiled_floats(int R, int heads, int dh);
-// time geometry only (causal, rotary): same outputs as attn_bwd_kernel (o3; with d_o3 also dproj, d_rv, dgamma_part)
+size_t attn_tiled_cross_floats(int Rq, int Rk, int heads, int dh);
+// the time geometry (causal, rotary) or the within-frame geometry (neither; num_special): same outputs as attn_bwd_kernel (o3; with d_o3 also dproj, d_rv, dgamma_part)
 int attn_tiled_core(const AttnBwdArgs& a, int dh, float* planes, hipStream_t s);
+// the cross geometry: same outputs as xattn_bwd_kernel (o3; with d_o3 also dprojq, dprojk, dgamma_part)
+int attn_tiled_cross_core(const XAttnArgs& a, int dh, float* planes, hipStream_t s);
 
 }  // namespace d4

@@ -1,8 +1,15 @@
-// Tiled (flash-style) causal attention core of the training time layers: the semantics of backward.hip's attn_bwd_kernel (rotary on q and on
-// the normalised, scaled key; key RMS-norm with (gamma + 1) sqrt(dh); value-residual mix; softclamp; causal mask; belief projection; head
-// gate) for up to ATT_MAX_FRAMES frames per trajectory, with memory linear in the frames.
+// Tiled (flash-style) attention core of the training path: the semantics of backward.hip's attn_bwd_kernel (rotary on q and on the
+// normalised, scaled key; key RMS-norm with (gamma + 1) sqrt(dh); value-residual mix; softclamp; mask; belief projection; head gate) and
+// of its xattn_bwd_kernel, for up to ATT_MAX_FRAMES items per problem side, with memory linear in the items.  One set of kernels, three
+// geometries (the template argument GEO picks the visibility rule and which per-row features exist):
+//   GEO_TIME   the time layers: causal (j <= i), rotary, value residual, belief
+//   GEO_FRAME  within a frame: no rotary; query i sees key j unless i is ordinary and j special (the last num_special items); value
+//              residual, belief (a runtime flag)
+//   GEO_CROSS  nq queries over nk keys from separate projection buffers (keys group major or item major): no mask, no value residual, no belief
 //
-// Six kernels over per-row planes ([group * heads + head][frame][DH], so a (group, head) problem is contiguous whatever the row geometry):
+// Six kernels over per-row planes ([group * heads + head][item][DH], so a (group, head) problem is contiguous whatever the row geometry;
+// query-side planes hold nq rows per problem, key-side planes nk; the frames / keys below are the time geometry's, the other two differ
+// only in the bounds sees() / last_key() / first_query() give):
 //   pre    one wave per (row, head): phase A of attn_bwd_kernel written to the planes (rotated q, normalised / scaled / rotated k, unrotated
 //          normalised k, mixed v, 1/|k|, 1/|v|, mix and gate sigmoids)
 //   fwd    one wave per 16 queries (a block = a 64-query tile) walks the keys <= its last query, 64 at a time, with an online softmax;
@@ -26,27 +33,72 @@
 namespace d4 {
 
 int g_time_attn_tiled = 0;
+int g_space_attn_tiled = 0;
+int g_cross_attn_tiled = 0;
 
 namespace {
+
+enum { GEO_TIME = 0, GEO_FRAME = 1, GEO_CROSS = 2 };
+
+// row of item j of group g = (g / g_inner) * outer + g % g_inner + j * item   (AttnBwdArgs' rule; item-major keys: g_inner G, outer 0, item G)
+struct RowMap { int g_inner; int64_t outer, item; };
+__device__ __forceinline__ int64_t row_of(const RowMap& m, int g, int j) { return (int64_t)(g / m.g_inner) * m.outer + (g % m.g_inner) + j * m.item; }
+
+// what the kernels see of either argument block (AttnBwdArgs: one buffer, both sides; XAttnArgs: two)
+struct TiledArgs {
+    const float* projq; int ldq;       // q @ 0, gate logit @ gcol + head
+    const float* projk; int ldk;       // k @ kcol, v @ vcol, mix logit @ mcol + head (self geometries)
+    int kcol, vcol, gcol, mcol;
+    const float *rv, *gamma, *d_o3, *inv_freq;
+    float *o3, *dprojq, *dprojk, *d_rv, *dgamma_part;
+    int G, nq, nk, heads;
+    float softclamp; int num_special, belief;
+    RowMap qm, km;
+};
+
+// query i sees key j
+template <int GEO>
+__device__ __forceinline__ bool sees(int i, int j, int nk, int fs) {
+    if (GEO == GEO_TIME) return j <= i && j < nk;
+    if (GEO == GEO_FRAME) return j < nk && !(i < fs && j >= fs);
+    return j < nk;
+}
+// the last key any of the queries i0 .. i0 + 15 sees (a wave of ordinary queries stops before the special block)
+template <int GEO>
+__device__ __forceinline__ int last_key(int i0, int nk, int fs) {
+    if (GEO == GEO_TIME) return (i0 + 15 < nk - 1) ? i0 + 15 : nk - 1;
+    if (GEO == GEO_FRAME) return (i0 + 15 < fs) ? fs - 1 : nk - 1;
+    return nk - 1;
+}
+// the first query tile (a multiple of 16) with a query that sees any of the keys j0 .. j0 + 15 (an all-special key tile: the special queries only)
+template <int GEO>
+__device__ __forceinline__ int first_query(int j0, int fs) {
+    if (GEO == GEO_TIME) return j0;
+    if (GEO == GEO_FRAME) return j0 >= fs ? (fs & ~15) : 0;
+    return 0;
+}
 
 __device__ __forceinline__ float sigm_t(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct TiledPlanes {
-    float *qr, *kn, *kh, *vm, *o, *dO, *dvd, *dq, *dkn, *dv;      // [F * heads][T][DH]
-    float *kinv, *vinv, *mx, *gt, *lse, *delta;                    // [F * heads][T]
+    float *qr, *o, *dO, *dq;                                       // [G * heads][nq][DH]
+    float *kn, *kh, *vm, *dvd, *dkn, *dv;                          // [G * heads][nk][DH]  (dvd, like vinv and mx: the self geometries only)
+    float *gt, *lse, *delta;                                       // [G * heads][nq]
+    float *kinv, *vinv, *mx;                                       // [G * heads][nk]
 };
 
-constexpr int TL_PLANES = 10, TL_SCALARS = 6;
-
-TiledPlanes carve(float* base, int R, int heads, int dh) {
-    TiledPlanes t{};
+// Rq query rows and Rk key rows in all (the self geometries: Rq = Rk); base null: the size only
+size_t carve(TiledPlanes& t, float* base, size_t Rq, size_t Rk, int heads, int dh, bool cross) {
     size_t off = 0;
-    auto take = [&](size_t n) { float* p = base + off; off += (n + 63) / 64 * 64; return p; };
-    const size_t big = (size_t)R * heads * dh, small = (size_t)R * heads;
-    t.qr = take(big); t.kn = take(big); t.kh = take(big); t.vm = take(big); t.o = take(big); t.dO = take(big); t.dvd = take(big);
-    t.dq = take(big); t.dkn = take(big); t.dv = take(big);
-    t.kinv = take(small); t.vinv = take(small); t.mx = take(small); t.gt = take(small); t.lse = take(small); t.delta = take(small);
-    return t;
+    auto take = [&](size_t n) { float* p = base ? base + off : nullptr; off += (n + 63) / 64 * 64; return p; };
+    const size_t bq = Rq * heads * dh, bk = Rk * heads * dh, sq = Rq * heads, sk = Rk * heads;
+    t.qr = take(bq); t.kn = take(bk); t.kh = take(bk); t.vm = take(bk); t.o = take(bq); t.dO = take(bq);
+    t.dvd = cross ? nullptr : take(bk);
+    t.dq = take(bq); t.dkn = take(bk); t.dv = take(bk);
+    t.kinv = take(sk);
+    t.vinv = cross ? nullptr : take(sk); t.mx = cross ? nullptr : take(sk);
+    t.gt = take(sq); t.lse = take(sq); t.delta = take(sq);
+    return off;
 }
 
 // rotary as in attn_bwd_kernel: lane = feature, the partner feature is lane ^ (DH / 2)
@@ -65,37 +117,54 @@ __device__ __forceinline__ float rot_bwd(float y, int pos, float freq, int lane,
     return on ? y * cs + (lane < DH / 2 ? partner : -partner) : 0.f;
 }
 
-__device__ __forceinline__ int64_t group_row0(const AttnBwdArgs& p, int f) { return (int64_t)(f / p.g_inner) * p.g_outer_stride + (f % p.g_inner); }
-
-// ---- pre-pass: grid (F * heads, ceil(T / 4)), one wave per row
-template <int DH>
-__global__ __launch_bounds__(256) void tiled_pre_kernel(AttnBwdArgs p, TiledPlanes t) {
-    const int T = p.S, hd = p.heads * DH;
+// ---- pre-pass: grid (G * heads, ceil(max(nq, nk) / 4)), one wave per row
+template <int DH, int GEO>
+__global__ __launch_bounds__(256) void tiled_pre_kernel(TiledArgs p, TiledPlanes t) {
+    const int hd = p.heads * DH;
     const int gh = blockIdx.x, f = gh / p.heads, h = gh % p.heads;
     const int lane = threadIdx.x & 63;
     const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (j >= T) return;
     const bool on = lane < DH;
-    const int64_t row = group_row0(p, f) + j * p.item_stride;
     const float sc = on ? (p.gamma[h * DH + lane] + 1.f) * sqrtf((float)DH) : 0.f;
-    const float freq = on ? p.inv_freq[lane & (DH / 2 - 1)] : 0.f;
-    const float* pr = p.proj + row * p.ldp;
+    if (GEO == GEO_CROSS) {                                            // the two sides are different rows of different buffers
+        if (j < p.nk) {
+            const float* pr = p.projk + row_of(p.km, f, j) * p.ldk;
+            const float kv = on ? pr[p.kcol + h * DH + lane] : 0.f, vv = on ? pr[p.vcol + h * DH + lane] : 0.f;
+            const float ki = 1.f / fmaxf(sqrtf(wave_sum(kv * kv)), 1e-12f);
+            const int64_t sj = (int64_t)gh * p.nk + j;
+            if (on) { t.kh[sj * DH + lane] = kv * ki; t.kn[sj * DH + lane] = kv * ki * sc; t.vm[sj * DH + lane] = vv; }
+            if (lane == 0) t.kinv[sj] = ki;
+        }
+        if (j < p.nq) {
+            const float* pr = p.projq + row_of(p.qm, f, j) * p.ldq;
+            const int64_t si = (int64_t)gh * p.nq + j;
+            if (on) t.qr[si * DH + lane] = pr[h * DH + lane];
+            if (lane == 0) t.gt[si] = sigm_t(pr[p.gcol + h]);
+        }
+        return;
+    }
+    const int T = p.nk;
+    if (j >= T) return;
+    const int64_t row = row_of(p.km, f, j);
+    const float freq = (GEO == GEO_TIME && on) ? p.inv_freq[lane & (DH / 2 - 1)] : 0.f;
+    const float* pr = p.projk + row * p.ldk;
     const float qv = on ? pr[h * DH + lane] : 0.f, kv = on ? pr[hd + h * DH + lane] : 0.f;
     float vv = on ? pr[2 * hd + h * DH + lane] : 0.f;
     float mx = 0.f;
     if (p.rv) {
-        mx = sigm_t(pr[3 * hd + p.hp4 + h]);
+        mx = sigm_t(pr[p.mcol + h]);
         const float r = on ? p.rv[row * hd + h * DH + lane] : 0.f;
         vv = vv + mx * (r - vv);
     }
     const float ki = 1.f / fmaxf(sqrtf(wave_sum(kv * kv)), 1e-12f);
     const float vi = 1.f / fmaxf(sqrtf(wave_sum(vv * vv)), 1e-12f);
-    const float qrot = rot_fwd<DH>(qv, j, freq, lane, on), krot = rot_fwd<DH>(kv * ki * sc, j, freq, lane, on);
+    const float qrot = GEO == GEO_TIME ? rot_fwd<DH>(qv, j, freq, lane, on) : qv;
+    const float krot = GEO == GEO_TIME ? rot_fwd<DH>(kv * ki * sc, j, freq, lane, on) : kv * ki * sc;
     const int64_t sj = (int64_t)gh * T + j;
     if (on) {
         t.qr[sj * DH + lane] = qrot; t.kh[sj * DH + lane] = kv * ki; t.kn[sj * DH + lane] = krot; t.vm[sj * DH + lane] = vv;
     }
-    if (lane == 0) { t.kinv[sj] = ki; t.vinv[sj] = vi; t.mx[sj] = mx; t.gt[sj] = sigm_t(pr[3 * hd + h]); }
+    if (lane == 0) { t.kinv[sj] = ki; t.vinv[sj] = vi; t.mx[sj] = mx; t.gt[sj] = sigm_t(pr[p.gcol + h]); }
 }
 
 // operand row `row` of a [T][DH] plane as DH / 16 float4s: features 16 s + 4 kq .. + 3 (zero past the last row)
@@ -133,22 +202,25 @@ __device__ __forceinline__ void acc_rows(f32x4 (&acc)[NS], const f32x4& a, const
     }
 }
 
-// ---- forward: grid (F * heads, ceil(T / 64)); wave w of a block owns queries 64 blockIdx.y + 16 w .. + 15
-template <int DH>
-__global__ __launch_bounds__(256) void tiled_fwd_kernel(AttnBwdArgs p, TiledPlanes t) {
+// ---- forward: grid (G * heads, ceil(nq / 64)); wave w of a block owns queries 64 blockIdx.y + 16 w .. + 15
+// Every query sees key 0 in all three geometries (an ordinary key unless every item is special, and then every query is special), so the
+// running maximum is finite after the first 64 keys; a later tile that is all masked for a row leaves that row's m, l and o as they are
+// (its scores are -FLT_MAX, which the exponential step turns into exact zeros).
+template <int DH, int GEO>
+__global__ __launch_bounds__(256) void tiled_fwd_kernel(TiledArgs p, TiledPlanes t) {
     constexpr int NS = DH / 16;
-    const int T = p.S, hd = p.heads * DH;
+    const int nq = p.nq, nk = p.nk, hd = p.heads * DH, fs = nk - p.num_special;
     const int gh = blockIdx.x, f = gh / p.heads, h = gh % p.heads;
     const int lane = threadIdx.x & 63, tok = lane & 15, kq = lane >> 4;
     const int i0 = blockIdx.y * 64 + (threadIdx.x >> 6) * 16;
-    if (i0 >= T) return;
-    const int64_t pb = (int64_t)gh * T * DH, sb = (int64_t)gh * T;
-    const float *Q = t.qr + pb, *K = t.kn + pb, *V = t.vm + pb;
+    if (i0 >= nq) return;
+    const int64_t pbq = (int64_t)gh * nq * DH, sbq = (int64_t)gh * nq, pbk = (int64_t)gh * nk * DH, sbk = (int64_t)gh * nk;
+    const float *Q = t.qr + pbq, *K = t.kn + pbk, *V = t.vm + pbk;
     const float scale = rsqrtf((float)DH);
     const int i = i0 + tok;
-    const int jmax = (i0 + 15 < T - 1) ? i0 + 15 : T - 1;           // the last key any query of this wave sees
+    const int jmax = last_key<GEO>(i0, nk, fs);                       // the last key any query of this wave sees
     f32x4 q4[NS], o[NS];
-    load_rows<NS>(q4, Q, i, T, kq);
+    load_rows<NS>(q4, Q, i, nq, kq);
 #pragma unroll
     for (int s = 0; s < NS; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -FLT_MAX, l = 0.f;
@@ -162,14 +234,14 @@ __global__ __launch_bounds__(256) void tiled_fwd_kernel(AttnBwdArgs p, TiledPlan
             pr[kt] = f32x4{-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
             if (jb > jmax) continue;                                   // (wave-uniform)
             f32x4 k4[NS];
-            load_rows<NS>(k4, K, jb + tok, T, kq);
+            load_rows<NS>(k4, K, jb + tok, nk, kq);
             const f32x4 st = dot_tile<NS>(k4, q4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = jb + 4 * kq + r;
                 float simc = st[r] * scale;
                 if (p.softclamp > 0.f) simc = tanhf(simc / p.softclamp) * p.softclamp;
-                pr[kt][r] = (j <= i && j < T) ? simc : -FLT_MAX;
+                pr[kt][r] = sees<GEO>(i, j, nk, fs) ? simc : -FLT_MAX;
                 mt = fmaxf(mt, pr[kt][r]);
             }
         }
@@ -195,65 +267,65 @@ __global__ __launch_bounds__(256) void tiled_fwd_kernel(AttnBwdArgs p, TiledPlan
         for (int kt = 0; kt < 4; ++kt) {
             const int jb = j0 + 16 * kt;
             if (jb > jmax) continue;
-            acc_rows<NS>(o, pr[kt], V, jb, T, kq, tok);
+            acc_rows<NS>(o, pr[kt], V, jb, nk, kq, tok);
         }
     }
     const float lse = m + logf(l), linv = 1.f / l;
     float lse_r[4], linv_r[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) { lse_r[r] = __shfl(lse, 4 * kq + r); linv_r[r] = __shfl(linv, 4 * kq + r); }
-    const int64_t row0 = group_row0(p, f);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int qi = i0 + 4 * kq + r;
-        if (qi >= T) continue;                                         // (uniform over each 16-lane row group)
+        if (qi >= nq) continue;                                        // (uniform over each 16-lane row group)
         float on_[NS], vn[NS], dot = 0.f;
-        const float vinv = t.vinv[sb + qi];
+        const float vinv = GEO == GEO_CROSS ? 0.f : t.vinv[sbk + qi];   // (belief: the query's own value row; the cross geometry has neither)
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             on_[s] = o[s][r] * linv_r[r];
-            t.o[pb + (int64_t)qi * DH + 16 * s + tok] = on_[s];
-            vn[s] = V[(int64_t)qi * DH + 16 * s + tok] * vinv;
+            t.o[pbq + (int64_t)qi * DH + 16 * s + tok] = on_[s];
+            vn[s] = GEO == GEO_CROSS ? 0.f : V[(int64_t)qi * DH + 16 * s + tok] * vinv;
             dot = __builtin_fmaf(on_[s], vn[s], dot);
         }
-        dot = p.belief ? row_sum16(dot) : 0.f;
-        if (tok == 0) t.lse[sb + qi] = lse_r[r];
-        const float gt = t.gt[sb + qi];
-        float* orow = p.o3 + (row0 + qi * p.item_stride) * hd + h * DH;
+        dot = (GEO != GEO_CROSS && p.belief) ? row_sum16(dot) : 0.f;
+        if (tok == 0) t.lse[sbq + qi] = lse_r[r];
+        const float gt = t.gt[sbq + qi];
+        float* orow = p.o3 + row_of(p.qm, f, qi) * hd + h * DH;
 #pragma unroll
         for (int s = 0; s < NS; ++s) orow[16 * s + tok] = (on_[s] - dot * vn[s]) * gt;
     }
 }
 
-// ---- gate and belief backward per row: grid (F * heads, ceil(T / 4)), one wave per row, lane = feature
-template <int DH>
-__global__ __launch_bounds__(256) void tiled_dprep_kernel(AttnBwdArgs p, TiledPlanes t) {
-    const int T = p.S, hd = p.heads * DH;
+// ---- gate and belief backward per query row: grid (G * heads, ceil(nq / 4)), one wave per row, lane = feature
+template <int DH, int GEO>
+__global__ __launch_bounds__(256) void tiled_dprep_kernel(TiledArgs p, TiledPlanes t) {
+    const int nq = p.nq, hd = p.heads * DH;
     const int gh = blockIdx.x, f = gh / p.heads, h = gh % p.heads;
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (i >= T) return;
+    if (i >= nq) return;
     const bool on = lane < DH;
-    const int64_t row = group_row0(p, f) + i * p.item_stride;
-    const int64_t si = (int64_t)gh * T + i;
+    const bool belief = GEO != GEO_CROSS && p.belief;
+    const int64_t row = row_of(p.qm, f, i);
+    const int64_t si = (int64_t)gh * nq + i;
     const float o = on ? t.o[si * DH + lane] : 0.f;
-    const float vinv = t.vinv[si], gt = t.gt[si];
-    const float vni = (on ? t.vm[si * DH + lane] : 0.f) * vinv;
-    const float sdot = p.belief ? wave_sum(o * vni) : 0.f;
+    const float vinv = GEO == GEO_CROSS ? 0.f : t.vinv[si], gt = t.gt[si];
+    const float vni = (GEO != GEO_CROSS && on ? t.vm[si * DH + lane] : 0.f) * vinv;
+    const float sdot = belief ? wave_sum(o * vni) : 0.f;
     const float o2 = o - sdot * vni;
     const float d3 = on ? p.d_o3[row * hd + h * DH + lane] : 0.f;
     const float dgl = wave_sum(d3 * o2) * gt * (1.f - gt);
-    if (lane == 0) p.dproj[row * p.ldp + 3 * hd + h] = dgl;
+    if (lane == 0) p.dprojq[row * p.ldq + p.gcol + h] = dgl;
     const float d2 = d3 * gt;
     float dOi = d2, dvdir = 0.f;
-    if (p.belief) {
+    if (belief) {
         const float c2 = wave_sum(d2 * vni);
         dOi = d2 - c2 * vni;
         const float dvn = -(sdot * d2 + c2 * o);
         dvdir = (dvn - wave_sum(dvn * vni) * vni) * vinv;
     }
     const float delta = wave_sum(dOi * o);                             // the softmax backward's row term: sum_j P_ij (dO_i . v_j) = dO_i . o_i
-    if (on) { t.dO[si * DH + lane] = dOi; t.dvd[si * DH + lane] = dvdir; }
+    if (on) { t.dO[si * DH + lane] = dOi; if (GEO != GEO_CROSS) t.dvd[si * DH + lane] = dvdir; }
     if (lane == 0) t.delta[si] = delta;
 }
 
@@ -268,30 +340,30 @@ __device__ __forceinline__ void p_and_ds(float dotqk, float dp, float lse, float
     ds *= scale;
 }
 
-// ---- dQ: grid (F * heads, ceil(T / 64)); wave w owns queries 64 blockIdx.y + 16 w .. + 15 and walks the key tiles <= its own
-template <int DH>
-__global__ __launch_bounds__(256) void tiled_dq_kernel(AttnBwdArgs p, TiledPlanes t) {
+// ---- dQ: grid (G * heads, ceil(nq / 64)); wave w owns queries 64 blockIdx.y + 16 w .. + 15 and walks the key tiles up to the last it sees
+template <int DH, int GEO>
+__global__ __launch_bounds__(256) void tiled_dq_kernel(TiledArgs p, TiledPlanes t) {
     constexpr int NS = DH / 16;
-    const int T = p.S;
+    const int nq = p.nq, nk = p.nk, fs = nk - p.num_special;
     const int gh = blockIdx.x;
     const int lane = threadIdx.x & 63, tok = lane & 15, kq = lane >> 4;
     const int i0 = blockIdx.y * 64 + (threadIdx.x >> 6) * 16;
-    if (i0 >= T) return;
-    const int64_t pb = (int64_t)gh * T * DH, sb = (int64_t)gh * T;
-    const float *Q = t.qr + pb, *K = t.kn + pb, *V = t.vm + pb, *DO = t.dO + pb;
+    if (i0 >= nq) return;
+    const int64_t pbq = (int64_t)gh * nq * DH, sbq = (int64_t)gh * nq, pbk = (int64_t)gh * nk * DH;
+    const float *Q = t.qr + pbq, *K = t.kn + pbk, *V = t.vm + pbk, *DO = t.dO + pbq;
     const float scale = rsqrtf((float)DH);
     const int i = i0 + tok;
-    const int jmax = (i0 + 15 < T - 1) ? i0 + 15 : T - 1;
+    const int jmax = last_key<GEO>(i0, nk, fs);
     f32x4 q4[NS], do4[NS], dq[NS];
-    load_rows<NS>(q4, Q, i, T, kq);
-    load_rows<NS>(do4, DO, i, T, kq);
+    load_rows<NS>(q4, Q, i, nq, kq);
+    load_rows<NS>(do4, DO, i, nq, kq);
 #pragma unroll
     for (int s = 0; s < NS; ++s) dq[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float lse = i < T ? t.lse[sb + i] : 0.f, delta = i < T ? t.delta[sb + i] : 0.f;
+    const float lse = i < nq ? t.lse[sbq + i] : 0.f, delta = i < nq ? t.delta[sbq + i] : 0.f;
     for (int jb = 0; jb <= jmax; jb += 16) {
         f32x4 k4[NS], v4[NS];
-        load_rows<NS>(k4, K, jb + tok, T, kq);
-        load_rows<NS>(v4, V, jb + tok, T, kq);
+        load_rows<NS>(k4, K, jb + tok, nk, kq);
+        load_rows<NS>(v4, V, jb + tok, nk, kq);
         const f32x4 st = dot_tile<NS>(k4, q4);                         // st[r] = q_i . k_j, j = jb + 4 kq + r
         const f32x4 dpt = dot_tile<NS>(v4, do4);                       // dO_i . v_j
         f32x4 ds;
@@ -299,145 +371,175 @@ __global__ __launch_bounds__(256) void tiled_dq_kernel(AttnBwdArgs p, TiledPlane
         for (int r = 0; r < 4; ++r) {
             const int j = jb + 4 * kq + r;
             float pij, d;
-            p_and_ds(st[r], dpt[r], lse, delta, j <= i && j < T && i < T, scale, p.softclamp, pij, d);
+            p_and_ds(st[r], dpt[r], lse, delta, sees<GEO>(i, j, nk, fs) && i < nq, scale, p.softclamp, pij, d);
             ds[r] = d;
         }
-        acc_rows<NS>(dq, ds, K, jb, T, kq, tok);                       // dq_i += sum_j dS_ij k_j
+        acc_rows<NS>(dq, ds, K, jb, nk, kq, tok);                      // dq_i += sum_j dS_ij k_j
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int qi = i0 + 4 * kq + r;
-        if (qi >= T) continue;
+        if (qi >= nq) continue;
 #pragma unroll
-        for (int s = 0; s < NS; ++s) t.dq[pb + (int64_t)qi * DH + 16 * s + tok] = dq[s][r];
+        for (int s = 0; s < NS; ++s) t.dq[pbq + (int64_t)qi * DH + 16 * s + tok] = dq[s][r];
     }
 }
 
-// ---- dK / dV: grid (F * heads, ceil(T / 64)); wave w owns keys 64 blockIdx.y + 16 w .. + 15 and walks the query tiles >= its own
-template <int DH>
-__global__ __launch_bounds__(256) void tiled_dkv_kernel(AttnBwdArgs p, TiledPlanes t) {
+// ---- dK / dV: grid (G * heads, ceil(nk / 64)); wave w owns keys 64 blockIdx.y + 16 w .. + 15 and walks the query tiles from the first that sees one
+template <int DH, int GEO>
+__global__ __launch_bounds__(256) void tiled_dkv_kernel(TiledArgs p, TiledPlanes t) {
     constexpr int NS = DH / 16;
-    const int T = p.S;
+    const int nq = p.nq, nk = p.nk, fs = nk - p.num_special;
     const int gh = blockIdx.x;
     const int lane = threadIdx.x & 63, tok = lane & 15, kq = lane >> 4;
     const int j0 = blockIdx.y * 64 + (threadIdx.x >> 6) * 16;
-    if (j0 >= T) return;
-    const int64_t pb = (int64_t)gh * T * DH, sb = (int64_t)gh * T;
-    const float *Q = t.qr + pb, *K = t.kn + pb, *V = t.vm + pb, *DO = t.dO + pb;
+    if (j0 >= nk) return;
+    const int64_t pbq = (int64_t)gh * nq * DH, sbq = (int64_t)gh * nq, pbk = (int64_t)gh * nk * DH;
+    const float *Q = t.qr + pbq, *K = t.kn + pbk, *V = t.vm + pbk, *DO = t.dO + pbq;
     const float scale = rsqrtf((float)DH);
     const int j = j0 + tok;
     f32x4 k4[NS], v4[NS], dk[NS], dv[NS];
-    load_rows<NS>(k4, K, j, T, kq);
-    load_rows<NS>(v4, V, j, T, kq);
+    load_rows<NS>(k4, K, j, nk, kq);
+    load_rows<NS>(v4, V, j, nk, kq);
 #pragma unroll
     for (int s = 0; s < NS; ++s) { dk[s] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[s] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    for (int ib = j0; ib < T; ib += 16) {
+    for (int ib = first_query<GEO>(j0, fs); ib < nq; ib += 16) {
         f32x4 q4[NS], do4[NS];
-        load_rows<NS>(q4, Q, ib + tok, T, kq);
-        load_rows<NS>(do4, DO, ib + tok, T, kq);
+        load_rows<NS>(q4, Q, ib + tok, nq, kq);
+        load_rows<NS>(do4, DO, ib + tok, nq, kq);
         const f32x4 st = dot_tile<NS>(q4, k4);                         // st[r] = q_i . k_j, i = ib + 4 kq + r
         const f32x4 dpt = dot_tile<NS>(do4, v4);
         f32x4 pt, ds;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = ib + 4 * kq + r;
-            const bool in = i < T;
-            const float lse = in ? t.lse[sb + i] : 0.f, delta = in ? t.delta[sb + i] : 0.f;
+            const bool in = i < nq;
+            const float lse = in ? t.lse[sbq + i] : 0.f, delta = in ? t.delta[sbq + i] : 0.f;
             float pij, d;
-            p_and_ds(st[r], dpt[r], lse, delta, in && j <= i && j < T, scale, p.softclamp, pij, d);
+            p_and_ds(st[r], dpt[r], lse, delta, in && sees<GEO>(i, j, nk, fs), scale, p.softclamp, pij, d);
             pt[r] = pij; ds[r] = d;
         }
-        acc_rows<NS>(dv, pt, DO, ib, T, kq, tok);                      // dv_j += sum_i P_ij dO_i
-        acc_rows<NS>(dk, ds, Q, ib, T, kq, tok);                       // dk_j += sum_i dS_ij q_i
+        acc_rows<NS>(dv, pt, DO, ib, nq, kq, tok);                     // dv_j += sum_i P_ij dO_i
+        acc_rows<NS>(dk, ds, Q, ib, nq, kq, tok);                      // dk_j += sum_i dS_ij q_i
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int kj = j0 + 4 * kq + r;
-        if (kj >= T) continue;
+        if (kj >= nk) continue;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            t.dkn[pb + (int64_t)kj * DH + 16 * s + tok] = dk[s][r];
-            t.dv[pb + (int64_t)kj * DH + 16 * s + tok] = dv[s][r];
+            t.dkn[pbk + (int64_t)kj * DH + 16 * s + tok] = dk[s][r];
+            t.dv[pbk + (int64_t)kj * DH + 16 * s + tok] = dv[s][r];
         }
     }
 }
 
 // ---- post-pass: one block per (group, head), wave w takes rows w, w + 4, ...; lane = feature
-template <int DH>
-__global__ __launch_bounds__(256) void tiled_post_kernel(AttnBwdArgs p, TiledPlanes t) {
+template <int DH, int GEO>
+__global__ __launch_bounds__(256) void tiled_post_kernel(TiledArgs p, TiledPlanes t) {
     __shared__ float gpart[4][64];
-    const int T = p.S, hd = p.heads * DH;
+    const int nq = p.nq, nk = p.nk, hd = p.heads * DH;
     const int gh = blockIdx.x, f = gh / p.heads, h = gh % p.heads;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const bool on = lane < DH;
-    const int64_t row0 = group_row0(p, f);
     const float sc = on ? (p.gamma[h * DH + lane] + 1.f) * sqrtf((float)DH) : 0.f;
-    const float freq = on ? p.inv_freq[lane & (DH / 2 - 1)] : 0.f;
+    const float freq = (GEO == GEO_TIME && on) ? p.inv_freq[lane & (DH / 2 - 1)] : 0.f;
     float gacc = 0.f;
-    for (int j = w; j < T; j += 4) {
-        const int64_t sj = (int64_t)gh * T + j, row = row0 + j * p.item_stride;
-        float* dr = p.dproj + row * p.ldp;
-        const float dq = rot_bwd<DH>(on ? t.dq[sj * DH + lane] : 0.f, j, freq, lane, on);
-        if (on) dr[h * DH + lane] = dq;
-        const float dkn = rot_bwd<DH>(on ? t.dkn[sj * DH + lane] : 0.f, j, freq, lane, on);
-        const float dv = on ? t.dvd[sj * DH + lane] + t.dv[sj * DH + lane] : 0.f;
+    for (int j = w; j < nk; j += 4) {
+        const int64_t sj = (int64_t)gh * nk + j, row = row_of(p.km, f, j);
+        float* dr = p.dprojk + row * p.ldk;
+        if (GEO != GEO_CROSS) {                                        // (query j is the same row)
+            const float dqp = on ? t.dq[sj * DH + lane] : 0.f;
+            const float dq = GEO == GEO_TIME ? rot_bwd<DH>(dqp, j, freq, lane, on) : dqp;
+            if (on) dr[h * DH + lane] = dq;
+        }
+        const float dknp = on ? t.dkn[sj * DH + lane] : 0.f;
+        const float dkn = GEO == GEO_TIME ? rot_bwd<DH>(dknp, j, freq, lane, on) : dknp;
         const float khj = on ? t.kh[sj * DH + lane] : 0.f;
         gacc += dkn * khj;
         const float dkh = dkn * sc;
         const float dk = (dkh - wave_sum(dkh * khj) * khj) * t.kinv[sj];
-        if (on) dr[hd + h * DH + lane] = dk;
+        if (on) dr[p.kcol + h * DH + lane] = dk;
+        if (GEO == GEO_CROSS) {
+            if (on) dr[p.vcol + h * DH + lane] = t.dv[sj * DH + lane];
+            continue;
+        }
+        const float dv = on ? t.dvd[sj * DH + lane] + t.dv[sj * DH + lane] : 0.f;
         if (p.rv) {
             const float mx = t.mx[sj];
-            const float* pr = p.proj + row * p.ldp;
+            const float* pr = p.projk + row * p.ldk;
             const float vraw = on ? pr[2 * hd + h * DH + lane] : 0.f;
             const float r = on ? p.rv[row * hd + h * DH + lane] : 0.f;
             const float dmx = wave_sum(dv * (r - vraw));
             if (on) { dr[2 * hd + h * DH + lane] = dv * (1.f - mx); p.d_rv[row * hd + h * DH + lane] = dv * mx; }
-            if (lane == 0) dr[3 * hd + p.hp4 + h] = dmx * mx * (1.f - mx);
+            if (lane == 0) dr[p.mcol + h] = dmx * mx * (1.f - mx);
         } else {
             if (on) dr[2 * hd + h * DH + lane] = dv;
-            if (lane == 0) dr[3 * hd + p.hp4 + h] = 0.f;
+            if (lane == 0) dr[p.mcol + h] = 0.f;
         }
     }
+    if (GEO == GEO_CROSS)
+        for (int i = w; i < nq; i += 4)
+            if (on) p.dprojq[row_of(p.qm, f, i) * p.ldq + h * DH + lane] = t.dq[((int64_t)gh * nq + i) * DH + lane];
     gpart[w][lane] = gacc;
     __syncthreads();
     if (w == 0 && on) p.dgamma_part[(int64_t)f * hd + h * DH + lane] = (((gpart[0][lane] + gpart[1][lane]) + gpart[2][lane]) + gpart[3][lane]) * sqrtf((float)DH);
 }
 
-template <int DH>
-int launch_tiled(const AttnBwdArgs& a, const TiledPlanes& t, hipStream_t s) {
-    const int T = a.S;
-    const dim3 block(256), rows(a.F * a.heads, (T + 3) / 4), tiles(a.F * a.heads, (T + 63) / 64);
-    hipLaunchKernelGGL(tiled_pre_kernel<DH>, rows, block, 0, s, a, t);
-    hipLaunchKernelGGL(tiled_fwd_kernel<DH>, tiles, block, 0, s, a, t);
+template <int DH, int GEO>
+int launch_tiled(const TiledArgs& a, const TiledPlanes& t, hipStream_t s) {
+    const int nmax = a.nq > a.nk ? a.nq : a.nk, gh = a.G * a.heads;
+    const dim3 block(256), rows(gh, (nmax + 3) / 4), qrows(gh, (a.nq + 3) / 4), qtiles(gh, (a.nq + 63) / 64), ktiles(gh, (a.nk + 63) / 64);
+    hipLaunchKernelGGL((tiled_pre_kernel<DH, GEO>), rows, block, 0, s, a, t);
+    hipLaunchKernelGGL((tiled_fwd_kernel<DH, GEO>), qtiles, block, 0, s, a, t);
     D4_LAUNCH_CHECK();
     if (!a.d_o3) return 0;
-    hipLaunchKernelGGL(tiled_dprep_kernel<DH>, rows, block, 0, s, a, t);
-    hipLaunchKernelGGL(tiled_dq_kernel<DH>, tiles, block, 0, s, a, t);
-    hipLaunchKernelGGL(tiled_dkv_kernel<DH>, tiles, block, 0, s, a, t);
-    hipLaunchKernelGGL(tiled_post_kernel<DH>, dim3(a.F * a.heads), block, 0, s, a, t);
+    hipLaunchKernelGGL((tiled_dprep_kernel<DH, GEO>), qrows, block, 0, s, a, t);
+    hipLaunchKernelGGL((tiled_dq_kernel<DH, GEO>), qtiles, block, 0, s, a, t);
+    hipLaunchKernelGGL((tiled_dkv_kernel<DH, GEO>), ktiles, block, 0, s, a, t);
+    hipLaunchKernelGGL((tiled_post_kernel<DH, GEO>), dim3(gh), block, 0, s, a, t);
     D4_LAUNCH_CHECK();
     return 0;
 }
 
-}  // namespace
-
-size_t attn_tiled_floats(int R, int heads, int dh) {
-    const size_t big = ((size_t)R * heads * dh + 63) / 64 * 64, small = ((size_t)R * heads + 63) / 64 * 64;
-    return TL_PLANES * big + TL_SCALARS * small;
+template <int GEO>
+int launch_dh(const TiledArgs& a, int dh, float* planes, hipStream_t s) {
+    D4_REQUIRE(planes, "tiled attention core: no planes");
+    D4_REQUIRE(a.nq >= 1 && a.nq <= ATT_MAX_FRAMES && a.nk >= 1 && a.nk <= ATT_MAX_FRAMES, "tiled attention core: %d queries / %d keys per problem (max %d)",
+               a.nq, a.nk, ATT_MAX_FRAMES);
+    D4_REQUIRE((int64_t)a.G * a.heads <= 0x7fffffff, "tiled attention core: grid too large");
+    if (a.G * a.heads == 0) return 0;
+    TiledPlanes t{};
+    carve(t, planes, (size_t)a.G * a.nq, (size_t)a.G * a.nk, a.heads, dh, GEO == GEO_CROSS);
+    if (dh == 64) return launch_tiled<64, GEO>(a, t, s);
+    if (dh == 32) return launch_tiled<32, GEO>(a, t, s);
+    D4_REQUIRE(dh == 16, "tiled attention core: head dim %d (16, 32 or 64)", dh);
+    return launch_tiled<16, GEO>(a, t, s);
 }
 
+}  // namespace
+
+size_t attn_tiled_floats(int R, int heads, int dh) { TiledPlanes t{}; return carve(t, nullptr, R, R, heads, dh, false); }
+size_t attn_tiled_cross_floats(int Rq, int Rk, int heads, int dh) { TiledPlanes t{}; return carve(t, nullptr, Rq, Rk, heads, dh, true); }
+
 int attn_tiled_core(const AttnBwdArgs& a, int dh, float* planes, hipStream_t s) {
-    D4_REQUIRE(a.causal && a.inv_freq && planes, "tiled attention core: time geometry (causal, rotary) and its planes only");
-    D4_REQUIRE(a.S >= 1 && a.S <= ATT_MAX_FRAMES, "tiled attention core: %d frames (max %d)", a.S, ATT_MAX_FRAMES);
-    D4_REQUIRE(a.num_special == 0, "tiled attention core: no special-token mask in the time geometry");
-    D4_REQUIRE((int64_t)a.F * a.heads <= 0x7fffffff, "tiled attention core: grid too large");
-    if (a.F * a.heads == 0) return 0;
-    const TiledPlanes t = carve(planes, a.F * a.S, a.heads, dh);
-    if (dh == 64) return launch_tiled<64>(a, t, s);
-    if (dh == 32) return launch_tiled<32>(a, t, s);
-    D4_REQUIRE(dh == 16, "tiled attention core: head dim %d (16, 32 or 64)", dh);
-    return launch_tiled<16>(a, t, s);
+    const bool time = a.causal && a.inv_freq;
+    D4_REQUIRE(time || (!a.causal && !a.inv_freq), "tiled attention core: the time geometry (causal, rotary) or the within-frame geometry (neither)");
+    D4_REQUIRE(a.S >= 1 && a.S <= ATT_MAX_FRAMES, "tiled attention core: %d items per group (max %d)", a.S, ATT_MAX_FRAMES);
+    D4_REQUIRE(time ? a.num_special == 0 : (a.num_special >= 0 && a.num_special <= a.S), "tiled attention core: %d special items of %d", a.num_special, a.S);
+    const int hd = a.heads * dh;
+    const RowMap rm{a.g_inner, a.g_outer_stride, a.item_stride};
+    const TiledArgs p{a.proj, a.ldp, a.proj, a.ldp, hd, 2 * hd, 3 * hd, 3 * hd + a.hp4, a.rv, a.gamma, a.d_o3, a.inv_freq,
+                      a.o3, a.dproj, a.dproj, a.d_rv, a.dgamma_part, a.F, a.S, a.S, a.heads, a.softclamp, a.num_special, a.belief, rm, rm};
+    return time ? launch_dh<GEO_TIME>(p, dh, planes, s) : launch_dh<GEO_FRAME>(p, dh, planes, s);
+}
+
+int attn_tiled_cross_core(const XAttnArgs& a, int dh, float* planes, hipStream_t s) {
+    const int hd = a.heads * dh;
+    const RowMap qm{1, a.nq, 1}, km = a.item_major ? RowMap{a.G > 0 ? a.G : 1, 0, a.G} : RowMap{1, a.nk, 1};
+    const TiledArgs p{a.projq, a.ldq, a.projk, a.ldk, 0, hd, hd, 0, nullptr, a.gamma, a.d_o3, nullptr,
+                      a.o3, a.dprojq, a.dprojk, nullptr, a.dgamma_part, a.G, a.nq, a.nk, a.heads, a.softclamp, 0, 0, qm, km};
+    return launch_dh<GEO_CROSS>(p, dh, planes, s);
 }
 
 }  // namespace d4

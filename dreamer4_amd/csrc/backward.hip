@@ -62,6 +62,11 @@ static int gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, 
 // out features >= 16 and in features >= 16 (so the forward / input-gradient product has N >= 16, K >= 16 and the weight-gradient product M >= 16,
 // N >= 16), any number of rows; the heads-wide gate and mix projections are separate fp32 products by construction.
 static std::atomic<int> g_train_arith{0};
+// d4_train_wide_set(1): the within-frame and cross attentions accept up to ATT_MAX_FRAMES items per side, and take the tiled core
+// (attn_tiled.hip) where a side has more than 64; at <= 64 items, and with the switch off, nothing changes (kernels, workspace sizes, refusals)
+static std::atomic<int> g_train_wide{0};
+static bool space_tiled(int tokens) { return g_space_attn_tiled != 0 || (g_train_wide.load() && tokens > 64); }
+static bool cross_tiled(int nq, int nk) { return g_cross_attn_tiled != 0 || (g_train_wide.load() && (nq > 64 || nk > 64)); }
 struct Bf16Ctx {
     uint16_t *a = nullptr, *b = nullptr, *w = nullptr; size_t act = 0, wgt = 0;      // images: two activation-sized, one weight-sized (elements)
     const float* a_src = nullptr; int a_ld = 0, a_rows = 0, a_cols = 0;               // what image `a` holds: a dY feeds two products of one call
@@ -397,7 +402,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnBwdArgs p) {
     if (w == 0 && on) p.dgamma_part[(int64_t)f * hd + h * DH + lane] = (((gpart[0][lane] + gpart[1][lane]) + gpart[2][lane]) + gpart[3][lane]) * sqrtf((float)DH);
 }
 
-// `tiled`: the per-row planes of the tiled core (attn_tiled.hip), given when the time geometry runs more than AB_S frames (or the test hook asks)
+// `tiled`: the per-row planes of the tiled core (attn_tiled.hip), given under the rule of attn_tiled(): the time geometry above AB_S frames, the
+// within-frame geometry above AB_S tokens with d4_train_wide_set(1), either at any size when its test hook asks
 static int attn_core(const AttnBwdArgs& a, int dh, hipStream_t s, float* tiled = nullptr) {
     if (a.F * a.heads == 0) return 0;
     if (tiled) return attn_tiled_core(a, dh, tiled, s);
@@ -425,17 +431,7 @@ static int attn_core(const AttnBwdArgs& a, int dh, hipStream_t s, float* tiled =
 // D4:2143-2177), the final special-token cross attention (D4:3227-3234) and the learned-query pools (D4:2179-2210).  No value residual,
 // no belief projection (the reference skips it when a context is given), optional soft clamp.  One block per (group, head); up to 64
 // queries and 64 keys in (dynamic) LDS.  projq rows: q @ 0, gate logit @ hd + head; projk rows: k @ 0, v @ hd.
-struct XAttnArgs {
-    const float* projq; int ldq;       // [G * nq][ldq], row g * nq + i
-    const float* projk; int ldk;       // key j of group g: row g * nk + j (group major) or j * G + g (item major: the stack of hiddens)
-    const float* gamma;
-    const float* d_o3;                 // [G * nq][hd] or null (forward only)
-    float* o3;                         // [G * nq][hd]
-    float* dprojq; float* dprojk;      // gradients, same layouts
-    float* dgamma_part;                // [G][hd]
-    int G, nq, nk, heads, item_major;
-    float softclamp;
-};
+// (XAttnArgs, the argument block of the core: attn_tiled.h)
 
 constexpr int XA_N = 64;
 template <int DH>
@@ -536,8 +532,10 @@ __global__ __launch_bounds__(256) void xattn_bwd_kernel(XAttnArgs p) {
     if (w == 0 && on) p.dgamma_part[(int64_t)g * hd + h * DH + lane] = (((gpart[lane] + gpart[64 + lane]) + gpart[128 + lane]) + gpart[192 + lane]) * sqrtf((float)DH);
 }
 
-static int xattn_core(const XAttnArgs& a, int dh, hipStream_t s) {
+// `tiled`: the planes of the tiled core, given when a side has more than XA_N items with d4_train_wide_set(1) (or the test hook asks)
+static int xattn_core(const XAttnArgs& a, int dh, hipStream_t s, float* tiled = nullptr) {
     if (a.G * a.heads == 0) return 0;
+    if (tiled) return attn_tiled_cross_core(a, dh, tiled, s);
     const size_t lds = sizeof(float) * ((size_t)(3 * a.nk + 4 * a.nq) * AB_LD + a.nk + a.nq + 256);
     static DeviceOnce attr_set;
     if (attr_set.need()) {
@@ -562,7 +560,7 @@ __global__ void zero_pad_cols_kernel(float* x, int rows, int ld, int c0, int c1)
 
 struct AttnWs {
     float *xn, *wcat, *bcat, *proj, *dproj, *d_o3, *o3, *dwcat, *tg, *dxn, *gpart, *part, *wt;
-    float* tiled;                    // per-row planes of the tiled time core, last, so that every other offset is the same with and without them
+    float* tiled;                    // per-row planes of the tiled core, last, so that every other offset is the same with and without them
     size_t total;
     int P, hp4;
 };
@@ -622,6 +620,7 @@ size_t d4_ff_bf16_scratch_bytes(int rows, int dim, int inner) { return ff_bf16_e
 int d4_train_scratch_bind(void* scratch, size_t bytes) { t_scratch.p = scratch; t_scratch.bytes = scratch ? bytes : 0; return 0; }
 int d4_train_arith_set(int arith) { return g_train_arith.exchange(arith ? 1 : 0); }
 int d4_train_arith_get(void) { return g_train_arith.load(); }
+int d4_train_wide_set(int on) { return g_train_wide.exchange(on ? 1 : 0); }
 
 int d4_ff_forward(const float* x, const float* norm_w, const float* w_in, const float* b_in, const float* w_out, const float* b_out,
                   int rows, int dim, int inner, float* y, float* workspace, size_t workspace_bytes, void* stream) {
@@ -690,7 +689,7 @@ int d4_ff_backward_saved(const float* x, const float* dy, const float* norm_w, c
 }
 
 size_t d4_attn_workspace_bytes(int frames, int tokens, int dim, int heads, int dim_head) {
-    return attn_ws(nullptr, frames * tokens, frames, dim, heads, dim_head).total * sizeof(float);
+    return attn_ws(nullptr, frames * tokens, frames, dim, heads, dim_head, space_tiled(tokens)).total * sizeof(float);
 }
 size_t d4_attn_bf16_scratch_bytes(int rows, int dim, int heads, int dim_head) { return attn_bf16_extra(rows, dim, heads * dim_head); }
 
@@ -703,12 +702,19 @@ struct AttnGeom {                  // how the rows of x group into attention pro
     int causal, num_special; const float* inv_freq;
 };
 
-// the time geometry (causal, rotary) takes the tiled core above AB_S frames, and at any length under the test hook
-bool attn_tiled(const AttnGeom& g) { return g.causal && g.inv_freq && (g.items > AB_S || g_time_attn_tiled != 0); }
+// the time geometry (causal, rotary) takes the tiled core above AB_S frames, and at any length under the test hook; the within-frame
+// geometry (neither) above AB_S tokens with d4_train_wide_set(1), and at any size under its own hook
+bool attn_tiled(const AttnGeom& g) {
+    if (g.causal && g.inv_freq) return g.items > AB_S || g_time_attn_tiled != 0;
+    return !g.causal && !g.inv_freq && space_tiled(g.items);
+}
 
 int attn_check(int rows, const AttnGeom& g, int dim, int heads, int dim_head, const float* workspace, size_t workspace_bytes) {
     if (g.causal && g.inv_freq) D4_REQUIRE(g.items >= 1 && g.items <= ATT_MAX_FRAMES, "time attention block: %d frames per trajectory (max %d)", g.items, ATT_MAX_FRAMES);
-    else D4_REQUIRE(g.items >= 1 && g.items <= AB_S, "attention block: %d items per group (max %d)", g.items, AB_S);
+    else {
+        const int cap = g_train_wide.load() ? ATT_MAX_FRAMES : AB_S;
+        D4_REQUIRE(g.items >= 1 && g.items <= cap, "attention block: %d items per group (max %d)", g.items, cap);
+    }
     D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "attention block: head dim %d (16, 32 or 64)", dim_head);
     D4_REQUIRE(dim % 4 == 0 && ((uintptr_t)workspace % 256) == 0, "attention block: dim must be a multiple of 4 and the workspace 256-byte aligned");
     D4_REQUIRE(workspace_bytes >= attn_ws(nullptr, rows, g.groups, dim, heads, dim_head, attn_tiled(g)).total * sizeof(float), "attention block: workspace too small");
@@ -795,9 +801,10 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
 
 struct XWs {
     float *qn, *cn, *wqg, *wkv, *projq, *projk, *dprojq, *dprojk, *d_o3, *o3, *dwqg, *dwkv, *tg, *dqn, *tgc, *dcn, *gpart, *part, *wt;
+    float* tiled;                    // planes of the tiled core, last, so that every other offset is the same with and without them
     size_t total; int Pq, Pk, hp4;
 };
-XWs x_ws(float* base, int Rq, int Rk, int G, int D, int Dc, int heads, int dh) {
+XWs x_ws(float* base, int Rq, int Rk, int G, int D, int Dc, int heads, int dh, bool tiled = false) {
     XWs w{};
     const int hd = heads * dh;
     w.hp4 = (heads + 3) / 4 * 4; w.Pq = hd + w.hp4; w.Pk = 2 * hd;
@@ -809,6 +816,7 @@ XWs x_ws(float* base, int Rq, int Rk, int G, int D, int Dc, int heads, int dh) {
     w.tg = take((size_t)Rq * D); w.dqn = take((size_t)Rq * D); w.tgc = take((size_t)Rk * Dc); w.dcn = take((size_t)Rk * Dc); w.gpart = take((size_t)G * hd);
     w.part = take(DW_PART_FLOATS);
     w.wt = take((size_t)(w.Pk > w.Pq ? w.Pk : w.Pq) * (D > Dc ? D : Dc));
+    if (tiled) w.tiled = take(attn_tiled_cross_floats(Rq, Rk, heads, dh));
     w.total = off;
     return w;
 }
@@ -842,10 +850,11 @@ size_t x_bf16_extra(int Rq, int Rk, int D, int Dc, int hd) {
 }
 
 int x_check(int G, int nq, int nk, int D, int Dc, int heads, int dh, const float* workspace, size_t workspace_bytes) {
-    D4_REQUIRE(nq >= 1 && nq <= XA_N && nk >= 1 && nk <= XA_N, "cross attention block: %d queries / %d keys per group (max %d)", nq, nk, XA_N);
+    const int cap = g_train_wide.load() ? ATT_MAX_FRAMES : XA_N;
+    D4_REQUIRE(nq >= 1 && nq <= cap && nk >= 1 && nk <= cap, "cross attention block: %d queries / %d keys per group (max %d)", nq, nk, cap);
     D4_REQUIRE(dh == 16 || dh == 32 || dh == 64, "cross attention block: head dim %d (16, 32 or 64)", dh);
     D4_REQUIRE(D % 4 == 0 && Dc % 4 == 0 && ((uintptr_t)workspace % 256) == 0, "cross attention block: dims must be multiples of 4 and the workspace 256-byte aligned");
-    D4_REQUIRE(workspace_bytes >= x_ws(nullptr, G * nq, G * nk, G, D, Dc, heads, dh).total * sizeof(float), "cross attention block: workspace too small");
+    D4_REQUIRE(workspace_bytes >= x_ws(nullptr, G * nq, G * nk, G, D, Dc, heads, dh, cross_tiled(nq, nk)).total * sizeof(float), "cross attention block: workspace too small");
     return 0;
 }
 
@@ -854,7 +863,7 @@ int x_check(int G, int nq, int nk, int D, int Dc, int heads, int dh, const float
 extern "C" {
 
 size_t d4_cross_attn_workspace_bytes(int groups, int nq, int nk, int dim, int dim_ctx, int heads, int dim_head) {
-    return x_ws(nullptr, groups * nq, groups * nk, groups, dim, dim_ctx, heads, dim_head).total * sizeof(float);
+    return x_ws(nullptr, groups * nq, groups * nk, groups, dim, dim_ctx, heads, dim_head, cross_tiled(nq, nk)).total * sizeof(float);
 }
 size_t d4_cross_attn_bf16_scratch_bytes(int groups, int nq, int nk, int dim, int dim_ctx, int heads, int dim_head) {
     return x_bf16_extra(groups * nq, groups * nk, dim, dim_ctx, heads * dim_head);
@@ -869,7 +878,7 @@ int d4_cross_attn_forward(const float* q_tokens, const float* ctx, const float* 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int Rq = groups * nq, Rk = groups * nk, hd = heads * dim_head;
     if (Rq == 0) return 0;
-    const XWs w = x_ws(workspace, Rq, Rk, groups, dim, dim_ctx, heads, dim_head);
+    const XWs w = x_ws(workspace, Rq, Rk, groups, dim, dim_ctx, heads, dim_head, cross_tiled(nq, nk));
     const XParams prm{norm_w, norm_ctx_w, wq, wk, wv, wo, w_gates, k_gamma};
     Bf16Scope bf;
     {
@@ -878,7 +887,7 @@ int d4_cross_attn_forward(const float* q_tokens, const float* ctx, const float* 
     }
     if ((rc = x_project(w, q_tokens, ctx, prm, Rq, Rk, dim, dim_ctx, heads, dim_head, s))) return rc;
     XAttnArgs a{w.projq, w.Pq, w.projk, w.Pk, k_gamma, nullptr, w.o3, nullptr, nullptr, nullptr, groups, nq, nk, heads, ctx_item_major, softclamp};
-    if ((rc = xattn_core(a, dim_head, s))) return rc;
+    if ((rc = xattn_core(a, dim_head, s, w.tiled))) return rc;
     return gemm_b(w.o3, hd, wo, hd, y, dim, nullptr, Rq, dim, hd, 0, s);
 }
 
@@ -895,7 +904,7 @@ static int cross_attn_backward_impl(const float* q_tokens, const float* ctx, con
     D4_REQUIRE(groups >= 1, "d4_cross_attn_backward: no groups");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int Rq = groups * nq, Rk = groups * nk, D = dim, Dc = dim_ctx, hd = heads * dim_head;
-    const XWs w = x_ws(workspace, Rq, Rk, groups, D, Dc, heads, dim_head);
+    const XWs w = x_ws(workspace, Rq, Rk, groups, D, Dc, heads, dim_head, cross_tiled(nq, nk));
     const XParams prm{norm_w, norm_ctx_w, wq, wk, wv, wo, w_gates, k_gamma};
     Bf16Scope bf;
     {
@@ -905,7 +914,7 @@ static int cross_attn_backward_impl(const float* q_tokens, const float* ctx, con
     if (!reuse && (rc = x_project(w, q_tokens, ctx, prm, Rq, Rk, D, Dc, heads, dim_head, s))) return rc;
     if ((rc = lin_dx(dy, D, wo, hd, w.d_o3, hd, Rq, hd, D, w.wt, s))) return rc;
     XAttnArgs a{w.projq, w.Pq, w.projk, w.Pk, k_gamma, w.d_o3, w.o3, w.dprojq, w.dprojk, w.gpart, groups, nq, nk, heads, ctx_item_major, softclamp};
-    if ((rc = xattn_core(a, dim_head, s))) return rc;
+    if ((rc = xattn_core(a, dim_head, s, w.tiled))) return rc;
     image_a_written(w.dprojq); image_a_written(w.dprojk);
     if (w.hp4 > heads) {
         hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)Rq * (w.hp4 - heads)), dim3(256), 0, s, w.dprojq, Rq, w.Pq, hd + heads, w.Pq);

@@ -1539,6 +1539,8 @@ int d4_debug_switch(const char* name, int value) {
     else if (name && !strcmp(name, "attn_out_cols")) sw = &d4::g_attn_out_cols;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
     else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
+    else if (name && !strcmp(name, "space_attn_tiled")) sw = &d4::g_space_attn_tiled;
+    else if (name && !strcmp(name, "cross_attn_tiled")) sw = &d4::g_cross_attn_tiled;
     if (!sw) return -1;
     const int old = *sw;
     *sw = value;

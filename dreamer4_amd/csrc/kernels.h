@@ -117,6 +117,8 @@ extern int g_time_attn_fused_append;     // attn.hip: 1 (default) the cached dec
 extern int g_pool_wide_keys;             // engine.hip: 1 (default) bf16 engine projects a hidden once for every later pool's keys; 0 one key projection per pool (test hook)
 extern int g_attn_out_cols;              // frame_fused.hip: 1 (default) attention inside the column-split output projection at <= 4 frames; 0 two launches (test hook)
 extern int g_time_attn_tiled;            // attn_tiled.hip: 0 (default) the tiled time-attention core of the training path runs above 64 frames only; 1 at any length (test hook)
+extern int g_space_attn_tiled;           // attn_tiled.hip: 1 the within-frame attention of the training path takes the tiled core at any size (test hook; default 0: above 64 tokens with d4_train_wide_set(1))
+extern int g_cross_attn_tiled;           // attn_tiled.hip: the same for the cross attentions
 int gemm_force_config(int id);                             // test hook; returns the number of configurations
 const char* gemm_profile_class_name(int c);
 

@@ -70,28 +70,37 @@ class _arith_mode:
     """The block arithmetic of libd4hip is process-wide: every forward / backward call of a block sets its own immediately before the C call
     (autograd runs the backward on another thread, and a saved workspace must meet the arithmetic it was written in) and puts the previous
     one back.  In bf16 mode the call also gets a scratch for its bf16 operand images (`scratch_bytes`), bound to this thread for the call and
-    released with it: nothing of it is kept between the forward and the backward."""
-    def __init__(self, lib, a, scratch_bytes=0, device=None):
-        self.lib, self.a = lib, a
+    released with it: nothing of it is kept between the forward and the backward.
+    `wide` (None: leave it alone) is the other process-wide switch, d4_train_wide_set, handled the same way for the same reason: the
+    workspace size query, the forward and the backward of a space / cross block must all meet the setting the block was called with."""
+    def __init__(self, lib, a, scratch_bytes=0, device=None, wide=None):
+        self.lib, self.a, self.wide = lib, a, wide
         self.scratch = _workspace(scratch_bytes, device) if a else None
 
     def __enter__(self):
         self.prev = self.lib.d4_train_arith_set(self.a)
+        if self.wide is not None:
+            self.prev_wide = self.lib.d4_train_wide_set(self.wide)
         if self.scratch is not None:
             self.lib.d4_train_scratch_bind(self.scratch[1], self.scratch[0].numel() - 256)
 
     def __exit__(self, *exc):
         if self.scratch is not None:
             self.lib.d4_train_scratch_bind(None, 0)
+        if self.wide is not None:
+            self.lib.d4_train_wide_set(self.prev_wide)
         self.lib.d4_train_arith_set(self.prev)
         return False
 
 
-def _no_dispatcher(arith):
+def _no_dispatcher(arith, wide=False):
     if arith != 'fp32':
         arith_id(arith)
         raise NotImplementedError(f"D4_TRUNK_DISPATCHER=1 does not carry arith={arith!r}: the torch.ops.d4hip block registrations are fp32 only "
                                   "(run the bf16 training arithmetic on the default autograd.Function route)")
+    if wide:
+        raise NotImplementedError("D4_TRUNK_DISPATCHER=1 does not carry wide=True: the torch.ops.d4hip block registrations stop at 64 items per "
+                                  "group (run wide frames on the default autograd.Function route)")
 
 
 def _workspace(nbytes, device):
@@ -141,7 +150,7 @@ class _FeedForward(torch.autograd.Function):
 
 class _SpaceAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, softclamp, num_special, belief, arith=0):
+    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, softclamp, num_special, belief, arith=0, wide=0):
         x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma = _prep(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma)
         assert x.ndim == 3, 'x must be (frames, tokens, dim)'
         F_, S, D = x.shape
@@ -149,14 +158,14 @@ class _SpaceAttention(torch.autograd.Function):
         assert wq.shape == (heads * dh, D) and wo.shape == (D, heads * dh) and wg.shape == (heads, D)
         assert rv is None or rv.shape == (F_, S, heads, dh)
         lib = _lib.load()
-        nbytes = lib.d4_attn_workspace_bytes(F_, S, D, heads, dh)
-        ws, wp = _workspace(nbytes, x.device)
         y = torch.empty_like(x)
-        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if arith else 0, x.device):
+        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if arith else 0, x.device, wide):
+            nbytes = lib.d4_attn_workspace_bytes(F_, S, D, heads, dh)
+            ws, wp = _workspace(nbytes, x.device)
             _lib.check(lib.d4_space_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
                                                  _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh,
                                                  float(softclamp or 0.), int(num_special), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
-        ctx.arith = arith
+        ctx.arith, ctx.wide = arith, wide
         ctx.save_for_backward(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma)
         ctx.cfg = (float(softclamp or 0.), int(num_special), int(bool(belief)))
         ctx.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx.needs_input_grad) else None
@@ -169,21 +178,21 @@ class _SpaceAttention(torch.autograd.Function):
         F_, S, D = x.shape
         heads, dh = gamma.shape
         lib = _lib.load()
-        if ctx.fwd_ws is not None:
-            (ws, wp, nbytes), fn = ctx.fwd_ws, lib.d4_space_attn_backward_saved
-        else:
-            nbytes = lib.d4_attn_workspace_bytes(F_, S, D, heads, dh)
-            (ws, wp), fn = _workspace(nbytes, x.device), lib.d4_space_attn_backward
         e = torch.empty_like
         dx, dn, dq, dk, dv, do, dg, dgam = e(x), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         drv, dwm, dbm = (e(rv), e(wm), e(bm)) if rv is not None else (None, None, None)
-        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if ctx.arith else 0, x.device):
+        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if ctx.arith else 0, x.device, ctx.wide):
+            if ctx.fwd_ws is not None:
+                (ws, wp, nbytes), fn = ctx.fwd_ws, lib.d4_space_attn_backward_saved
+            else:
+                nbytes = lib.d4_attn_workspace_bytes(F_, S, D, heads, dh)
+                (ws, wp), fn = _workspace(nbytes, x.device), lib.d4_space_attn_backward
             _lib.check(fn(
                 _lib.ptr(x), _lib.ptr(rv), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg),
                 _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh, *ctx.cfg,
                 _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
                 _lib.ptr(dgam), wp, nbytes, _stream(x)))
-        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None
+        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None, None
 
 
 class _TimeAttention(torch.autograd.Function):
@@ -235,7 +244,7 @@ class _TimeAttention(torch.autograd.Function):
 
 class _CrossAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx_, q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma, item_major, softclamp, arith=0):
+    def forward(ctx_, q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma, item_major, softclamp, arith=0, wide=0):
         q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma = _prep(q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma)
         assert q_tokens.ndim == 3 and context.ndim == 3
         G, nq, D = q_tokens.shape
@@ -244,14 +253,14 @@ class _CrossAttention(torch.autograd.Function):
         heads, dh = gamma.shape
         assert wq.shape == (heads * dh, D) and wk.shape == (heads * dh, Dc) and wv.shape == (heads * dh, Dc) and wo.shape == (D, heads * dh)
         lib = _lib.load()
-        nbytes = lib.d4_cross_attn_workspace_bytes(G, nq, nk, D, Dc, heads, dh)
-        ws, wp = _workspace(nbytes, q_tokens.device)
         y = torch.empty_like(q_tokens)
-        with _arith_mode(lib, arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if arith else 0, q_tokens.device):
+        with _arith_mode(lib, arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if arith else 0, q_tokens.device, wide):
+            nbytes = lib.d4_cross_attn_workspace_bytes(G, nq, nk, D, Dc, heads, dh)
+            ws, wp = _workspace(nbytes, q_tokens.device)
             _lib.check(lib.d4_cross_attn_forward(_lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk),
                                                  _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, int(bool(item_major)), D, Dc, heads, dh,
                                                  float(softclamp or 0.), _lib.ptr(y), wp, nbytes, _stream(q_tokens)))
-        ctx_.arith = arith
+        ctx_.arith, ctx_.wide = arith, wide
         ctx_.save_for_backward(q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma)
         ctx_.cfg = (G, nq, nk, int(bool(item_major)), D, Dc, heads, dh, float(softclamp or 0.))
         ctx_.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx_.needs_input_grad) else None
@@ -263,21 +272,21 @@ class _CrossAttention(torch.autograd.Function):
         (dy,) = _prep(dy)
         G, nq, nk, item_major, D, Dc, heads, dh, softclamp = ctx_.cfg
         lib = _lib.load()
-        if ctx_.fwd_ws is not None:
-            (ws, wp, nbytes), fn = ctx_.fwd_ws, lib.d4_cross_attn_backward_saved
-        else:
-            nbytes = lib.d4_cross_attn_workspace_bytes(G, nq, nk, D, Dc, heads, dh)
-            (ws, wp), fn = _workspace(nbytes, q_tokens.device), lib.d4_cross_attn_backward
         e = torch.empty_like
         dq_t, dc, dn, dq, dk, dv, do, dg, dgam = e(q_tokens), e(context), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         dnc = e(norm_ctx_w) if norm_ctx_w is not None else None
-        with _arith_mode(lib, ctx_.arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if ctx_.arith else 0, q_tokens.device):
+        with _arith_mode(lib, ctx_.arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if ctx_.arith else 0, q_tokens.device, ctx_.wide):
+            if ctx_.fwd_ws is not None:
+                (ws, wp, nbytes), fn = ctx_.fwd_ws, lib.d4_cross_attn_backward_saved
+            else:
+                nbytes = lib.d4_cross_attn_workspace_bytes(G, nq, nk, D, Dc, heads, dh)
+                (ws, wp), fn = _workspace(nbytes, q_tokens.device), lib.d4_cross_attn_backward
             _lib.check(fn(
                 _lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv),
                 _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, item_major, D, Dc, heads, dh, softclamp,
                 _lib.ptr(dq_t), _lib.ptr(dc), _lib.ptr(dn), _lib.ptr(dnc), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dgam),
                 wp, nbytes, _stream(q_tokens)))
-        return dq_t, dc, dn, dnc, dq, dk, dv, do, dg, dgam, None, None, None
+        return dq_t, dc, dn, dnc, dq, dk, dv, do, dg, dgam, None, None, None, None
 
 
 def _dev(*ts):
@@ -297,16 +306,18 @@ def feedforward(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, p
 
 
 def space_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, *, residual_values=None, mix_weight=None, mix_bias=None,
-                    softclamp_value=50., num_special=1, belief=True, arith='fp32'):
+                    softclamp_value=50., num_special=1, belief=True, arith='fp32', wide=False):
     """Attention.forward (dreamer4.py:1968-2075), self attention within each frame: x (frames, tokens, dim) -> (frames, tokens, dim).
     `residual_values` (frames, tokens, heads, dim_head) with `mix_weight` / `mix_bias` = to_learned_value_residual_mix.0 (every layer
-    but the first); `num_special` trailing tokens are hidden from ordinary queries (dreamer4.py:1769-1783).  (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_space.)"""
+    but the first); `num_special` trailing tokens are hidden from ordinary queries (dreamer4.py:1769-1783).  tokens <= 64; with `wide=True`
+    <= 1024 (above 64 the tiled core of csrc/attn_tiled.hip; at <= 64 the same kernel and the same bits as without).
+    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_space, not with `wide`.)"""
     _dev(x)
     assert x.ndim == 3, 'x must be (frames, tokens, dim)'
     if not via_dispatcher():
         return _SpaceAttention.apply(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma,
-                                     softclamp_value, num_special, belief, arith_id(arith))
-    _no_dispatcher(arith)
+                                     softclamp_value, num_special, belief, arith_id(arith), int(bool(wide)))
+    _no_dispatcher(arith, wide)
     return torch.ops.d4hip.attn_block_space(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma,
                                             float(softclamp_value or 0.), int(num_special), bool(belief))[0]
 
@@ -327,16 +338,17 @@ def time_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, 
 
 
 def cross_attention(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, *,
-                    context_item_major=False, softclamp_value=None, arith='fp32'):
+                    context_item_major=False, softclamp_value=None, arith='fp32', wide=False):
     """Attention.forward with a context (dreamer4.py:1968-2075): q_tokens (groups, nq, dim); context (groups, nk, dim_ctx), or
-    (nk, groups, dim_ctx) with `context_item_major` (the stack of layer hiddens of the AttentionPool).  nq, nk <= 64.
-    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_cross.)"""
+    (nk, groups, dim_ctx) with `context_item_major` (the stack of layer hiddens of the AttentionPool).  nq, nk <= 64; with `wide=True`
+    nq, nk <= 1024 (the tiled core of csrc/attn_tiled.hip as soon as either exceeds 64; otherwise the same kernel and bits).
+    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_cross, not with `wide`.)"""
     _dev(q_tokens)
     assert q_tokens.ndim == 3 and context.ndim == 3
     if not via_dispatcher():
         return _CrossAttention.apply(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
-                                     context_item_major, softclamp_value, arith_id(arith))
-    _no_dispatcher(arith)
+                                     context_item_major, softclamp_value, arith_id(arith), int(bool(wide)))
+    _no_dispatcher(arith, wide)
     return torch.ops.d4hip.attn_block_cross(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
                                             bool(context_item_major), float(softclamp_value or 0.))[0]
 
@@ -358,7 +370,7 @@ def _ff(W, pre, x, arith='fp32'):
                        arith=arith)
 
 
-def _pool(W, pre, x, hiddens, arith='fp32'):
+def _pool(W, pre, x, hiddens, arith='fp32', wide=False):
     """Residual(AttentionPool) (dreamer4.py:2143-2177 + 1869): one query per token over the stack of layer hiddens.
     hiddens: a list of layer hiddens, or the stack itself (L, rows, D) — `transformer` grows ONE stack by concatenation, so that in the
     backward every pool's context gradient meets the previous pools' as one (L, rows, D) sum instead of L per-hidden sums per pool."""
@@ -366,16 +378,17 @@ def _pool(W, pre, x, hiddens, arith='fp32'):
     ctx = hiddens if torch.is_tensor(hiddens) else torch.stack([h.reshape(-1, shape[-1]) for h in hiddens], dim=0)     # (L, rows, D): item major
     p = pre + 'fn.attn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, p)
-    out = cross_attention(x.reshape(-1, 1, shape[-1]), ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, context_item_major=True, arith=arith)
+    out = cross_attention(x.reshape(-1, 1, shape[-1]), ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, context_item_major=True, arith=arith, wide=wide)
     return x + out.reshape(shape)
 
 
-def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='transformer.', arith='fp32'):
+def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='transformer.', arith='fp32', wide=False):
     """AxialSpaceTimeTransformer.forward (dreamer4.py:2927-3267, defaults: value residual, attention pools, final special cross
     attention; final RMSNorm when the weights hold one) for training: no KV cache, every block a HIP forward + backward operator;
     only the residual adds, reshapes and the two bare RMSNorm + Linear pieces (value residual projection, final norm) are torch ops.
     W: the reference's trunk parameters by state_dict key (with the prefix `pre`); tokens (batch, frames, tokens, dim); is_time: per
-    layer.  Differentiable with respect to tokens and every parameter."""
+    layer.  Differentiable with respect to tokens and every parameter.  `wide=True`: up to 1024 tokens per frame and pooled hiddens (space
+    blocks, attention pools and the final special cross attention take `wide`)."""
     from torch.nn import functional as F
     b, t, s, d = tokens.shape
     gamma0 = W[pre + 'layers.0.2.fn.k_heads_rmsnorm.gamma']
@@ -394,30 +407,30 @@ def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='
                                  mix_bias=mb, softclamp_value=softclamp_value, arith=arith)
         else:
             out = space_attention(tokens.reshape(b * t, s, d), nw, wq, wk, wv, wo, wg, gam, residual_values=vres.reshape(b * t, s, h, dh),
-                                  mix_weight=mw, mix_bias=mb, softclamp_value=softclamp_value, num_special=num_special, arith=arith).reshape(b, t, s, d)
+                                  mix_weight=mw, mix_bias=mb, softclamp_value=softclamp_value, num_special=num_special, arith=arith, wide=wide).reshape(b, t, s, d)
         tokens = tokens + out
         after_attn = tokens
         tokens = tokens + _ff(W, f'{pre}layers.{i}.3.fn.', tokens, arith)
         hiddens = torch.cat((hiddens, after_attn.reshape(1, -1, d), tokens.reshape(1, -1, d)), dim=0)
         if i != depth - 1:
-            tokens = _pool(W, f'{pre}attn_pools.{i}.', tokens, hiddens, arith)
+            tokens = _pool(W, f'{pre}attn_pools.{i}.', tokens, hiddens, arith, wide)
     # the special tokens cross-attend the ordinary tokens of their frame, then their own feedforward   dreamer4.py:3227-3238
     non_special, special = tokens[:, :, :-num_special], tokens[:, :, -num_special:]
     cp = pre + 'final_special_cross_attn.fn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, cp)
     out = cross_attention(special.reshape(b * t, num_special, d), non_special.reshape(b * t, s - num_special, d), nw, W[cp + 'norm_context.weight'],
-                          wq, wk, wv, wo, wg, gam, arith=arith)
+                          wq, wk, wv, wo, wg, gam, arith=arith, wide=wide)
     special = special + out.reshape(b, t, num_special, d)
     special = special + _ff(W, pre + 'final_special_ff.fn.', special, arith)
     tokens = torch.cat((non_special, special), dim=2)
-    tokens = _pool(W, pre + 'final_attn_pool.', tokens, hiddens, arith)
+    tokens = _pool(W, pre + 'final_attn_pool.', tokens, hiddens, arith, wide)
     if pre + 'final_norm.weight' in W:
         tokens = torch.ops.d4hip.rmsnorm(tokens, W[pre + 'final_norm.weight'], eps)
     return tokens
 
 
 # ------------------------------------------------------------------------------------------------ the dynamics model, training form
-def _lq_pool(W, pre, x, arith='fp32'):
+def _lq_pool(W, pre, x, arith='fp32', wide=False):
     """LearnedQueriesAttentionPool (dreamer4.py:2179-2210): x (..., n, d_ctx) -> (..., num_queries, dim)."""
     lead = x.shape[:-2]
     ctx = x.reshape(-1, *x.shape[-2:])
@@ -425,12 +438,13 @@ def _lq_pool(W, pre, x, arith='fp32'):
     q = queries[None].expand(ctx.shape[0], -1, -1)
     p = pre + 'attn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, p)
-    out = cross_attention(q, ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, arith=arith)
+    out = cross_attention(q, ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, arith=arith, wide=wide)
     return out.reshape(*lead, *out.shape[-2:])
 
 
 def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *, is_time, num_spatial_tokens, num_register_tokens,
-                           num_discrete_actions=(), discrete_actions=None, continuous_actions=None, tasks=None, softclamp_value=50., arith='fp32'):
+                           num_discrete_actions=(), discrete_actions=None, continuous_actions=None, tasks=None, softclamp_value=50., arith='fp32',
+                           wide=False):
     """DynamicsWorldModel's `get_prediction` (dreamer4.py:7156-7287) for training: noised latents (b, t, n, dl), signal_levels (b, t),
     step_sizes_log2 (b,) -> (latent prediction (b, t, n, dl), agent embedding (b, t, dim)).  Token packing, embeddings and the bare
     RMSNorm + Linear of the latent head are torch ops; the trunk and the learned-query pools are the HIP forward + backward blocks.
@@ -445,7 +459,7 @@ def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *,
     if num_spatial_tokens == n:
         space = torch.ops.d4hip.linear(noised_latents, W['latents_to_spatial_tokens.weight'], W['latents_to_spatial_tokens.bias'], None, 0, 0.)
     else:
-        space = _lq_pool(W, 'latents_to_spatial_tokens.', noised_latents, arith)
+        space = _lq_pool(W, 'latents_to_spatial_tokens.', noised_latents, arith, wide)
     sig = W['signal_levels_embed.weight'][signal_levels]
     stp = W['step_size_embed.weight'][step_sizes_log2][:, None].expand(b, t, -1)
     flow_tok = torch.cat((sig, stp), dim=-1)[:, :, None]
@@ -472,11 +486,11 @@ def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *,
             act = F.pad(emb, (0, 0, 1, 0), value=0.)
         parts.append(act[:, :, None])
     parts.append(agent)
-    tokens = transformer(W, torch.cat(parts, dim=2), is_time=is_time, softclamp_value=softclamp_value, arith=arith)
+    tokens = transformer(W, torch.cat(parts, dim=2), is_time=is_time, softclamp_value=softclamp_value, arith=arith, wide=wide)
     space_out, agent_embed = tokens[:, :, 1:1 + num_spatial_tokens], tokens[:, :, -1]
     x = torch.ops.d4hip.rmsnorm(space_out, W['to_latent_pred.0.weight'], eps)
     if num_spatial_tokens != n:
-        x = _lq_pool(W, 'to_latent_pred.1.', x, arith)
+        x = _lq_pool(W, 'to_latent_pred.1.', x, arith, wide)
     return torch.ops.d4hip.linear(x, W['to_latent_pred.2.weight'], None, None, 0, 0.), agent_embed
 
 
@@ -497,7 +511,8 @@ def _action_offsets(sizes, dev):
 def dynamics_flow_losses(W, latents, noise, signal_levels, step_sizes_log2, shortcut_train, *, max_steps, return_agent_embed=False, lens=None, **model):
     """The flow and shortcut-consistency losses of the dynamics training forward (dreamer4.py:6990-7003, 7335-7431; x-space prediction,
     ramp loss weight, no proprio / variable lengths / loss normalisers: the reference defaults).  `model`: the keyword arguments of
-    `world_model_prediction` (among them `arith='fp32' | 'bf16'`, the arithmetic of the blocks' Linears in all three predictions).  Returns (flow_loss, shortcut_loss[, agent_embed of the main prediction]); backward runs through the HIP blocks."""
+    `world_model_prediction` (among them `arith='fp32' | 'bf16'`, the arithmetic of the blocks' Linears in all three predictions, and `wide=True`
+    for more than 64 tokens per frame, latents or pooled hiddens).  Returns (flow_loss, shortcut_loss[, agent_embed of the main prediction]); backward runs through the HIP blocks."""
     from torch.nn import functional as F
     times = signal_levels.float() / max_steps
     tt = times[:, :, None, None]

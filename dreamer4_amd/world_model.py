@@ -174,6 +174,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         continuous_beta_param='softplus_p1',
         matmul_dtype='fp32',
         train_matmul_dtype='fp32',
+        train_wide_frames=False,
         use_loss_normalization=False,
         latent_flow_loss_weight=1.,
         shortcut_loss_weight=1.,
@@ -218,6 +219,12 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         if train_matmul_dtype not in ('fp32', 'bf16'):
             raise ValueError("train_matmul_dtype must be 'fp32' or 'bf16'")
         self.train_matmul_dtype = train_matmul_dtype
+        # (not a reference argument) wide frames in the TRAINING forward: False (default) a space block, a learned-query pool and
+        # an attention pool take at most 64 tokens per frame / latents / pooled hiddens (a larger model's training forward raises D4Error);
+        # True: up to 1024 of each, on the tiled attention core (csrc/attn_tiled.hip) wherever a problem side exceeds 64 — smaller problems
+        # run the same kernels with the same bits as with False.  Training only: the inference engine keeps its limit, so generate() / the
+        # inference forward() of such a model still fail at d4_engine_create ("tokens per frame / pooled hiddens exceed 64").
+        self.train_wide_frames = bool(train_wide_frames)
         self.use_loss_normalization = bool(use_loss_normalization)
         # loss weights of the training forward's total (dreamer4.py:4719-4725, 5257-5267, 7708-7723): two plain floats and four persistent
         # buffers of 1 or multi_token_pred_len elements — a checkpoint's values are loaded and used
@@ -812,7 +819,8 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             num_register_tokens=self.num_register_tokens, num_discrete_actions=tuple(self.num_discrete_actions),
             discrete_actions=discrete_actions.to(dev).long() if discrete_actions is not None else None,
             continuous_actions=continuous_actions.to(dev).float() if continuous_actions is not None else None,
-            tasks=tasks.to(dev).long() if tasks is not None else None, softclamp_value=self.attn_softclamp_value, arith=self.train_matmul_dtype)
+            tasks=tasks.to(dev).long() if tasks is not None else None, softclamp_value=self.attn_softclamp_value, arith=self.train_matmul_dtype,
+            wide=self.train_wide_frames)
         rew = rewards.to(dev).float() if rewards is not None else None
         if rew is not None and rew.shape[1] == T - 1:
             rew = torch.nn.functional.pad(rew, (1, 0), value=0.)                                           # dreamer4.py:6905-6907

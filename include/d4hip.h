@@ -275,7 +275,9 @@ int d4_frame_fused_set(int mode);
  * Read when a frame is ENQUEUED: a captured hipGraph keeps the form it was captured with.
  * "time_attn_tiled" (training time attention, csrc/attn_tiled.hip; NOT bit-identical: another summation order): 0 (default) the tiled core
  * runs above 64 frames only, 1 at any length, so that it can be checked at shapes the LDS core also handles.  Read by
- * d4_time_attn_workspace_bytes too: size the workspace with the value the calls will run under. */
+ * d4_time_attn_workspace_bytes too: size the workspace with the value the calls will run under.
+ * "space_attn_tiled" / "cross_attn_tiled" (training space / cross attention; NOT bit-identical either): 0 (default) the tiled core runs above
+ * 64 items per side with d4_train_wide_set(1) only, 1 at any size.  Read by d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes too. */
 int d4_debug_switch(const char* name, int value);
 int d4_gemm_force_config(int id);
 
@@ -379,6 +381,13 @@ size_t d4_ff_workspace_bytes(int rows, int dim, int inner);
  * training loop per process, with autograd's single backward thread, is the supported use. */
 int d4_train_arith_set(int arith);
 int d4_train_arith_get(void);
+/* Wide frames: 0 (default) the space and cross attention blocks take at most 64 items per group and side, as ever; 1 they take
+ * up to 1024, and above 64 items on a side run the tiled core of csrc/attn_tiled.hip (at <= 64 the same kernels and the same bits as with 0).
+ * d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes answer for the CURRENT setting (larger above 64 items with 1, unchanged otherwise),
+ * so a caller sets the switch around the size query and around EACH forward / backward call alike (a `*_backward_saved` call must meet the
+ * setting of its forward) and restores it after.  Process-wide like d4_train_arith_set; returns the previous value.  The inference engine is
+ * not concerned: d4_engine_create still refuses more than 64 tokens per frame / pooled hiddens. */
+int d4_train_wide_set(int on);
 int d4_train_scratch_bind(void* scratch, size_t bytes);
 size_t d4_ff_bf16_scratch_bytes(int rows, int dim, int inner);
 size_t d4_attn_bf16_scratch_bytes(int rows, int dim, int heads, int dim_head);
@@ -394,7 +403,7 @@ int d4_ff_backward_saved(const float* x, const float* dy, const float* norm_w, c
 /* Space attention block (Attention.forward, dreamer4.py:1968-2075, self attention within a frame): x / y [frames*tokens][dim],
  * residual_values [frames*tokens][heads*dim_head] or null (then w_mix / b_mix and their gradients are unused), wq / wk / wv
  * [heads*dim_head][dim], wo [dim][heads*dim_head], w_gates / w_mix [heads][dim], b_mix [heads], k_gamma [heads][dim_head];
- * tokens <= 64 per frame, dim_head 16 / 32 / 64; num_special trailing tokens are hidden from the ordinary queries (dreamer4.py:1769-1783). */
+ * tokens <= 64 per frame (<= 1024 with d4_train_wide_set(1)), dim_head 16 / 32 / 64; num_special trailing tokens are hidden from the ordinary queries (dreamer4.py:1769-1783). */
 size_t d4_attn_workspace_bytes(int frames, int tokens, int dim, int heads, int dim_head);
 int d4_space_attn_forward(const float* x, const float* residual_values, const float* norm_w, const float* wq, const float* wk, const float* wv,
                           const float* wo, const float* w_gates, const float* w_mix, const float* b_mix, const float* k_gamma,
@@ -438,7 +447,7 @@ int d4_time_attn_backward_saved(const float* x, const float* residual_values, co
 /* Cross-attention block (Attention.forward with a context: the AttentionPool over the layer hiddens dreamer4.py:2143-2177, the final
  * special-token cross attention :3227-3234, the learned-query pools :2179-2210): q_tokens [groups*nq][dim], ctx [groups*nk][dim_ctx] with key
  * j of group g at row g*nk + j, or at row j*groups + g when ctx_item_major (the stack of hiddens); norm_ctx_w may be null (context not
- * normalised); wk / wv [heads*dim_head][dim_ctx]; nq, nk <= 64.  No value residual and no belief projection (as the reference with a context). */
+ * normalised); wk / wv [heads*dim_head][dim_ctx]; nq, nk <= 64 (<= 1024 with d4_train_wide_set(1)).  No value residual and no belief projection (as the reference with a context). */
 size_t d4_cross_attn_workspace_bytes(int groups, int nq, int nk, int dim, int dim_ctx, int heads, int dim_head);
 int d4_cross_attn_forward(const float* q_tokens, const float* ctx, const float* norm_w, const float* norm_ctx_w, const float* wq, const float* wk,
                           const float* wv, const float* wo, const float* w_gates, const float* k_gamma, int groups, int nq, int nk, int ctx_item_major,
