@@ -39,6 +39,7 @@ class Config(C.Structure):
         ('decoder_flow_steps', C.c_int32), ('decoder_pos_mlp_depth', C.c_int32),
         ('max_batch', C.c_int32), ('max_frames', C.c_int32), ('max_parallel_frames', C.c_int32),
         ('max_learn_rows', C.c_int32),
+        ('wide_frames', C.c_int32),
     ]
 
 
@@ -152,6 +153,7 @@ SYMBOLS = {
     'd4_gemm_split2': (_I, [_P, _I, _P, _L, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
     'd4_rmsnorm': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P]),
     'd4_small_attn': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
+    'd4_small_attn_wide': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
     'd4_pool_mix': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'd4_time_attn_decode': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P] + [_I] * 8 + [_P, _F, _I, _I, _P]),
     'd4_debug_last_form': (C.c_char_p, [C.c_char_p]),

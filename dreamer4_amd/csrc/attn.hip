@@ -23,7 +23,7 @@ namespace d4 {
 
 // Which kernel form each launcher of this file picked last: a host-side record for the operator tests (d4_debug_last_form / d4_debug_forms in
 // engine.hip).  A plain store on the host; nothing on the device, no launch depends on it.
-enum { FAM_SMALL_ATTN, FAM_POOL_MIX, FAM_TIME_KV_APPEND, FAM_TIME_ATTN, FAM_N };
+enum { FAM_SMALL_ATTN, FAM_POOL_MIX, FAM_TIME_KV_APPEND, FAM_TIME_ATTN, FAM_WIDE_ATTN, FAM_N };
 static const char* const k_small_attn_forms[] = {
     "attn_mfma_kernel<1,1>", "attn_mfma_kernel<1,2>", "attn_mfma_kernel<1,4,2>", "attn_mfma_kernel<2,1>", "attn_mfma_kernel<4,1>",
     "space_attn_kernel<64>", "space_attn_kernel<32>", "space_attn_kernel<16>",
@@ -40,9 +40,10 @@ static const char* const k_time_attn_forms[] = {
     "time_attn64_few_kernel<8>", "time_attn64_few_kernel<16>", "time_attn64_few_kernel<8,append>", "time_attn64_few_kernel<16,append>",
     "time_attn64_kernel<false>", "time_attn64_kernel<false,append>", "time_attn64_kernel<true>",
     "time_attn_kernel<64>", "time_attn_kernel<32>", "time_attn_kernel<16>", nullptr};
-static const char* const k_family_names[FAM_N] = {"small_attn", "pool_mix", "time_kv_append", "time_attn"};
-static const char* const* const k_family_forms[FAM_N] = {k_small_attn_forms, k_pool_mix_forms, k_time_kv_append_forms, k_time_attn_forms};
-static const char* g_last_form[FAM_N] = {nullptr, nullptr, nullptr, nullptr};
+static const char* const k_wide_attn_forms[] = {"wide_attn_kernel<16>", "wide_attn_kernel<32>", "wide_attn_kernel<64>", nullptr};     // attn_wide_mfma.hip
+static const char* const k_family_names[FAM_N] = {"small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn"};
+static const char* const* const k_family_forms[FAM_N] = {k_small_attn_forms, k_pool_mix_forms, k_time_kv_append_forms, k_time_attn_forms, k_wide_attn_forms};
+static const char* g_last_form[FAM_N] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 static inline void note_form(int fam, const char* name) { g_last_form[fam] = name; }
 static int form_family(const char* family) {
     for (int f = 0; f < FAM_N; ++f) if (family && !strcmp(family, k_family_names[f])) return f;
@@ -487,6 +488,12 @@ int small_attn(const SmallAttnArgs& p, hipStream_t stream) {
         // only the kernels that write the bf16 copy themselves can run without the fp32 output
         D4_REQUIRE(false, "small_attn: out_b without out is not supported");
     }
+    if (p.wide && (g_small_attn_wide || p.nq > 64 || p.nk > 64)) {
+        // wide frames (SmallAttnArgs::wide): the tiled matrix-pipe core; it writes the fp32 output only
+        const char* form = nullptr;
+        if (int rc = wide_attn(p, stream, &form)) return rc;
+        if (form) note_form(FAM_WIDE_ATTN, form);
+    } else
     if (int rc = small_attn_impl(p, stream, &wrote_b)) return rc;
     if (!p.out_b || wrote_b || p.groups * p.heads == 0) return 0;
     const int nq_out = p.q_hi > 0 ? (p.q_hi - p.q_lo + p.q_last) : p.nq;

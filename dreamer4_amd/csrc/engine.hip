@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 
 using namespace d4;
 
@@ -795,6 +796,7 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
     sa.k_gamma = a.k_gamma;
     sa.out = e->pool_att; sa.o_group_stride = hp; sa.o_item_stride = 0;
     sa.groups = M; sa.heads = c.pool_heads; sa.nq = 1; sa.nk = L;
+    sa.wide = c.wide_frames;
     sa.out_b = t_bf16 ? t_bf16->shadow_of(e->pool_att) : nullptr;
     if ((rc = small_attn(sa, s))) return rc;
     }
@@ -877,6 +879,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->lq_in.k_gamma;
         sa.out = e->latt; sa.o_group_stride = (int64_t)ns * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = ns; sa.nk = n;
+        sa.wide = c.wide_frames;
         if ((rc = small_attn(sa, s))) return rc;
     }
     if ((rc = gemm_simple(e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0, s))) return rc;
@@ -932,6 +935,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             sa.k_gamma = a.k_gamma;
             sa.out = e->att; sa.o_group_stride = (int64_t)S * hd; sa.o_item_stride = hd;
             sa.groups = Fr; sa.heads = h; sa.nq = S; sa.nk = S;
+            sa.wide = c.wide_frames;
             sa.softclamp = c.attn_softclamp_value; sa.mask_special = e->encoder ? n : has_agent; sa.belief = 1;
             sa.out_b = t_bf16 ? t_bf16->shadow_of(e->att) : nullptr;
             if (denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8) {
@@ -992,6 +996,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->cross.k_gamma;
         sa.out = e->catt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = P;
+        sa.wide = c.wide_frames;
         if ((rc = small_attn(sa, s))) return rc;
         if ((rc = gemm_simple(e->catt, hd, e->cross.to_out, hd, xfc, D, Mc, D, hd, 0, nullptr, spec, D, s))) return rc;
         if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, xfc, D, xfc, D, Mc, s))) return rc;
@@ -1024,6 +1029,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->cross.k_gamma;
         sa.out = e->catt; sa.o_group_stride = hd; sa.o_item_stride = 0;
         sa.groups = Fr; sa.heads = h; sa.nq = 1; sa.nk = S - 1;
+        sa.wide = c.wide_frames;
         if ((rc = small_attn(sa, s))) return rc;
         if ((rc = gemm_simple(e->catt, hd, e->cross.to_out, hd, agent_rows, ldc, Fr, D, hd, 0, nullptr, agent_in, lda, s))) return rc;
         if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, agent_rows, ldc, agent_rows, ldc, Fr, s))) return rc;
@@ -1049,6 +1055,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->lq_out.k_gamma;
         sa.out = e->oatt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = ns;
+        sa.wide = c.wide_frames;
         if ((rc = small_attn(sa, s))) return rc;
     }
     if ((rc = gemm_simple(e->oatt, hd, e->lout_w, hd, e->pred, dl, Fr * n, dl, hd, 0, nullptr, nullptr, 0, s))) return rc;
@@ -1133,7 +1140,12 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
     const bool encoder = c.mode == D4_MODE_ENCODER;
     const bool decoder = c.mode == D4_MODE_DECODER || encoder;          // (shared geometry checks below; e->decoder is set for the decoder only)
     D4_REQUIRE(c.mode == D4_MODE_DYNAMICS || decoder, "unknown engine mode %d", c.mode);
-    D4_REQUIRE(c.num_latent_tokens <= 64 && (decoder || c.num_spatial_tokens <= 64), "at most 64 latent / spatial tokens");
+    const bool wide = c.wide_frames != 0;                                // wide frames: the limits below rise to WIDE_ATTN_MAX (the wide attention core's cap)
+    if (wide) {
+        D4_REQUIRE(c.num_latent_tokens <= d4::WIDE_ATTN_MAX && (decoder || c.num_spatial_tokens <= d4::WIDE_ATTN_MAX), "wide frames: at most %d latent / spatial tokens", d4::WIDE_ATTN_MAX);
+    } else {
+        D4_REQUIRE(c.num_latent_tokens <= 64 && (decoder || c.num_spatial_tokens <= 64), "at most 64 latent / spatial tokens");
+    }
     if (decoder) {
         D4_REQUIRE(c.attn_dim_head == 64, "decoder mode: attn_dim_head must be 64 (the wide attention kernel)");
         D4_REQUIRE(c.patch_size >= 1 && c.channels >= 1 && c.image_height % c.patch_size == 0 && c.image_width % c.patch_size == 0 && c.image_height > 0 && c.image_width > 0,
@@ -1145,7 +1157,8 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
     }
     D4_REQUIRE((c.max_steps & (c.max_steps - 1)) == 0, "max_steps must be a power of two");
     D4_REQUIRE(c.policy_head_mlp_depth <= 6 && c.value_head_mlp_depth <= 6 && c.terminal_mlp_depth <= 6, "mlp depth > 6");
-    d4_engine* e = new d4_engine();
+    std::unique_ptr<d4_engine> owner(new d4_engine());           // every refusal below returns through D4_REQUIRE: the owner frees the engine
+    d4_engine* e = owner.get();
     e->c = c;
     e->D = c.dim;
     e->S = 1 + c.num_spatial_tokens + c.num_register_tokens + ((c.num_discrete_action_types > 0 || c.num_continuous_actions > 0) ? 1 : 0) + 1;   // no action token without an action space
@@ -1159,9 +1172,10 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
         e->S = e->P + c.num_latent_tokens;                     // [patches | latent tokens]; the last latent token is the trunk's one special token
         e->keep_lo = 0; e->keep_hi = e->P;
         if (encoder) { e->keep_lo = e->P; e->keep_hi = e->P + c.num_latent_tokens; }       // the latent (special) tokens are the encoder's output rows
-        D4_REQUIRE(e->S - 1 <= 160, "decoder mode: %d tokens per frame exceed the wide attention kernel's 160", e->S - 1);
+        D4_REQUIRE(wide || e->S - 1 <= 160, "decoder mode: %d tokens per frame exceed the wide attention kernel's 160", e->S - 1);
     }
-    D4_REQUIRE((decoder || e->S <= 64) && 2 * c.depth + 1 <= 64, "tokens per frame / pooled hiddens exceed 64");
+    D4_REQUIRE(!wide || e->S <= d4::WIDE_ATTN_MAX, "wide frames: %d tokens per frame exceed %d", e->S, d4::WIDE_ATTN_MAX);
+    D4_REQUIRE((wide || decoder || e->S <= 64) && 2 * c.depth + 1 <= 64, "tokens per frame / pooled hiddens exceed 64");
     e->hd = c.attn_heads * c.attn_dim_head;
     e->php = c.pool_heads;
     e->hp = c.pool_heads * 64;
@@ -1201,7 +1215,7 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
     d4::mlp_dims(e->posmlp, 2, 2 * c.dim, c.dim, (decoder && !encoder) ? c.decoder_pos_mlp_depth : 0, c.head_mlp_recipe);      // D4:3526-3532
     if (const char* gm = getenv("D4_GRAPH_MAX_ROWS")) e->graph_max_rows = atoi(gm);     // 0 disables graph replay
     d4::engine_layout(e, false);
-    *out = e;
+    *out = owner.release();
     return 0;
 }
 
@@ -1541,6 +1555,7 @@ int d4_debug_switch(const char* name, int value) {
     else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
     else if (name && !strcmp(name, "space_attn_tiled")) sw = &d4::g_space_attn_tiled;
     else if (name && !strcmp(name, "cross_attn_tiled")) sw = &d4::g_cross_attn_tiled;
+    else if (name && !strcmp(name, "small_attn_wide")) sw = &d4::g_small_attn_wide;
     if (!sw) return -1;
     const int old = *sw;
     *sw = value;
@@ -1691,12 +1706,13 @@ int d4_rmsnorm(const float* x, int ldx, const float* gamma, float* y, int ldy, i
 }
 
 // Operator-level test entry points of the inference attention cores (attn.hip): each fills the launcher's argument struct and calls it.
-int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+static int small_attn_entry(int wide, const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
                   const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
                   const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
                   int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
                   float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
     d4::SmallAttnArgs sa{};
+    sa.wide = wide;
     sa.q = q; sa.q_group_stride = q_group_stride; sa.q_item_stride = q_item_stride;
     sa.k = k; sa.k_group_stride = k_group_stride; sa.k_item_stride = k_item_stride;
     sa.v = v; sa.v_group_stride = v_group_stride; sa.v_item_stride = v_item_stride;
@@ -1709,6 +1725,24 @@ int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride,
     sa.softclamp = softclamp; sa.mask_special = mask_special; sa.belief = belief;
     sa.q_lo = q_lo; sa.q_hi = q_hi; sa.q_last = q_last; sa.dh = dh;
     return d4::small_attn(sa, static_cast<hipStream_t>(stream));
+}
+int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
+    return small_attn_entry(0, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
+                            k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
+                            nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
+}
+int d4_small_attn_wide(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
+    return small_attn_entry(1, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
+                            k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
+                            nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
 }
 
 int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,

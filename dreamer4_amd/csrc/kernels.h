@@ -119,6 +119,7 @@ extern int g_attn_out_cols;              // frame_fused.hip: 1 (default) attenti
 extern int g_time_attn_tiled;            // attn_tiled.hip: 0 (default) the tiled time-attention core of the training path runs above 64 frames only; 1 at any length (test hook)
 extern int g_space_attn_tiled;           // attn_tiled.hip: 1 the within-frame attention of the training path takes the tiled core at any size (test hook; default 0: above 64 tokens with d4_train_wide_set(1))
 extern int g_cross_attn_tiled;           // attn_tiled.hip: the same for the cross attentions
+extern int g_small_attn_wide;            // attn_wide_mfma.hip: 1 a small_attn call with `wide` set takes the wide core at any size (test hook; default 0: above 64 items per side)
 int gemm_force_config(int id);                             // test hook; returns the number of configurations
 const char* gemm_profile_class_name(int c);
 
@@ -143,8 +144,12 @@ struct SmallAttnArgs {
     int q_lo = 0, q_hi = 0, q_last = 1;   // q_last = 0: do not add the last token to the restricted query set
     int dh = 64;                          // head dim (16 / 32 / 64): lanes >= dh of the wavefront idle; rows are packed h * dh + lane
     uint16_t* out_b = nullptr;            // optional bf16 copy of the output (same strides as `out`): the next GEMM's bf16 activation image (bf16 engine)
+    int wide = 0;                         // != 0: more than 64 items on a side go to the tiled matrix-pipe core (attn_wide_mfma.hip, up to WIDE_ATTN_MAX per side);
+                                          // 0: the forms of attn.hip and their limits only
 };
 int small_attn(const SmallAttnArgs& p, hipStream_t stream);
+constexpr int WIDE_ATTN_MAX = 1024;       // cap of the wide core, items per side
+int wide_attn(const SmallAttnArgs& p, hipStream_t stream, const char** form);   // attn_wide_mfma.hip: validates and launches; called by small_attn only
 
 // AttentionPool core, value-side restructured: scores over the L hiddens from projected keys, then the softmax-
 // weighted (and gated) sum of the NORMALISED hiddens per head, u[m][h][:] = sigmoid(gate) * sum_l p[l][h] * h_l[m] / rms(h_l[m]);

@@ -175,6 +175,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         matmul_dtype='fp32',
         train_matmul_dtype='fp32',
         train_wide_frames=False,
+        wide_frames=False,
         use_loss_normalization=False,
         latent_flow_loss_weight=1.,
         shortcut_loss_weight=1.,
@@ -222,9 +223,14 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         # (not a reference argument) wide frames in the TRAINING forward: False (default) a space block, a learned-query pool and
         # an attention pool take at most 64 tokens per frame / latents / pooled hiddens (a larger model's training forward raises D4Error);
         # True: up to 1024 of each, on the tiled attention core (csrc/attn_tiled.hip) wherever a problem side exceeds 64 — smaller problems
-        # run the same kernels with the same bits as with False.  Training only: the inference engine keeps its limit, so generate() / the
-        # inference forward() of such a model still fail at d4_engine_create ("tokens per frame / pooled hiddens exceed 64").
+        # run the same kernels with the same bits as with False.  Training only: the inference engine has its own option, `wide_frames`.
         self.train_wide_frames = bool(train_wide_frames)
+        # (not a reference argument) wide frames in the inference engine, independent of `train_wide_frames`: False (default)
+        # at most 64 latent tokens, spatial tokens and tokens per frame (a larger model's generate() / inference forward() raise D4Error at
+        # d4_engine_create); True: up to 1024 of each, on the tiled matrix-pipe attention core (csrc/attn_wide_mfma.hip) wherever an
+        # attention has more than 64 items on a side — smaller ones run the same kernels with the same bits as with False.  More than 64
+        # pooled hiddens (depth >= 32) stay refused.
+        self.wide_frames = bool(wide_frames)
         self.use_loss_normalization = bool(use_loss_normalization)
         # loss weights of the training forward's total (dreamer4.py:4719-4725, 5257-5267, 7708-7723): two plain floats and four persistent
         # buffers of 1 or multi_token_pred_len elements — a checkpoint's values are loaded and used
@@ -529,6 +535,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         c.hl_gauss_sigma_to_bin_ratio, c.hl_gauss_eps = self.hl_sigma_ratio, self.hl_eps
         c.value_min, c.value_max = self.value_range
         c.max_batch, c.max_frames, c.max_parallel_frames, c.max_learn_rows = caps
+        c.wide_frames = int(self.wide_frames)
         return c
 
     def _ensure_engine(self, batch=1, frames=1, parallel=1, learn_rows=0):

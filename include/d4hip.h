@@ -79,6 +79,10 @@ typedef struct d4_config {
     int32_t max_frames;           /* KV-cache capacity in frames (prompt + generated) */
     int32_t max_parallel_frames;  /* frames evaluated in one parallel pass (1 = cached decode only) */
     int32_t max_learn_rows;       /* batch * time rows of one learn_from_experience call (0 = no learner) */
+    /* Wide frames: 0 (a zero-initialised struct) the engine takes at most 64 latent / spatial tokens and 64 tokens per frame
+     * (decoder / encoder mode: 160), as ever; != 0 each may reach 1024 in every mode, and an attention with more than 64 items on a side runs
+     * the tiled matrix-pipe core of csrc/attn_wide_mfma.hip (at <= 64 the same kernels and the same bits as with 0). */
+    int32_t wide_frames;
 } d4_config;
 
 typedef struct d4_engine d4_engine;
@@ -277,7 +281,10 @@ int d4_frame_fused_set(int mode);
  * runs above 64 frames only, 1 at any length, so that it can be checked at shapes the LDS core also handles.  Read by
  * d4_time_attn_workspace_bytes too: size the workspace with the value the calls will run under.
  * "space_attn_tiled" / "cross_attn_tiled" (training space / cross attention; NOT bit-identical either): 0 (default) the tiled core runs above
- * 64 items per side with d4_train_wide_set(1) only, 1 at any size.  Read by d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes too. */
+ * 64 items per side with d4_train_wide_set(1) only, 1 at any size.  Read by d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes too.
+ * "small_attn_wide" (inference attention, csrc/attn_wide_mfma.hip; NOT bit-identical: another summation order): 0 (default) a call with the wide
+ * option (d4_small_attn_wide, d4_config.wide_frames) takes the wide core above 64 items on a side only, 1 at any size.  Read when a frame is
+ * enqueued, like "pool_wide_keys". */
 int d4_debug_switch(const char* name, int value);
 int d4_gemm_force_config(int id);
 
@@ -386,7 +393,7 @@ int d4_train_arith_get(void);
  * d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes answer for the CURRENT setting (larger above 64 items with 1, unchanged otherwise),
  * so a caller sets the switch around the size query and around EACH forward / backward call alike (a `*_backward_saved` call must meet the
  * setting of its forward) and restores it after.  Process-wide like d4_train_arith_set; returns the previous value.  The inference engine is
- * not concerned: d4_engine_create still refuses more than 64 tokens per frame / pooled hiddens. */
+ * not concerned: its own option is d4_config.wide_frames (up to 1024 tokens per frame; more than 64 pooled hiddens stay refused). */
 int d4_train_wide_set(int on);
 int d4_train_scratch_bind(void* scratch, size_t bytes);
 size_t d4_ff_bf16_scratch_bytes(int rows, int dim, int inner);
@@ -477,13 +484,22 @@ int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride,
                   const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
                   int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
                   float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream);
+/* d4_small_attn with the wide option (SmallAttnArgs::wide = 1, what an engine with d4_config.wide_frames passes): more than 64 queries or keys
+ * run wide_attn_kernel<dh> (csrc/attn_wide_mfma.hip: up to 1024 per side, dh 16 / 32 / 64, 16-byte aligned q / k / v / output
+ * rows, no query restriction, belief with nq == nk only); at <= 64 per side the forms of d4_small_attn, bit for bit.  Forms are recorded under
+ * the family "wide_attn". */
+int d4_small_attn_wide(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream);
 int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
                 const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
                 const uint16_t* hid_b, void* stream);
 int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, const float* k_gamma, const float* inv_freq, float* cache, float* out,
                         int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
                         float softclamp, int dh, int mode, void* stream);
-/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn") picked at their last call (NULL: unknown
+/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn") picked at their last call (NULL: unknown
  * family or no call yet), and the family's full list: d4_debug_forms returns the number of forms (-1: unknown family), *name = form i or NULL. */
 const char* d4_debug_last_form(const char* family);
 int d4_debug_forms(const char* family, int i, const char** name);
