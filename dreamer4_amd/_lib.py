@@ -57,6 +57,23 @@ class RolloutIO(C.Structure):
     ]
 
 
+class GemmDesc(C.Structure):
+    """d4_gemm_desc: the GemmArgs fields the engine sets (include/d4hip.h)."""
+    _fields_ = [
+        ('A', C.c_void_p), ('lda', C.c_int32), ('W', C.c_void_p), ('ldw', C.c_int32), ('C', C.c_void_p), ('ldc', C.c_int32),
+        ('bias', C.c_void_p), ('R', C.c_void_p), ('ldr', C.c_int32),
+        ('M', C.c_int32), ('N', C.c_int32), ('K', C.c_int32), ('flags', C.c_int32), ('rms_eps', C.c_float),
+        ('C2', C.c_void_p), ('ldc2', C.c_int32), ('c2_S', C.c_int32), ('c2_lo', C.c_int32), ('c2_hi', C.c_int32), ('c2_last', C.c_int32),
+        ('batch', C.c_int32), ('strideA', C.c_int64), ('strideW', C.c_int64), ('strideC', C.c_int64),
+        ('Ab', C.c_void_p), ('Wb', C.c_void_p), ('Cb', C.c_void_p), ('C2b', C.c_void_p),
+        ('wplane', C.c_int64), ('wscale', C.c_void_p), ('strideWs', C.c_int64), ('aexp', C.c_void_p),
+    ]
+
+
+# d4_gemm_run families / d4_gemm_run_pair targets
+GEMM_TILE, GEMM_V2, GEMM_V2_KSPLIT, GEMM_X3, GEMM_X3SK, GEMM_H2, GEMM_SKINNY, GEMM_BF16, GEMM_BF16A = range(9)
+PAIR_SKINNY, PAIR_BF16A, PAIR_V2 = range(3)
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p)
 
 
@@ -156,6 +173,14 @@ SYMBOLS = {
     'd4_small_attn_wide': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
     'd4_pool_mix': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'd4_time_attn_decode': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P] + [_I] * 8 + [_P, _F, _I, _I, _P]),
+    'd4_gemm_family_configs': (_I, [_I]),
+    'd4_gemm_run': (_I, [C.POINTER(GemmDesc), _I, _I, _P]),
+    'd4_gemm_run_pair': (_I, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _I, _I, _P]),
+    'd4_tile16_weights': (_I, [_P, _I, _P, _I, _I, _P]),
+    'd4_frame_attn_out': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 2 + [_P] + [_I] * 3 + [_F] + [_I] * 3 + [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'd4_attn_out_cols': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 2 + [_P] + [_I] * 3 + [_F] + [_I] * 3 + [_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'd4_frame_pool': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'd4_frame_pool_tail': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'd4_debug_last_form': (C.c_char_p, [C.c_char_p]),
     'd4_debug_forms': (_I, [C.c_char_p, _I, C.POINTER(C.c_char_p)]),
     'd4_rmsnorm_backward': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),

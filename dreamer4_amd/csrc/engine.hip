@@ -1769,6 +1769,179 @@ int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, 
 const char* d4_debug_last_form(const char* family) { return d4::attn_last_form(family); }
 int d4_debug_forms(const char* family, int i, const char** name) { return d4::attn_form_name(family, i, name); }
 
+// Operator-level test entry points of the GEMM launches only the engine reaches otherwise: one family / configuration named by the caller, straight to
+// its launcher; and the pair launches.  A refusal names its reason and nothing falls through to another family.
+static d4::GemmArgs gemm_args_of(const d4_gemm_desc& d) {
+    d4::GemmArgs g{d.A, d.lda, d.W, d.ldw, d.C, d.ldc, d.bias, d.R, d.ldr, d.M, d.N, d.K, d.flags, d.rms_eps};
+    g.C2 = d.C2; g.ldc2 = d.ldc2; g.c2_S = d.c2_S; g.c2_lo = d.c2_lo; g.c2_hi = d.c2_hi; g.c2_last = d.c2_last;
+    g.batch = d.batch > 0 ? d.batch : 1; g.strideA = d.strideA; g.strideW = d.strideW; g.strideC = d.strideC;
+    g.Ab = d.Ab; g.Wb = d.Wb; g.Cb = d.Cb; g.C2b = d.C2b; g.wplane = d.wplane; g.wscale = d.wscale; g.strideWs = d.strideWs; g.aexp = d.aexp;
+    return g;
+}
+static int gemm_desc_check(const char* who, const d4_gemm_desc* d) {
+    D4_REQUIRE(d && d->M >= 1 && d->N >= 1 && d->K >= 1 && (d->C || d->Cb), "%s: null descriptor, no output or bad sizes", who);
+    D4_REQUIRE(!(d->C2 || d->C2b) || (d->C2 && d->c2_S >= 1 && d->c2_lo >= 0 && d->c2_hi >= d->c2_lo && d->c2_hi <= d->c2_S && d->ldc2 >= d->N &&
+                                      (d->c2_last == 0 || d->c2_last == 1) && !(d->flags & d4::GEMM_SWIGLU)),
+               "%s: bad compaction arguments", who);
+    return 0;
+}
+int d4_gemm_family_configs(int family) {
+    switch (family) {
+        case D4_GEMM_TILE: return d4::gemm_configs();
+        case D4_GEMM_V2: return d4::gemm2_configs();
+        case D4_GEMM_X3: return d4::gemm_x3_configs();
+        case D4_GEMM_H2: return d4::gemm_h2_configs();
+        case D4_GEMM_BF16: return d4::gemm_bf16_configs();
+        case D4_GEMM_BF16A: return d4::gemm_bf16a_configs();
+        case D4_GEMM_V2_KSPLIT: case D4_GEMM_X3SK: case D4_GEMM_SKINNY: return 1;
+    }
+    return -1;
+}
+int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream) {
+    if (int rc = gemm_desc_check("d4_gemm_run", d)) return rc;
+    const d4::GemmArgs g = gemm_args_of(*d);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool al16 = ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && (g.lda % 4) == 0 && (g.ldw % 4) == 0;
+#define D4_RUN_REFUSE(cond, why) D4_REQUIRE(cond, "d4_gemm_run: call not supported (family %d, configuration %d, M=%d N=%d K=%d flags=%d: " why ")", family, config, g.M, g.N, g.K, g.flags)
+    switch (family) {
+        case D4_GEMM_TILE: {
+            D4_RUN_REFUSE(d4::gemm_config_valid(config, g), "the dispatcher does not run this configuration of the first family here - few-row shape, mirror weights or an epilogue the tile lacks");
+            d4_gemm_force_config(config);
+            const int rc = d4::gemm(g, s);
+            d4_gemm_force_config(-1);
+            return rc;
+        }
+        case D4_GEMM_V2:
+            D4_RUN_REFUSE(al16 && !g.Wb && d4::gemm2_config_valid(config, g), "gemm2_config_valid: K %% 32, lda / ldw %% 4, no transposed operand, SiLU-GLU tiles");
+            return d4::gemm2_launch(config, g, s);
+        case D4_GEMM_V2_KSPLIT:
+            D4_RUN_REFUSE(al16 && d4::gemm2_ksplit_applicable(g), "gemm2_ksplit_applicable: no batch, C2, row scale, bias-free flags other than SiLU; K >= 4 k-tiles");
+            return d4::gemm2_ksplit_launch(g, s);
+        case D4_GEMM_X3:
+            D4_RUN_REFUSE(al16 && !g.wscale && d4::gemm_x3_config_valid(config, g), "gemm_x3_config_valid: three bf16 planes, K %% 32, ldw / plane %% 8, SiLU-GLU tiles");
+            return d4::gemm_x3_launch(config, g, s);
+        case D4_GEMM_X3SK:
+            D4_RUN_REFUSE(al16 && !g.wscale && d4::gemm_x3sk_applicable(g), "gemm_x3sk_applicable: as gemm_x3, no batch");
+            return d4::gemm_x3sk_launch(g, s);
+        case D4_GEMM_H2:
+            D4_RUN_REFUSE(al16 && d4::gemm_h2_config_valid(config, g), "gemm_h2_config_valid: two fp16 planes + row scales, K %% 32, ldw / plane %% 8, SiLU-GLU tiles");
+            return d4::gemm_h2_launch(config, g, s);
+        case D4_GEMM_SKINNY:
+            D4_RUN_REFUSE(al16 && !g.Wb && d4::gemm_skinny_applicable(g) && (!(g.flags & d4::GEMM_SWIGLU) || g.N % 64 == 0),
+                          "gemm_skinny_applicable: at most 256 rows and fewer than 64 tiles, K % 4, no transposed operand, C2 without batch");
+            return d4::gemm_skinny(g, s);
+        case D4_GEMM_BF16: {
+            D4_RUN_REFUSE(((uintptr_t)g.A % 16) == 0 && !g.Ab && g.wplane == 0 && d4::gemm_bf16_config_valid(config, g), "gemm_bf16: bf16 weights, K %% 32, lda %% 4, ldw %% 8, SiLU-GLU tiles");
+            d4::gemm_bf16_force_config(config);
+            const int rc = d4::gemm_bf16(g, s);
+            d4::gemm_bf16_force_config(-1);
+            return rc;
+        }
+        case D4_GEMM_BF16A:
+            D4_RUN_REFUSE(d4::gemm_bf16a_config_valid(config, g), "gemm_bf16a_config_valid: bf16 images of both operands, K %% 64, lda / ldw %% 8, SiLU-GLU tiles");
+            return d4::gemm_bf16a_launch(config, g, s);
+    }
+    D4_REQUIRE(false, "d4_gemm_run: unknown family %d", family);
+#undef D4_RUN_REFUSE
+}
+int d4_gemm_run_pair(const d4_gemm_desc* da, const d4_gemm_desc* db, int target, int config, void* stream) {
+    if (int rc = gemm_desc_check("d4_gemm_run_pair", da)) return rc;
+    if (int rc = gemm_desc_check("d4_gemm_run_pair", db)) return rc;
+    const d4::GemmArgs a = gemm_args_of(*da), b = gemm_args_of(*db);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto al16 = [](const d4::GemmArgs& g) { return ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && (g.lda % 4) == 0 && (g.ldw % 4) == 0; };
+    switch (target) {
+        case D4_PAIR_SKINNY:
+            D4_REQUIRE(al16(a) && al16(b) && d4::gemm_skinny_pair_applicable(a, b),
+                       "d4_gemm_run_pair: call not supported (gemm_skinny_pair_applicable: two few-row products of equal K, no SiLU-GLU, batch or mirror weights)");
+            return d4::gemm_skinny_pair(a, b, s);
+        case D4_PAIR_BF16A:
+            D4_REQUIRE(d4::gemm_bf16a_pair_applicable(a, b),
+                       "d4_gemm_run_pair: call not supported (gemm_bf16a_pair_applicable: equal K, flags == RMS, no bias / R / C2 / batch, a 64 x 64 or 128 x 64 tile by the rule)");
+            return d4::gemm_bf16a_pair_launch(a, b, s);
+        case D4_PAIR_V2:
+            D4_REQUIRE(al16(a) && al16(b) && !a.Wb && !b.Wb && a.K == b.K && d4::gemm2_pair_config_ok(config) && d4::gemm2_pair_applicable(a, b) &&
+                       d4::gemm2_config_valid(config, a) && d4::gemm2_config_valid(config, b),
+                       "d4_gemm_run_pair: call not supported (gemm2 pair configuration %d: gemm2_pair_config_ok / gemm2_pair_applicable)", config);
+            return d4::gemm2_pair_launch(config, a, b, s);
+    }
+    D4_REQUIRE(false, "d4_gemm_run_pair: unknown target %d", target);
+}
+
+// ... and of the per-frame fused block tails (frame_fused.hip)
+int d4_tile16_weights(const float* W, int ldw, float* Wt, int N, int K, void* stream) {
+    D4_REQUIRE(W && Wt && N >= 16 && K >= 4 && ldw >= K && ((uintptr_t)W % 16) == 0 && ((uintptr_t)Wt % 16) == 0, "d4_tile16_weights: bad arguments");
+    return d4::tile16_weights(W, ldw, Wt, N, K, static_cast<hipStream_t>(stream));
+}
+static d4::SmallAttnArgs frame_attn_args(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                                         const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                                         const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                                         int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh) {
+    d4::SmallAttnArgs sa{};
+    sa.q = q; sa.q_group_stride = q_group_stride; sa.q_item_stride = q_item_stride;
+    sa.k = k; sa.k_group_stride = k_group_stride; sa.k_item_stride = k_item_stride;
+    sa.v = v; sa.v_group_stride = v_group_stride; sa.v_item_stride = v_item_stride;
+    sa.gate = gate; sa.g_group_stride = g_group_stride; sa.g_item_stride = g_item_stride;
+    sa.k_gamma = k_gamma;
+    sa.vres = vres; sa.r_group_stride = r_group_stride; sa.r_item_stride = r_item_stride;
+    sa.mix = mix; sa.m_group_stride = m_group_stride; sa.m_item_stride = m_item_stride;
+    sa.out_b = out_b;
+    sa.groups = frames; sa.heads = heads; sa.nq = S; sa.nk = S;
+    sa.softclamp = softclamp; sa.mask_special = mask_special; sa.belief = belief; sa.dh = dh;
+    return sa;
+}
+static int frame_out_check(const char* who, const float* resid, const float* out, const float* c2, int S, int c2_lo, int c2_hi, int c2_last) {
+    D4_REQUIRE(resid && out && ((uintptr_t)resid % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)c2 % 16) == 0, "%s: residual / output missing or not 16-byte aligned", who);
+    D4_REQUIRE(!c2 || (c2_lo >= 0 && c2_hi >= c2_lo && c2_hi <= S && (c2_last == 0 || c2_last == 1)), "%s: bad compaction arguments", who);
+    return 0;
+}
+int d4_frame_attn_out(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                      const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                      const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                      int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh,
+                      const float* wo_t, int D, const float* resid, int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last,
+                      void* stream) {
+    const d4::SmallAttnArgs sa = frame_attn_args(q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride,
+                                                 g_item_stride, k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out_b, frames, heads, S,
+                                                 softclamp, mask_special, belief, dh);
+    if (int rc = frame_out_check("d4_frame_attn_out", resid, out, c2, S, c2_lo, c2_hi, c2_last)) return rc;
+    D4_REQUIRE(wo_t && ((uintptr_t)wo_t % 16) == 0 && ldr >= D && ldo >= D && (!c2 || ldc2 >= D), "d4_frame_attn_out: weight image missing / misaligned or a leading dimension below D");
+    return d4::frame_attn_out(sa, wo_t, D, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
+}
+int d4_attn_out_cols(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                     const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                     const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                     int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh,
+                     const float* W, int ldw, int D, const float* resid, int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last,
+                     void* stream) {
+    const d4::SmallAttnArgs sa = frame_attn_args(q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride,
+                                                 g_item_stride, k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out_b, frames, heads, S,
+                                                 softclamp, mask_special, belief, dh);
+    D4_REQUIRE(resid && out && (!c2 || (c2_lo >= 0 && c2_hi >= c2_lo && c2_hi <= S && (c2_last == 0 || c2_last == 1))), "d4_attn_out_cols: residual / output missing or bad compaction arguments");
+    D4_REQUIRE(W && ldw >= heads * 64 && ldr >= D && ldo >= D && (!c2 || ldc2 >= D), "d4_attn_out_cols: weights missing or a leading dimension below its width");
+    return d4::attn_out_cols(sa, W, ldw, D, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
+}
+int d4_frame_pool(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
+                  const float* k_gamma, int M, int L, int heads, float eps, const float* wv_t, const float* wo_t, int frames, int S, const float* resid,
+                  int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream) {
+    d4::PoolMixArgs pm{};
+    pm.q = q; pm.ldq = ldq; pm.x = x; pm.ldx = ldx; pm.gate_w = gate_w; pm.k = k; pm.ldk = ldk; pm.hid = hid; pm.D = D; pm.k_gamma = k_gamma;
+    pm.M = M; pm.L = L; pm.heads = heads; pm.eps = eps;
+    if (int rc = frame_out_check("d4_frame_pool", resid, out, c2, S, c2_lo, c2_hi, c2_last)) return rc;
+    D4_REQUIRE(x && gate_w && hid && k_gamma && wv_t && wo_t && ((uintptr_t)wv_t % 16) == 0 && ((uintptr_t)wo_t % 16) == 0 && ((uintptr_t)q % 16) == 0 &&
+               ((uintptr_t)k % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)hid % 16) == 0 && ((uintptr_t)gate_w % 16) == 0 && ((uintptr_t)k_gamma % 16) == 0 &&
+               ldq % 4 == 0 && ldk % 4 == 0 && ldx % 4 == 0 && ldq >= heads * 64 && ldk >= heads * 64 && ldx >= D && ldr >= D && ldo >= D && (!c2 || ldc2 >= D),
+               "d4_frame_pool: operand missing / not 16-byte aligned or a leading dimension below its width");
+    return d4::frame_pool(pm, wv_t, wo_t, frames, S, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
+}
+int d4_frame_pool_tail(const float* u, const float* wv_t, const float* wo_t, int frames, int S, int D, int pool_heads, const float* resid, int ldr,
+                       float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream) {
+    if (int rc = frame_out_check("d4_frame_pool_tail", resid, out, c2, S, c2_lo, c2_hi, c2_last)) return rc;
+    D4_REQUIRE(u && wv_t && wo_t && ((uintptr_t)u % 16) == 0 && ((uintptr_t)wv_t % 16) == 0 && ((uintptr_t)wo_t % 16) == 0 && ldr >= D && ldo >= D && (!c2 || ldc2 >= D),
+               "d4_frame_pool_tail: operand missing / not 16-byte aligned or a leading dimension below D");
+    return d4::frame_pool_tail(u, wv_t, wo_t, frames, S, D, pool_heads, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
+}
+
 int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps, void* stream) {
     D4_REQUIRE(x && dy && gamma && dx && d_gamma && scratch, "d4_rmsnorm_backward: null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);

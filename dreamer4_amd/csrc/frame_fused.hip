@@ -318,6 +318,7 @@ bool frame_fused_frames_ok(int frames) { return frame_fused_on() && frames >= 19
 bool frame_attn_out_applicable(const SmallAttnArgs& sa, int D) {
     auto al4 = [](const void* q, int64_t a, int64_t b) { return ((uintptr_t)q % 16) == 0 && (a % 4) == 0 && (b % 4) == 0; };
     return frame_fused_frames_ok(sa.groups) && sa.dh == 64 && sa.heads == 8 && sa.nq == sa.nk && sa.nk >= 1 && sa.nk <= 16 && sa.q_hi == 0 && D % 32 == 0 && D >= 256 &&
+           !sa.out_b &&                // (the kernel keeps the attention output in LDS: there is no bf16 image to write; the engine never asks for one here)
            al4(sa.q, sa.q_group_stride, sa.q_item_stride) && al4(sa.k, sa.k_group_stride, sa.k_item_stride) && al4(sa.v, sa.v_group_stride, sa.v_item_stride) &&
            (!sa.vres || al4(sa.vres, sa.r_group_stride, sa.r_item_stride)) && ((uintptr_t)sa.k_gamma % 16) == 0;
 }

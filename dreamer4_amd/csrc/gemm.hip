@@ -522,6 +522,13 @@ static std::map<TuneKey, int> g_tuned, g_tuned2, g_tuned3, g_tuned4;
 static int g_forced_cfg = -1;          // test hook (d4_gemm_force_config): run this configuration wherever it is valid;
                                        // 100 + c: configuration c of the second family (gemm2.hip)
 int gemm_force_config(int id) { g_forced_cfg = id; return N_TILE_CFG; }
+int gemm_configs() { return N_TILE_CFG; }
+// would gemm() under gemm_force_config(c) run configuration c of THIS family on the call?  (The few-row kernel and the mirror-weight families come first there.)
+bool gemm_config_valid(int c, const GemmArgs& p) {
+    if (c < 0 || c >= N_TILE_CFG || p.Wb || p.M < 1 || gemm_skinny_applicable(p)) return false;
+    const bool ta = p.flags & GEMM_TRANS_A, tb = p.flags & GEMM_TRANS_B;
+    return ta ? (tb ? cfg_valid<true, true>(c, p) : cfg_valid<true, false>(c, p)) : (tb ? cfg_valid<false, true>(c, p) : cfg_valid<false, false>(c, p));
+}
 
 // D4_GEMM_TUNE_CACHE=<file>: the shape -> configuration table is read at first use and every new entry is appended, so a
 // later process (a profiler pass, a restarted trainer) starts with the choices already made and never re-times.

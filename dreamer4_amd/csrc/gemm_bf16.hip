@@ -358,6 +358,9 @@ static bool bf16_cfg_valid(int id, const GemmArgs& p) {
     return true;
 }
 
+int gemm_bf16_configs() { return B16_N; }
+bool gemm_bf16_config_valid(int c, const GemmArgs& p) { return gemm_bf16_applicable(p) && bf16_cfg_valid(c, p); }
+
 // tile choice by rule
 int gemm_bf16(const GemmArgs& p, hipStream_t stream) {
     D4_REQUIRE(gemm_bf16_applicable(p), "gemm_bf16: call not supported (M=%d N=%d K=%d flags=%d)", p.M, p.N, p.K, p.flags);

@@ -164,22 +164,21 @@ __global__ __launch_bounds__(512) void gemm_bf16p_kernel(GemmArgs p) {
                 for (int j = 0; j < 2; ++j)
                     acc[MI * 4 + i][NJ * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][h], af[i][h], acc[MI * 4 + i][NJ * 2 + j], 0, 0, 0);
     };
-    // folded RMSNorm: the wave column wc owns the row sums of m-tile wc of a0 and of a1 (register index 0 of each, see `rot`): v_dot2c_f32_bf16 squares
-    // and adds two bf16 per instruction in fp32
-    float ssq[2] = {0.f, 0.f};
+    // folded RMSNorm: the wave column wc owns the row sums of m-tile wc of a0 and of a1 (register index 0 of each, see `rot`).  The sum of squares of a
+    // row is formed in the ORDER of gemm_bf16a.hip, so that the row scale — and with it every output — has the bits of the plain configurations: one
+    // fused multiply-add chain per 16-byte chunk of the row (8 elements per k-tile, k-tiles in order; this lane holds chunks kq and kq + 4), the eight
+    // chunk sums then as the balanced tree ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)) after the k-loop.
+    float ssq[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
     auto sumsq = [&](const bf16x8_p (&af)[4][2], auto which_tag) {
         constexpr int WHICH = decltype(which_tag)::value;
         if constexpr (RMS) {
-            typedef __bf16 bf16x2_p __attribute__((ext_vector_type(2)));
-            float s = ssq[WHICH];
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
+            for (int h = 0; h < 2; ++h) {
+                float s = ssq[WHICH][h];
 #pragma unroll
-                for (int e = 0; e < 8; e += 2) {
-                    const bf16x2_p v = {af[0][h][e], af[0][h][e + 1]};
-                    s = __builtin_amdgcn_fdot2_f32_bf16(v, v, s, false);
-                }
-            ssq[WHICH] = s;
+                for (int e = 0; e < 8; ++e) { const float f = (float)af[0][h][e]; s = __builtin_fmaf(f, f, s); }
+                ssq[WHICH][h] = s;
+            }
         }
     };
 
@@ -251,9 +250,10 @@ __global__ __launch_bounds__(512) void gemm_bf16p_kernel(GemmArgs p) {
     if constexpr (RMS) {
 #pragma unroll
         for (int w = 0; w < 2; ++w) {
-            float s = ssq[w];                                 // chunks kq and kq + 4 of row frow; the other six chunks sit in lanes frow + 16 q
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
+            float lo = ssq[w][0], hi = ssq[w][1];             // chunks kq and kq + 4 of row frow; the other six chunks sit in lanes frow + 16 q
+            lo += __shfl_xor(lo, 16); hi += __shfl_xor(hi, 16);
+            lo += __shfl_xor(lo, 32); hi += __shfl_xor(hi, 32);
+            const float s = lo + hi;
             if (kq == 0) rowscale_s[grp * 128 + w * 64 + wc * 16 + frow] = rsqrtf(s / (float)q.K + q.rms_eps);
         }
     }

@@ -49,6 +49,8 @@ int gemm(const GemmArgs& p, hipStream_t stream);
 // bf16 MFMA path (gemm_bf16.hip): A fp32 rounded to bf16 on the way into LDS, W pre-converted, fp32 accumulate / epilogue
 bool gemm_bf16_applicable(const GemmArgs& p);
 int gemm_bf16(const GemmArgs& p, hipStream_t stream);
+int gemm_bf16_configs();
+bool gemm_bf16_config_valid(int c, const GemmArgs& p);     // the forced configuration gemm_bf16 would take
 int gemm_bf16_force_config(int id);                          // test / microbenchmark hook; returns the number of configurations
 void gemm_bf16a_force_config(int id);                        // ... of the bf16-activation kernel (-1: by rule)
 int cvt_f32_to_bf16(const float* src, uint16_t* dst, int64_t n, hipStream_t s);
@@ -121,6 +123,8 @@ extern int g_space_attn_tiled;           // attn_tiled.hip: 1 the within-frame a
 extern int g_cross_attn_tiled;           // attn_tiled.hip: the same for the cross attentions
 extern int g_small_attn_wide;            // attn_wide_mfma.hip: 1 a small_attn call with `wide` set takes the wide core at any size (test hook; default 0: above 64 items per side)
 int gemm_force_config(int id);                             // test hook; returns the number of configurations
+int gemm_configs();                                        // first fp32 family (gemm.hip)
+bool gemm_config_valid(int c, const GemmArgs& p);          // gemm() under gemm_force_config(c) runs configuration c of the first family on this call
 const char* gemm_profile_class_name(int c);
 
 // ------------------------------------------------------------------------------------ small attention

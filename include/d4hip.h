@@ -504,6 +504,68 @@ int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, 
 const char* d4_debug_last_form(const char* family);
 int d4_debug_forms(const char* family, int i, const char** name);
 
+/* Operator-level entry points of the launches only the engine reaches otherwise (test / tooling use): one GEMM family and configuration chosen by
+ * the caller, the pair launches, and the per-frame fused block tails of csrc/frame_fused.hip.  Each fills the launcher's argument struct
+ * (csrc/kernels.h: GemmArgs, SmallAttnArgs, PoolMixArgs) and calls the launcher the engine calls; no kernel has a test-only branch.
+ * d4_gemm_desc carries every GemmArgs field the engine sets (see csrc/kernels.h for their meaning; strides and leading dimensions in elements). */
+typedef struct d4_gemm_desc {
+    const float* A; int32_t lda;
+    const float* W; int32_t ldw;
+    float* C; int32_t ldc;
+    const float* bias;
+    const float* R; int32_t ldr;
+    int32_t M, N, K, flags;
+    float rms_eps;
+    float* C2; int32_t ldc2, c2_S, c2_lo, c2_hi, c2_last;
+    int32_t batch; int64_t strideA, strideW, strideC;
+    const uint16_t* Ab; const uint16_t* Wb; uint16_t* Cb; uint16_t* C2b;
+    int64_t wplane; const float* wscale; int64_t strideWs; const int32_t* aexp;
+} d4_gemm_desc;
+#define D4_GEMM_TILE 0          /* first fp32 family (csrc/gemm.hip) through the dispatcher under d4_gemm_force_config(config) */
+#define D4_GEMM_V2 1            /* gemm2_launch(config) */
+#define D4_GEMM_V2_KSPLIT 2     /* gemm2_ksplit_launch (config ignored) */
+#define D4_GEMM_X3 3            /* gemm_x3_launch(config) */
+#define D4_GEMM_X3SK 4          /* gemm_x3sk_launch (config ignored) */
+#define D4_GEMM_H2 5            /* gemm_h2_launch(config) */
+#define D4_GEMM_SKINNY 6        /* gemm_skinny (config ignored) */
+#define D4_GEMM_BF16 7          /* gemm_bf16 under its force hook (config) */
+#define D4_GEMM_BF16A 8         /* gemm_bf16a_launch(config); configuration 6 is the phased kernel of csrc/gemm_bf16p.hip */
+#define D4_GEMM_FAMILIES 9
+/* Number of configurations of a family (1 for the single-form targets, -1 for an unknown family). */
+int d4_gemm_family_configs(int family);
+/* Runs `d` on exactly the family / configuration named.  A call the family's `*_applicable` / `*_config_valid` refuses fails with an error that
+ * starts "d4_gemm_run: call not supported" and names the reason; nothing falls through to another family. */
+int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream);
+#define D4_PAIR_SKINNY 0        /* gemm_skinny_pair */
+#define D4_PAIR_BF16A 1         /* gemm_bf16a_pair_launch */
+#define D4_PAIR_V2 2            /* gemm2_pair_launch(config) */
+/* Two descriptors in ONE launch of the pair form named; refusals as d4_gemm_run ("d4_gemm_run_pair: call not supported"). */
+int d4_gemm_run_pair(const d4_gemm_desc* a, const d4_gemm_desc* b, int target, int config, void* stream);
+/* The per-frame fused tails.  d4_tile16_weights: W [N][ldw] -> Wt [N / 16][K / 4][16][4], the weight image the frame kernels stream.
+ * d4_frame_attn_out / d4_attn_out_cols: within-frame self attention of `frames` frames of S tokens (8 heads x 64; arguments as d4_small_attn)
+ * -> output projection to D columns (wo_t: the tiled image of Wo [D][512]; W: Wo itself, row-major at ldw) + resid, written to out [frames * S][ldo]
+ * and, when c2 is given, the rows c2_lo <= s < c2_hi (+ the last token when c2_last) of every frame to c2 [frames * (c2_hi - c2_lo + c2_last)][ldc2].
+ * d4_frame_pool: AttentionPool mix (arguments as d4_pool_mix, M = frames * S rows) -> per-head value projection (wv_t: tiled [4 * 64][D]) -> output
+ * projection (wo_t: tiled [D][4 * 64]) + resid; d4_frame_pool_tail the same from the mixes u [frames * S][heads][D] of d4_pool_mix. */
+int d4_tile16_weights(const float* W, int ldw, float* Wt, int N, int K, void* stream);
+int d4_frame_attn_out(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                      const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                      const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                      int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh,
+                      const float* wo_t, int D, const float* resid, int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last,
+                      void* stream);
+int d4_attn_out_cols(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                     const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                     const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                     int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh,
+                     const float* W, int ldw, int D, const float* resid, int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last,
+                     void* stream);
+int d4_frame_pool(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
+                  const float* k_gamma, int M, int L, int heads, float eps, const float* wv_t, const float* wo_t, int frames, int S, const float* resid,
+                  int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream);
+int d4_frame_pool_tail(const float* u, const float* wv_t, const float* wo_t, int frames, int S, int D, int pool_heads, const float* resid, int ldr,
+                       float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream);
+
 int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps,
                         void* stream);
 int d4_hl_gauss_scalar(const float* logits, int ld, const float* centers, float* out, int rows,
