@@ -183,6 +183,10 @@ SYMBOLS = {
     'd4_frame_pool_tail': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'd4_debug_last_form': (C.c_char_p, [C.c_char_p]),
     'd4_debug_forms': (_I, [C.c_char_p, _I, C.POINTER(C.c_char_p)]),
+    'd4_train_attn_core_plane_floats': (C.c_size_t, [_I] * 3),
+    'd4_train_xattn_core_plane_floats': (C.c_size_t, [_I] * 4),
+    'd4_train_attn_core': (_I, [_P, _I] + [_P] * 7 + [_I] * 4 + [_F, _I, _I, _I, _L, _L, _I, _P, _I, _P, C.c_size_t, _P]),
+    'd4_train_xattn_core': (_I, [_P, _I, _P, _I] + [_P] * 6 + [_I] * 6 + [_F, _I, _P, C.c_size_t, _P]),
     'd4_rmsnorm_backward': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     'd4_hl_gauss_scalar': (_I, [_P, _I, _P, _P, _I, _I, _P]),
     'd4_ppo_policy_loss': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),

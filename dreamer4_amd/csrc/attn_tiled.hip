@@ -511,9 +511,12 @@ int launch_dh(const TiledArgs& a, int dh, float* planes, hipStream_t s) {
     if (a.G * a.heads == 0) return 0;
     TiledPlanes t{};
     carve(t, planes, (size_t)a.G * a.nq, (size_t)a.G * a.nk, a.heads, dh, GEO == GEO_CROSS);
-    if (dh == 64) return launch_tiled<64, GEO>(a, t, s);
-    if (dh == 32) return launch_tiled<32, GEO>(a, t, s);
+#define D4_TILED_FORM(DH_) (GEO == GEO_TIME ? "tiled<time," #DH_ ">" : GEO == GEO_FRAME ? "tiled<frame," #DH_ ">" : "tiled<cross," #DH_ ">")
+    if (dh == 64) { note_train_form(GEO == GEO_CROSS, D4_TILED_FORM(64)); return launch_tiled<64, GEO>(a, t, s); }
+    if (dh == 32) { note_train_form(GEO == GEO_CROSS, D4_TILED_FORM(32)); return launch_tiled<32, GEO>(a, t, s); }
     D4_REQUIRE(dh == 16, "tiled attention core: head dim %d (16, 32 or 64)", dh);
+    note_train_form(GEO == GEO_CROSS, D4_TILED_FORM(16));
+#undef D4_TILED_FORM
     return launch_tiled<16, GEO>(a, t, s);
 }
 

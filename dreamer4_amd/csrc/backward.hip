@@ -408,16 +408,17 @@ static int attn_core(const AttnBwdArgs& a, int dh, hipStream_t s, float* tiled =
     if (a.F * a.heads == 0) return 0;
     if (tiled) return attn_tiled_core(a, dh, tiled, s);
     auto lds_of = [](int cap) { return (size_t)(6 * cap * AB_LD + 2 * cap * (cap + 1) + 4 * cap) * sizeof(float); };
-    static bool attr = false;
-    if (!attr) {
+    static DeviceOnce attr_set;
+    if (attr_set.need()) {
         D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<64, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(64)));
         D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<32, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(64)));
         D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<16, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(64)));
-        attr = true;
+        attr_set.done();
     }
     const dim3 grid(a.F * a.heads), block(256);
     const int cap = a.S <= 16 ? 16 : (a.S <= 32 ? 32 : 64);
-#define D4_AB_LAUNCH(DH_, CAP_) hipLaunchKernelGGL((attn_bwd_kernel<DH_, CAP_>), grid, block, lds_of(CAP_), s, a)
+#define D4_AB_LAUNCH(DH_, CAP_) do { note_train_form(false, "attn_bwd_kernel<" #DH_ "," #CAP_ ">"); \
+                                     hipLaunchKernelGGL((attn_bwd_kernel<DH_, CAP_>), grid, block, lds_of(CAP_), s, a); } while (0)
     if (dh == 64) { if (cap == 16) D4_AB_LAUNCH(64, 16); else if (cap == 32) D4_AB_LAUNCH(64, 32); else D4_AB_LAUNCH(64, 64); }
     else if (dh == 32) { if (cap <= 32) D4_AB_LAUNCH(32, 32); else D4_AB_LAUNCH(32, 64); }
     else { if (cap <= 32) D4_AB_LAUNCH(16, 32); else D4_AB_LAUNCH(16, 64); }
@@ -545,6 +546,7 @@ static int xattn_core(const XAttnArgs& a, int dh, hipStream_t s, float* tiled = 
         D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn_bwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, mx));
         attr_set.done();
     }
+    note_train_form(true, dh == 64 ? "xattn_bwd_kernel<64>" : dh == 32 ? "xattn_bwd_kernel<32>" : "xattn_bwd_kernel<16>");
     if (dh == 64) hipLaunchKernelGGL(xattn_bwd_kernel<64>, dim3(a.G * a.heads), dim3(256), lds, s, a);
     else if (dh == 32) hipLaunchKernelGGL(xattn_bwd_kernel<32>, dim3(a.G * a.heads), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(xattn_bwd_kernel<16>, dim3(a.G * a.heads), dim3(256), lds, s, a);
@@ -1041,6 +1043,71 @@ int d4_time_attn_backward_saved(const float* x, const float* residual_values, co
     const AttnGrads o{dx, d_residual_values, d_norm_w, d_wq, d_wk, d_wv, d_wo, d_w_gates, d_w_mix, d_b_mix, d_k_gamma};
     return attn_block_backward(x, residual_values, dy, prm, batch * frames * tokens, g, dim, heads, dim_head, softclamp, belief, o, workspace,
                                workspace_bytes, static_cast<hipStream_t>(stream), true);
+}
+
+// ---- operator-level entries of the attention cores (tests/test_gpu_train_cores.py): the argument block filled from the arguments and the core the
+// blocks call; core 0: the whole-problem-in-LDS kernel, core 1: the tiled core on the caller's planes.  No arithmetic of their own.
+size_t d4_train_attn_core_plane_floats(int rows, int heads, int dim_head) {
+    return rows > 0 && heads > 0 && dim_head > 0 ? attn_tiled_floats(rows, heads, dim_head) : 0;
+}
+size_t d4_train_xattn_core_plane_floats(int q_rows, int k_rows, int heads, int dim_head) {
+    return q_rows > 0 && k_rows > 0 && heads > 0 && dim_head > 0 ? attn_tiled_cross_floats(q_rows, k_rows, heads, dim_head) : 0;
+}
+
+int d4_train_attn_core(const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3,
+                       float* o3, float* dproj, float* d_rv, float* dgamma_part,
+                       int groups, int items, int heads, int dim_head, float softclamp, int num_special, int belief,
+                       int g_inner, int64_t g_outer_stride, int64_t item_stride, int causal, const float* inv_freq,
+                       int core, float* planes, size_t plane_floats, void* stream) {
+    D4_REQUIRE(proj && gamma && o3, "d4_train_attn_core: null proj, gamma or o3");
+    D4_REQUIRE(!d_o3 || (dproj && dgamma_part), "d4_train_attn_core: d_o3 given with null dproj or dgamma_part");
+    D4_REQUIRE(!d_o3 || !rv || d_rv, "d4_train_attn_core: d_o3 and rv given with null d_rv");
+    D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "d4_train_attn_core: dim_head %d (16, 32 or 64)", dim_head);
+    D4_REQUIRE(groups >= 1 && heads >= 1, "d4_train_attn_core: groups %d, heads %d (at least 1)", groups, heads);
+    D4_REQUIRE(items >= 1, "d4_train_attn_core: items %d (at least 1)", items);
+    D4_REQUIRE(core == 0 || core == 1, "d4_train_attn_core: core %d (0: LDS kernel, 1: tiled)", core);
+    D4_REQUIRE(core != 0 || items <= AB_S, "d4_train_attn_core: items %d with core 0 (max %d)", items, AB_S);
+    D4_REQUIRE(core != 1 || items <= ATT_MAX_FRAMES, "d4_train_attn_core: items %d with core 1 (max %d)", items, ATT_MAX_FRAMES);
+    const int hd = heads * dim_head, hp4 = (heads + 3) / 4 * 4;
+    D4_REQUIRE(ldp >= 3 * hd + hp4 + heads, "d4_train_attn_core: ldp %d below 3 * heads * dim_head + hp4 + heads = %d", ldp, 3 * hd + hp4 + heads);
+    D4_REQUIRE((causal != 0) == (inv_freq != nullptr), "d4_train_attn_core: causal and inv_freq go together (the time geometry) or are both absent");
+    D4_REQUIRE(num_special >= 0 && num_special <= items, "d4_train_attn_core: num_special %d outside 0..items (%d)", num_special, items);
+    D4_REQUIRE(num_special == 0 || !causal, "d4_train_attn_core: num_special %d with causal", num_special);
+    D4_REQUIRE(g_inner >= 1 && g_outer_stride >= 0 && item_stride >= 1, "d4_train_attn_core: g_inner %d, g_outer_stride %lld, item_stride %lld",
+               g_inner, (long long)g_outer_stride, (long long)item_stride);
+    if (core == 1) {
+        D4_REQUIRE(planes && ((uintptr_t)planes % 16) == 0, "d4_train_attn_core: core 1 needs planes (16-byte aligned)");
+        const size_t need = attn_tiled_floats(groups * items, heads, dim_head);
+        D4_REQUIRE(plane_floats >= need, "d4_train_attn_core: plane_floats %zu below d4_train_attn_core_plane_floats = %zu", plane_floats, need);
+    }
+    AttnBwdArgs a{proj, ldp, rv, gamma, d_o3, o3, dproj, d_rv, dgamma_part, groups, items, heads, hp4, softclamp, num_special, belief ? 1 : 0};
+    a.g_inner = g_inner; a.g_outer_stride = g_outer_stride; a.item_stride = item_stride; a.causal = causal ? 1 : 0; a.inv_freq = inv_freq;
+    return attn_core(a, dim_head, static_cast<hipStream_t>(stream), core == 1 ? planes : nullptr);
+}
+
+int d4_train_xattn_core(const float* projq, int ldq, const float* projk, int ldk, const float* gamma, const float* d_o3,
+                        float* o3, float* dprojq, float* dprojk, float* dgamma_part,
+                        int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,
+                        int core, float* planes, size_t plane_floats, void* stream) {
+    D4_REQUIRE(projq && projk && gamma && o3, "d4_train_xattn_core: null projq, projk, gamma or o3");
+    D4_REQUIRE(!d_o3 || (dprojq && dprojk && dgamma_part), "d4_train_xattn_core: d_o3 given with null dprojq, dprojk or dgamma_part");
+    D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "d4_train_xattn_core: dim_head %d (16, 32 or 64)", dim_head);
+    D4_REQUIRE(groups >= 1 && heads >= 1, "d4_train_xattn_core: groups %d, heads %d (at least 1)", groups, heads);
+    D4_REQUIRE(nq >= 1, "d4_train_xattn_core: nq %d (at least 1)", nq);
+    D4_REQUIRE(nk >= 1, "d4_train_xattn_core: nk %d (at least 1)", nk);
+    D4_REQUIRE(core == 0 || core == 1, "d4_train_xattn_core: core %d (0: LDS kernel, 1: tiled)", core);
+    D4_REQUIRE(core != 0 || (nq <= XA_N && nk <= XA_N), "d4_train_xattn_core: nq %d / nk %d with core 0 (max %d)", nq, nk, XA_N);
+    D4_REQUIRE(core != 1 || (nq <= ATT_MAX_FRAMES && nk <= ATT_MAX_FRAMES), "d4_train_xattn_core: nq %d / nk %d with core 1 (max %d)", nq, nk, ATT_MAX_FRAMES);
+    const int hd = heads * dim_head;
+    D4_REQUIRE(ldq >= hd + heads, "d4_train_xattn_core: ldq %d below heads * dim_head + heads = %d", ldq, hd + heads);
+    D4_REQUIRE(ldk >= 2 * hd, "d4_train_xattn_core: ldk %d below 2 * heads * dim_head = %d", ldk, 2 * hd);
+    if (core == 1) {
+        D4_REQUIRE(planes && ((uintptr_t)planes % 16) == 0, "d4_train_xattn_core: core 1 needs planes (16-byte aligned)");
+        const size_t need = attn_tiled_cross_floats(groups * nq, groups * nk, heads, dim_head);
+        D4_REQUIRE(plane_floats >= need, "d4_train_xattn_core: plane_floats %zu below d4_train_xattn_core_plane_floats = %zu", plane_floats, need);
+    }
+    XAttnArgs a{projq, ldq, projk, ldk, gamma, d_o3, o3, dprojq, dprojk, dgamma_part, groups, nq, nk, heads, item_major ? 1 : 0, softclamp};
+    return xattn_core(a, dim_head, static_cast<hipStream_t>(stream), core == 1 ? planes : nullptr);
 }
 
 }  // extern "C"

@@ -223,7 +223,9 @@ int time_kv_append(const TimeAttnArgs& p, hipStream_t stream);   // normalise/ro
 int time_attn(const TimeAttnArgs& p, hipStream_t stream);        // attend over cache[0 .. t0+i], belief + gates
 int time_attn_append(const TimeAttnArgs& p, hipStream_t stream); // both; ONE launch for the cached decode of one frame (head dim 64, aligned rows)
 // Host-side record of the kernel form each launcher above (families "small_attn", "pool_mix", "time_kv_append", "time_attn") picked last, and the
-// full list of a family's forms: for the operator tests (tests/test_gpu_attn_cores.py).
+// full list of a family's forms: for the operator tests (tests/test_gpu_attn_cores.py).  The attention cores of the training path record theirs
+// (families "train_attn", "train_xattn": tests/test_gpu_train_cores.py) through note_train_form, where they choose the launch.
+void note_train_form(bool cross, const char* name);
 const char* attn_last_form(const char* family);                  // nullptr: unknown family or nothing launched yet
 int attn_form_name(const char* family, int i, const char** name); // number of forms of the family (-1: unknown); *name = form i or nullptr
 

@@ -499,10 +499,29 @@ int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* g
 int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, const float* k_gamma, const float* inv_freq, float* cache, float* out,
                         int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
                         float softclamp, int dh, int mode, void* stream);
-/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn") picked at their last call (NULL: unknown
+/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn", "train_attn", "train_xattn") picked at their last call (NULL: unknown
  * family or no call yet), and the family's full list: d4_debug_forms returns the number of forms (-1: unknown family), *name = form i or NULL. */
 const char* d4_debug_last_form(const char* family);
 int d4_debug_forms(const char* family, int i, const char** name);
+
+/* Operator-level entry points of the attention cores of the training path (test / tooling use; the blocks above call the same cores).  Arguments are
+ * the fields of the cores' argument blocks (csrc/attn_tiled.h: AttnBwdArgs, XAttnArgs; hp4 = heads rounded up to 4); core 0 is the
+ * whole-problem-in-LDS kernel (<= 64 items per side), core 1 the tiled core (<= 1024) on `planes` of at least the *_plane_floats floats (16-byte
+ * aligned; rows = groups * items, q_rows = groups * nq, k_rows = groups * nk).  d_o3 null: forward only, o3 alone is written.  With d_o3 the
+ * self core writes the q / k / v, gate and mix columns of dproj (mix: +0 without rv), d_rv (with rv) and dgamma_part [groups][heads * dim_head]; the cross
+ * core the q and gate columns of dprojq, the k / v columns of dprojk, and dgamma_part.  Nothing else is written.  Forms are recorded under the
+ * families "train_attn" and "train_xattn" (by the block calls too). */
+size_t d4_train_attn_core_plane_floats(int rows, int heads, int dim_head);
+size_t d4_train_xattn_core_plane_floats(int q_rows, int k_rows, int heads, int dim_head);
+int d4_train_attn_core(const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3,
+                       float* o3, float* dproj, float* d_rv, float* dgamma_part,
+                       int groups, int items, int heads, int dim_head, float softclamp, int num_special, int belief,
+                       int g_inner, int64_t g_outer_stride, int64_t item_stride, int causal, const float* inv_freq,
+                       int core, float* planes, size_t plane_floats, void* stream);
+int d4_train_xattn_core(const float* projq, int ldq, const float* projk, int ldk, const float* gamma, const float* d_o3,
+                        float* o3, float* dprojq, float* dprojk, float* dgamma_part,
+                        int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,
+                        int core, float* planes, size_t plane_floats, void* stream);
 
 /* Operator-level entry points of the launches only the engine reaches otherwise (test / tooling use): one GEMM family and configuration chosen by
  * the caller, the pair launches, and the per-frame fused block tails of csrc/frame_fused.hip.  Each fills the launcher's argument struct
