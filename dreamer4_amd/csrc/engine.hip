@@ -775,13 +775,16 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
         if (t_bf16) if (uint16_t* ub = t_bf16->shadow_of(e->pool_u)) { pm.u_b = ub; if (t_bf16->shadow_only(e->pool_u)) pm.u = nullptr; }   // only the value GEMM reads the mixes
         // per-frame fused form (mix -> value projection -> output projection + residual in one kernel) where a frame per workgroup fills the chip;
         // frame_fused mode 2 (test hook): the mix stays its own kernel and only the tail is fused
+        // more than 64 hiddens (deep trunks): the chunked mix, always as its own kernel — the per-frame fused mix stays at L <= 64, its tail does not
+        // depend on L (test hook g_pool_mix_deep: the pools of <= 64 hiddens take the chunked kernel too)
+        const bool deep = L > 64 || g_pool_mix_deep;
         if (S > 0 && M % S == 0 && !e->pv_t.empty() && (!t_bf16 || t_bf16->fp32_planes()) && frame_pool_tail_applicable(M / S, S, D, c.pool_heads)) {
-            const bool tail_only = frame_fused_mode() == 2;
+            const bool tail_only = deep || frame_fused_mode() == 2;
             if (!tail_only) return frame_pool(pm, e->pv_t[p], e->po_t[p], M / S, S, x, D, y, D, y_compact, D, e->keep_lo, e->keep_hi, has_agent, s);
-            if ((rc = pool_mix(pm, s))) return rc;
+            if ((rc = deep ? pool_mix_deep(pm, s) : pool_mix(pm, s))) return rc;
             return frame_pool_tail(e->pool_u, e->pv_t[p], e->po_t[p], M / S, S, D, c.pool_heads, x, D, y, D, y_compact, D, e->keep_lo, e->keep_hi, has_agent, s);
         }
-        if ((rc = pool_mix(pm, s))) return rc;
+        if ((rc = deep ? pool_mix_deep(pm, s) : pool_mix(pm, s))) return rc;
         GemmArgs gv{e->pool_u, c.pool_heads * D, e->pkv_w[p] + (size_t)hp * D, D, e->pool_att, hp, nullptr, nullptr, 0, M, 64, D, 0, RMS_EPS};
         gv.batch = c.pool_heads; gv.strideA = D; gv.strideW = (int64_t)64 * D; gv.strideC = 64;
         if ((rc = engine_gemm(gv, s))) return rc;
@@ -1175,7 +1178,12 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
         D4_REQUIRE(wide || e->S - 1 <= 160, "decoder mode: %d tokens per frame exceed the wide attention kernel's 160", e->S - 1);
     }
     D4_REQUIRE(!wide || e->S <= d4::WIDE_ATTN_MAX, "wide frames: %d tokens per frame exceed %d", e->S, d4::WIDE_ATTN_MAX);
-    D4_REQUIRE((wide || decoder || e->S <= 64) && 2 * c.depth + 1 <= 64, "tokens per frame / pooled hiddens exceed 64");
+    D4_REQUIRE((wide || decoder || e->S <= 64) && (wide || 2 * c.depth + 1 <= 64), "tokens per frame / pooled hiddens exceed 64");
+    if (wide) {                                                          // deep trunks: pools of more than 64 hiddens take the chunked pool mix (pool_mix_deep.hip)
+        D4_REQUIRE(2 * c.depth + 1 <= d4::POOL_DEEP_MAX, "wide frames: %d pooled hiddens (depth %d) exceed %d", 2 * c.depth + 1, c.depth, d4::POOL_DEEP_MAX);
+        D4_REQUIRE(2 * c.depth + 1 <= 64 || (c.pool_heads == 4 && c.dim <= 1024),
+                   "wide frames: more than 64 pooled hiddens (depth %d) need the pool's mix path: pool_heads == 4 && dim <= 1024 (pool_heads=%d, dim=%d)", c.depth, c.pool_heads, c.dim);
+    }
     e->hd = c.attn_heads * c.attn_dim_head;
     e->php = c.pool_heads;
     e->hp = c.pool_heads * 64;
@@ -1552,6 +1560,7 @@ int d4_debug_switch(const char* name, int value) {
     if (name && !strcmp(name, "time_attn_fused_append")) sw = &d4::g_time_attn_fused_append;
     else if (name && !strcmp(name, "attn_out_cols")) sw = &d4::g_attn_out_cols;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
+    else if (name && !strcmp(name, "pool_mix_deep")) sw = &d4::g_pool_mix_deep;
     else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
     else if (name && !strcmp(name, "space_attn_tiled")) sw = &d4::g_space_attn_tiled;
     else if (name && !strcmp(name, "cross_attn_tiled")) sw = &d4::g_cross_attn_tiled;
@@ -1764,6 +1773,15 @@ int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, 
     ta.cache_batch = cache_batch; ta.cache_S = cache_S; ta.t0_dev = t0_dev; ta.softclamp = softclamp; ta.dh = dh;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return mode == 0 ? d4::time_attn_append(ta, s) : mode == 1 ? d4::time_kv_append(ta, s) : d4::time_attn(ta, s);
+}
+
+int d4_pool_mix_deep(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
+                     const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
+                     const uint16_t* hid_b, void* stream) {
+    d4::PoolMixArgs pm{};
+    pm.q = q; pm.ldq = ldq; pm.x = x; pm.ldx = ldx; pm.gate_w = gate_w; pm.k = k; pm.ldk = ldk; pm.hid = hid; pm.D = D; pm.k_gamma = k_gamma;
+    pm.u = u; pm.M = M; pm.L = L; pm.heads = heads; pm.eps = eps; pm.u_b = u_b; pm.k_b = k_b; pm.q_b = q_b; pm.hid_b = hid_b;
+    return d4::pool_mix_deep(pm, static_cast<hipStream_t>(stream));
 }
 
 const char* d4_debug_last_form(const char* family) { return d4::attn_last_form(family); }

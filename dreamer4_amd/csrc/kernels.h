@@ -175,6 +175,13 @@ struct PoolMixArgs {
                                        // values the pool's key GEMM consumed, at half the bytes of the kernel's dominant stream
 };
 int pool_mix(const PoolMixArgs& p, hipStream_t stream);
+// The same core over up to POOL_DEEP_MAX hiddens (pool_mix_deep.hip): the hiddens are walked in chunks of POOL_DEEP_CHUNK with an online-softmax
+// carry, so nothing of size L lives in LDS or registers.  The engine's pools of more than 64 hiddens (wide_frames, depth >= 32).
+constexpr int POOL_DEEP_MAX = 1024;       // cap of the chunked pool mix, hiddens per pool (2 depth + 1 <= 1024: depth <= 511)
+constexpr int POOL_DEEP_CHUNK = 64;
+int pool_mix_deep(const PoolMixArgs& p, hipStream_t stream);
+extern int g_pool_mix_deep;              // pool_mix_deep.hip: 1 = the engine's pools of <= 64 hiddens take pool_mix_deep too (test hook; default 0)
+void note_pool_deep_form(const char* name);                      // attn.hip: the form record of family "pool_mix_deep"
 
 // ------------------------------------------------------------------------------------ per-frame fused block tails (frame_fused.hip)
 // W [N][K] -> Wt [N / 16][K / 4][16][4]: the weight image the per-frame kernels stream (a 16-row tile is one contiguous run)
@@ -224,7 +231,8 @@ int time_attn(const TimeAttnArgs& p, hipStream_t stream);        // attend over 
 int time_attn_append(const TimeAttnArgs& p, hipStream_t stream); // both; ONE launch for the cached decode of one frame (head dim 64, aligned rows)
 // Host-side record of the kernel form each launcher above (families "small_attn", "pool_mix", "time_kv_append", "time_attn") picked last, and the
 // full list of a family's forms: for the operator tests (tests/test_gpu_attn_cores.py).  The attention cores of the training path record theirs
-// (families "train_attn", "train_xattn": tests/test_gpu_train_cores.py) through note_train_form, where they choose the launch.
+// (families "train_attn", "train_xattn": tests/test_gpu_train_cores.py) through note_train_form, where they choose the launch; the chunked pool mix
+// (family "pool_mix_deep": tests/test_gpu_deep_pool.py) through note_pool_deep_form.
 void note_train_form(bool cross, const char* name);
 const char* attn_last_form(const char* family);                  // nullptr: unknown family or nothing launched yet
 int attn_form_name(const char* family, int i, const char** name); // number of forms of the family (-1: unknown); *name = form i or nullptr

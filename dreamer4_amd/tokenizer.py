@@ -37,7 +37,8 @@ class VideoTokenizer(SaveLoad, nn.Module):
                  channels=3, decoder_flow_steps=1, head_mlp_recipe='pre_rms', wide_frames=False, **kwargs):
         """`wide_frames` is not a reference argument: False (default) the decoder and encoder engines take at most 160 tokens (patches +
         latents) and 64 latent tokens per frame; True up to 1024 of each, on the tiled attention core of csrc/attn_wide_mfma.hip above 64
-        items per side."""
+        items per side, and encoder / decoder trunks of depth >= 32 (up to 1024 pooled layer hiddens, the chunked pool mix of
+        csrc/pool_mix_deep.hip; refused without the option)."""
         config = dict(locals())
         super().__init__()
         self._record_config(config)

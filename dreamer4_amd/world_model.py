@@ -228,8 +228,9 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         # (not a reference argument) wide frames in the inference engine, independent of `train_wide_frames`: False (default)
         # at most 64 latent tokens, spatial tokens and tokens per frame (a larger model's generate() / inference forward() raise D4Error at
         # d4_engine_create); True: up to 1024 of each, on the tiled matrix-pipe attention core (csrc/attn_wide_mfma.hip) wherever an
-        # attention has more than 64 items on a side — smaller ones run the same kernels with the same bits as with False.  More than 64
-        # pooled hiddens (depth >= 32) stay refused.
+        # attention has more than 64 items on a side — smaller ones run the same kernels with the same bits as with False.  The same
+        # option takes the attention pools to 1024 layer hiddens (depth <= 511): a pool of more than 64 hiddens runs the chunked
+        # mix of csrc/pool_mix_deep.hip, pools of at most 64 keep their kernels and bits; without it depth >= 32 is refused at d4_engine_create.
         self.wide_frames = bool(wide_frames)
         self.use_loss_normalization = bool(use_loss_normalization)
         # loss weights of the training forward's total (dreamer4.py:4719-4725, 5257-5267, 7708-7723): two plain floats and four persistent

@@ -284,7 +284,10 @@ int d4_frame_fused_set(int mode);
  * 64 items per side with d4_train_wide_set(1) only, 1 at any size.  Read by d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes too.
  * "small_attn_wide" (inference attention, csrc/attn_wide_mfma.hip; NOT bit-identical: another summation order): 0 (default) a call with the wide
  * option (d4_small_attn_wide, d4_config.wide_frames) takes the wide core above 64 items on a side only, 1 at any size.  Read when a frame is
- * enqueued, like "pool_wide_keys". */
+ * enqueued, like "pool_wide_keys".
+ * "pool_mix_deep" (engine attention pools, csrc/pool_mix_deep.hip; NOT bit-identical: another summation order): 0 (default) a pool takes the
+ * chunked mix above 64 hiddens only (d4_config.wide_frames, depth >= 32), 1 every pool of the mix path does, as its own kernel in front of the
+ * fused tail where that applies.  Read when a frame is enqueued. */
 int d4_debug_switch(const char* name, int value);
 int d4_gemm_force_config(int id);
 
@@ -496,10 +499,18 @@ int d4_small_attn_wide(const float* q, int64_t q_group_stride, int64_t q_item_st
 int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
                 const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
                 const uint16_t* hid_b, void* stream);
+/* d4_pool_mix over 1 <= L <= 1024 hiddens (csrc/pool_mix_deep.hip; what an engine with d4_config.wide_frames runs for its pools of more than 64
+ * hiddens): same arguments, same arithmetic, the hiddens walked in chunks of 64 with an online-softmax carry (another summation order than
+ * d4_pool_mix at L <= 64, same values).  D % 4 == 0, D <= 1024, heads == 4; anything else is refused before any launch.  Forms are recorded
+ * under the family "pool_mix_deep". */
+int d4_pool_mix_deep(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
+                     const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
+                     const uint16_t* hid_b, void* stream);
 int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, const float* k_gamma, const float* inv_freq, float* cache, float* out,
                         int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
                         float softclamp, int dh, int mode, void* stream);
-/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn", "train_attn", "train_xattn") picked at their last call (NULL: unknown
+/* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn", "train_attn", "train_xattn",
+ * "pool_mix_deep") picked at their last call (NULL: unknown
  * family or no call yet), and the family's full list: d4_debug_forms returns the number of forms (-1: unknown family), *name = form i or NULL. */
 const char* d4_debug_last_form(const char* family);
 int d4_debug_forms(const char* family, int i, const char** name);
