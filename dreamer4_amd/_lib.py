@@ -171,6 +171,7 @@ SYMBOLS = {
     'd4_rmsnorm': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P]),
     'd4_small_attn': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
     'd4_small_attn_wide': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
+    'd4_small_attn_wide_bf16': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 3 + [_P] + [_I] * 4 + [_F] + [_I] * 6 + [_P]),
     'd4_pool_mix': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'd4_pool_mix_deep': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'd4_time_attn_decode': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P] + [_I] * 8 + [_P, _F, _I, _I, _P]),

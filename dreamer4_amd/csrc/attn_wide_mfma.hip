@@ -227,6 +227,7 @@ int wide_attn(const SmallAttnArgs& p, hipStream_t stream, const char** form) {
     const int64_t units = (int64_t)p.groups * p.heads;
     D4_REQUIRE(p.groups >= 0 && p.heads >= 0 && units <= 0x7fffffff, "wide attention: %d groups x %d heads", p.groups, p.heads);
     if (units == 0) return 0;
+    if (p.wide == 2) return wide_attn_bf16_launch(p, stream, form);      // bf16 products (attn_wide_bf16.hip): the same validation, grid and refusals
     const dim3 grid((unsigned)units, (unsigned)cdiv(p.nq, 64)), block(256);
     if (p.dh == 64) { *form = "wide_attn_kernel<64>"; hipLaunchKernelGGL(wide_attn_kernel<64>, grid, block, 0, stream, p); }
     else if (p.dh == 32) { *form = "wide_attn_kernel<32>"; hipLaunchKernelGGL(wide_attn_kernel<32>, grid, block, 0, stream, p); }

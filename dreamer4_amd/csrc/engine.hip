@@ -799,7 +799,7 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
     sa.k_gamma = a.k_gamma;
     sa.out = e->pool_att; sa.o_group_stride = hp; sa.o_item_stride = 0;
     sa.groups = M; sa.heads = c.pool_heads; sa.nq = 1; sa.nk = L;
-    sa.wide = c.wide_frames;
+    sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
     sa.out_b = t_bf16 ? t_bf16->shadow_of(e->pool_att) : nullptr;
     if ((rc = small_attn(sa, s))) return rc;
     }
@@ -882,7 +882,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->lq_in.k_gamma;
         sa.out = e->latt; sa.o_group_stride = (int64_t)ns * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = ns; sa.nk = n;
-        sa.wide = c.wide_frames;
+        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
         if ((rc = small_attn(sa, s))) return rc;
     }
     if ((rc = gemm_simple(e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0, s))) return rc;
@@ -938,7 +938,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             sa.k_gamma = a.k_gamma;
             sa.out = e->att; sa.o_group_stride = (int64_t)S * hd; sa.o_item_stride = hd;
             sa.groups = Fr; sa.heads = h; sa.nq = S; sa.nk = S;
-            sa.wide = c.wide_frames;
+            sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
             sa.softclamp = c.attn_softclamp_value; sa.mask_special = e->encoder ? n : has_agent; sa.belief = 1;
             sa.out_b = t_bf16 ? t_bf16->shadow_of(e->att) : nullptr;
             if (denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8) {
@@ -999,7 +999,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->cross.k_gamma;
         sa.out = e->catt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = P;
-        sa.wide = c.wide_frames;
+        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
         if ((rc = small_attn(sa, s))) return rc;
         if ((rc = gemm_simple(e->catt, hd, e->cross.to_out, hd, xfc, D, Mc, D, hd, 0, nullptr, spec, D, s))) return rc;
         if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, xfc, D, xfc, D, Mc, s))) return rc;
@@ -1032,7 +1032,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->cross.k_gamma;
         sa.out = e->catt; sa.o_group_stride = hd; sa.o_item_stride = 0;
         sa.groups = Fr; sa.heads = h; sa.nq = 1; sa.nk = S - 1;
-        sa.wide = c.wide_frames;
+        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
         if ((rc = small_attn(sa, s))) return rc;
         if ((rc = gemm_simple(e->catt, hd, e->cross.to_out, hd, agent_rows, ldc, Fr, D, hd, 0, nullptr, agent_in, lda, s))) return rc;
         if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, agent_rows, ldc, agent_rows, ldc, Fr, s))) return rc;
@@ -1058,7 +1058,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->lq_out.k_gamma;
         sa.out = e->oatt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = ns;
-        sa.wide = c.wide_frames;
+        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
         if ((rc = small_attn(sa, s))) return rc;
     }
     if ((rc = gemm_simple(e->oatt, hd, e->lout_w, hd, e->pred, dl, Fr * n, dl, hd, 0, nullptr, nullptr, 0, s))) return rc;
@@ -1143,7 +1143,10 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
     const bool encoder = c.mode == D4_MODE_ENCODER;
     const bool decoder = c.mode == D4_MODE_DECODER || encoder;          // (shared geometry checks below; e->decoder is set for the decoder only)
     D4_REQUIRE(c.mode == D4_MODE_DYNAMICS || decoder, "unknown engine mode %d", c.mode);
-    const bool wide = c.wide_frames != 0;                                // wide frames: the limits below rise to WIDE_ATTN_MAX (the wide attention core's cap)
+    // wide_frames is a bit set: bit 0 wide frames, bit 1 (with bit 0: value 3) the wide attention core's products on the bf16 matrix pipe
+    D4_REQUIRE(c.wide_frames >= 0 && c.wide_frames <= 3, "wide_frames=%d: 0, 1 (wide frames) or 3 (wide frames with bf16 attention products)", c.wide_frames);
+    D4_REQUIRE(c.wide_frames != 2, "wide_frames=2: bf16 attention products (bit 1) need wide frames (bit 0): there is nothing to switch without them");
+    const bool wide = (c.wide_frames & 1) != 0;                          // wide frames: the limits below rise to WIDE_ATTN_MAX (the wide attention core's cap)
     if (wide) {
         D4_REQUIRE(c.num_latent_tokens <= d4::WIDE_ATTN_MAX && (decoder || c.num_spatial_tokens <= d4::WIDE_ATTN_MAX), "wide frames: at most %d latent / spatial tokens", d4::WIDE_ATTN_MAX);
     } else {
@@ -1750,6 +1753,16 @@ int d4_small_attn_wide(const float* q, int64_t q_group_stride, int64_t q_item_st
                   int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
                   float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
     return small_attn_entry(1, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
+                            k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
+                            nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
+}
+
+int d4_small_attn_wide_bf16(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
+    return small_attn_entry(2, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
                             k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
                             nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
 }

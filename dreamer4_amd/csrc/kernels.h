@@ -149,11 +149,12 @@ struct SmallAttnArgs {
     int dh = 64;                          // head dim (16 / 32 / 64): lanes >= dh of the wavefront idle; rows are packed h * dh + lane
     uint16_t* out_b = nullptr;            // optional bf16 copy of the output (same strides as `out`): the next GEMM's bf16 activation image (bf16 engine)
     int wide = 0;                         // != 0: more than 64 items on a side go to the tiled matrix-pipe core (attn_wide_mfma.hip, up to WIDE_ATTN_MAX per side);
-                                          // 0: the forms of attn.hip and their limits only
+                                          // 2: that core with both products on the bf16 matrix pipe (attn_wide_bf16.hip); 0: the forms of attn.hip and their limits only
 };
 int small_attn(const SmallAttnArgs& p, hipStream_t stream);
 constexpr int WIDE_ATTN_MAX = 1024;       // cap of the wide core, items per side
 int wide_attn(const SmallAttnArgs& p, hipStream_t stream, const char** form);   // attn_wide_mfma.hip: validates and launches; called by small_attn only
+int wide_attn_bf16_launch(const SmallAttnArgs& p, hipStream_t stream, const char** form);   // attn_wide_bf16.hip: launches what wide_attn has validated (wide == 2)
 
 // AttentionPool core, value-side restructured: scores over the L hiddens from projected keys, then the softmax-
 // weighted (and gated) sum of the NORMALISED hiddens per head, u[m][h][:] = sigmoid(gate) * sum_l p[l][h] * h_l[m] / rms(h_l[m]);

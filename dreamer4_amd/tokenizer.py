@@ -34,11 +34,15 @@ _UNSUPPORTED = dict(
 class VideoTokenizer(SaveLoad, nn.Module):
     def __init__(self, dim, dim_latent, patch_size, image_size=None, image_height=None, image_width=None, num_latent_tokens=64,
                  encoder_depth=4, decoder_depth=4, time_block_every=4, attn_dim_head=64, attn_heads=8, decoder_pos_mlp_depth=2,
-                 channels=3, decoder_flow_steps=1, head_mlp_recipe='pre_rms', wide_frames=False, **kwargs):
+                 channels=3, decoder_flow_steps=1, head_mlp_recipe='pre_rms', wide_frames=False, attn_products='fp32',
+                 **kwargs):
         """`wide_frames` is not a reference argument: False (default) the decoder and encoder engines take at most 160 tokens (patches +
         latents) and 64 latent tokens per frame; True up to 1024 of each, on the tiled attention core of csrc/attn_wide_mfma.hip above 64
         items per side, and encoder / decoder trunks of depth >= 32 (up to 1024 pooled layer hiddens, the chunked pool mix of
-        csrc/pool_mix_deep.hip; refused without the option)."""
+        csrc/pool_mix_deep.hip; refused without the option).
+        `attn_products` is not a reference argument either: 'fp32' (default) the wide core's two products on the f32-input MFMA, as ever;
+        'bf16' (needs `wide_frames=True`) on the bf16 MFMA with bf16-rounded q, k', v' and softmax numerators and fp32 accumulation
+        (csrc/attn_wide_bf16.hip).  Attentions of at most 64 items per side keep their kernels and bits."""
         config = dict(locals())
         super().__init__()
         self._record_config(config)
@@ -63,6 +67,11 @@ class VideoTokenizer(SaveLoad, nn.Module):
         self.decoder_pos_mlp_depth, self.decoder_flow_steps = decoder_pos_mlp_depth, decoder_flow_steps
         self.head_mlp_recipe = head_mlp_recipe
         self.wide_frames = bool(wide_frames)
+        if attn_products not in ('fp32', 'bf16'):
+            raise ValueError("attn_products must be 'fp32' or 'bf16'")
+        if attn_products == 'bf16' and not self.wide_frames:
+            raise ValueError("attn_products='bf16' needs wide_frames=True: only the wide attention core has a bf16 form")
+        self.attn_products = attn_products
         self.latent_shape = (num_latent_tokens, dim_latent)
         self.ff_inner = int(dim * 4 * 2 / 3)
         self._build_parameters()
@@ -196,7 +205,7 @@ class VideoTokenizer(SaveLoad, nn.Module):
             c.patch_size, c.channels, c.image_height, c.image_width = self.patch_size, self.channels, self.image_height, self.image_width
             c.decoder_flow_steps, c.decoder_pos_mlp_depth = self.decoder_flow_steps, self.decoder_pos_mlp_depth
             c.max_batch, c.max_frames, c.max_parallel_frames, c.max_learn_rows = caps[0], caps[1], caps[1], 0
-            c.wide_frames = int(self.wide_frames)
+            c.wide_frames = 3 if self.attn_products == 'bf16' else int(self.wide_frames)
             eng = C.c_void_p()
             _lib.check(lib.d4_engine_create(C.byref(c), C.byref(eng)))
             st['engine'], st['caps'] = eng, caps

@@ -176,6 +176,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         train_matmul_dtype='fp32',
         train_wide_frames=False,
         wide_frames=False,
+        attn_products='fp32',
         use_loss_normalization=False,
         latent_flow_loss_weight=1.,
         shortcut_loss_weight=1.,
@@ -232,6 +233,18 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         # option takes the attention pools to 1024 layer hiddens (depth <= 511): a pool of more than 64 hiddens runs the chunked
         # mix of csrc/pool_mix_deep.hip, pools of at most 64 keep their kernels and bits; without it depth >= 32 is refused at d4_engine_create.
         self.wide_frames = bool(wide_frames)
+        # (not a reference argument) arithmetic of the two products of the engine's wide attention core, independent of
+        # `matmul_dtype`, `train_matmul_dtype` and `train_wide_frames`:
+        #   'fp32' (default)  q k'^T and p v' on the f32-input MFMA (csrc/attn_wide_mfma.hip), as ever, bit for bit
+        #   'bf16'            needs `wide_frames=True`: an attention with more than 64 items on a side runs csrc/attn_wide_bf16.hip — k' and
+        #                     v' prepared in fp32 and rounded to bf16, q and the softmax numerators rounded to bf16, both products on the bf16
+        #                     MFMA with fp32 accumulation; softmax, row sum, belief projection and head gate stay fp32.  Attentions of at
+        #                     most 64 items per side keep their kernels and bits.
+        if attn_products not in ('fp32', 'bf16'):
+            raise ValueError("attn_products must be 'fp32' or 'bf16'")
+        if attn_products == 'bf16' and not self.wide_frames:
+            raise ValueError("attn_products='bf16' needs wide_frames=True: only the wide attention core has a bf16 form")
+        self.attn_products = attn_products
         self.use_loss_normalization = bool(use_loss_normalization)
         # loss weights of the training forward's total (dreamer4.py:4719-4725, 5257-5267, 7708-7723): two plain floats and four persistent
         # buffers of 1 or multi_token_pred_len elements — a checkpoint's values are loaded and used
@@ -536,7 +549,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         c.hl_gauss_sigma_to_bin_ratio, c.hl_gauss_eps = self.hl_sigma_ratio, self.hl_eps
         c.value_min, c.value_max = self.value_range
         c.max_batch, c.max_frames, c.max_parallel_frames, c.max_learn_rows = caps
-        c.wide_frames = int(self.wide_frames)
+        c.wide_frames = 3 if self.attn_products == 'bf16' else int(self.wide_frames)      # (a bit set: 1 wide frames, 2 bf16 attention products)
         return c
 
     def _ensure_engine(self, batch=1, frames=1, parallel=1, learn_rows=0):

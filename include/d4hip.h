@@ -81,7 +81,9 @@ typedef struct d4_config {
     int32_t max_learn_rows;       /* batch * time rows of one learn_from_experience call (0 = no learner) */
     /* Wide frames: 0 (a zero-initialised struct) the engine takes at most 64 latent / spatial tokens and 64 tokens per frame
      * (decoder / encoder mode: 160), as ever; != 0 each may reach 1024 in every mode, and an attention with more than 64 items on a side runs
-     * the tiled matrix-pipe core of csrc/attn_wide_mfma.hip (at <= 64 the same kernels and the same bits as with 0). */
+     * the tiled matrix-pipe core of csrc/attn_wide_mfma.hip (at <= 64 the same kernels and the same bits as with 0).
+     * A bit set: bit 0 (value 1) is the above; bit 1 on top of it (value 3) runs those attentions on the bf16-product form of
+     * the core (csrc/attn_wide_bf16.hip), with any matmul_dtype.  2 (bit 1 alone) and values above 3 are refused by d4_engine_create. */
     int32_t wide_frames;
 } d4_config;
 
@@ -283,8 +285,8 @@ int d4_frame_fused_set(int mode);
  * "space_attn_tiled" / "cross_attn_tiled" (training space / cross attention; NOT bit-identical either): 0 (default) the tiled core runs above
  * 64 items per side with d4_train_wide_set(1) only, 1 at any size.  Read by d4_attn_workspace_bytes / d4_cross_attn_workspace_bytes too.
  * "small_attn_wide" (inference attention, csrc/attn_wide_mfma.hip; NOT bit-identical: another summation order): 0 (default) a call with the wide
- * option (d4_small_attn_wide, d4_config.wide_frames) takes the wide core above 64 items on a side only, 1 at any size.  Read when a frame is
- * enqueued, like "pool_wide_keys".
+ * option (d4_small_attn_wide, d4_config.wide_frames) takes the wide core above 64 items on a side only, 1 at any size (with the bf16-product
+ * option, d4_small_attn_wide_bf16 / wide_frames 3: that form of the core).  Read when a frame is enqueued, like "pool_wide_keys".
  * "pool_mix_deep" (engine attention pools, csrc/pool_mix_deep.hip; NOT bit-identical: another summation order): 0 (default) a pool takes the
  * chunked mix above 64 hiddens only (d4_config.wide_frames, depth >= 32), 1 every pool of the mix path does, as its own kernel in front of the
  * fused tail where that applies.  Read when a frame is enqueued. */
@@ -496,6 +498,16 @@ int d4_small_attn_wide(const float* q, int64_t q_group_stride, int64_t q_item_st
                   const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
                   int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
                   float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream);
+/* d4_small_attn_wide with both products on the bf16 matrix pipe (SmallAttnArgs::wide = 2, what an engine with d4_config.wide_frames = 3 passes):
+ * more than 64 queries or keys run wide_attn_bf16_kernel<dh> (csrc/attn_wide_bf16.hip) — k' and v' computed in fp32 and rounded to
+ * bf16, q and the per-tile p = exp(s - running max) rounded to bf16, fp32 accumulation, softmax, row sum, belief projection and head gate in
+ * fp32.  The limits and refusals of d4_small_attn_wide, with its messages; at <= 64 per side the forms of d4_small_attn, bit for bit.  Forms are
+ * recorded under the family "wide_attn_bf16". */
+int d4_small_attn_wide_bf16(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
+                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
+                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
+                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
+                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream);
 int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
                 const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
                 const uint16_t* hid_b, void* stream);
@@ -510,7 +522,7 @@ int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, 
                         int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
                         float softclamp, int dh, int mode, void* stream);
 /* Which kernel form the launchers of a family ("small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn", "train_attn", "train_xattn",
- * "pool_mix_deep") picked at their last call (NULL: unknown
+ * "pool_mix_deep", "wide_attn_bf16") picked at their last call (NULL: unknown
  * family or no call yet), and the family's full list: d4_debug_forms returns the number of forms (-1: unknown family), *name = form i or NULL. */
 const char* d4_debug_last_form(const char* family);
 int d4_debug_forms(const char* family, int i, const char** name);
