@@ -13,6 +13,31 @@ __device__ __forceinline__ float lerp_torch(float a, float b, float w) {
     return (fabsf(w) < 0.5f) ? a + w * d : b - d * (1.f - w);
 }
 
+// One online-softmax step over a 64-key tile of S^T accumulators: pr[kt][r] = S[query l & 15][key 16 kt + 4 kq + r] (-FLT_MAX: masked) and
+// this lane's maximum mt come in, the numerators exp(s - m) go out; m, l and the rows of o (queries 4 kq + r) are brought to the new maximum.
+// A tile that is all masked for a row leaves that row's m, l and o as they are.
+template <int NS>
+__device__ __forceinline__ void online_softmax_step(f32x4 (&pr)[4], float mt, float& m, float& l, f32x4 (&o)[NS], int kq) {
+    mt = fmaxf(mt, __shfl_xor(mt, 16)); mt = fmaxf(mt, __shfl_xor(mt, 32));
+    const float mn = fmaxf(m, mt);
+    const float alpha = expf(m - mn);                       // (first tile: exp(-huge) = 0 onto l = 0, o = 0)
+    float ls = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { pr[kt][r] = pr[kt][r] > -FLT_MAX ? expf(pr[kt][r] - mn) : 0.f; ls += pr[kt][r]; }
+    ls += __shfl_xor(ls, 16); ls += __shfl_xor(ls, 32);
+    l = l * alpha + ls;                                     // (the row sum takes the numerators as they are, before any rounding for P V)
+    m = mn;
+    // the accumulator's rows are queries 4 kq + r: their rescale sits on lane 4 kq + r
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float ar = __shfl(alpha, 4 * kq + r);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) o[s][r] *= ar;
+    }
+}
+
 constexpr int SM_LDV = 68;
 // One (group g, head h) on the calling wave.  Vs [KT * 16][SM_LDV], kinv_s / vinv_s [KT * 16]: this wave's LDS scratch.
 // store(orank, t, tok, value): output row `orank` (after the query-set restriction), feature 16 t + tok of head h.

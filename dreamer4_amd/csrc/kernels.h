@@ -152,7 +152,7 @@ struct SmallAttnArgs {
                                           // 2: that core with both products on the bf16 matrix pipe (attn_wide_bf16.hip); 0: the forms of attn.hip and their limits only
 };
 int small_attn(const SmallAttnArgs& p, hipStream_t stream);
-constexpr int WIDE_ATTN_MAX = 1024;       // cap of the wide core, items per side
+constexpr int WIDE_ATTN_MAX = 1024;       // cap of the wide core, items per side (attn_wide.h: the kernel skeleton both product forms below instantiate)
 int wide_attn(const SmallAttnArgs& p, hipStream_t stream, const char** form);   // attn_wide_mfma.hip: validates and launches; called by small_attn only
 int wide_attn_bf16_launch(const SmallAttnArgs& p, hipStream_t stream, const char** form);   // attn_wide_bf16.hip: launches what wide_attn has validated (wide == 2)
 
