@@ -70,6 +70,18 @@ class GemmDesc(C.Structure):
     ]
 
 
+class AssembleDesc(C.Structure):
+    """d4_assemble_desc: the AssembleArgs fields (include/d4hip.h)."""
+    _fields_ = [
+        ('tokens', C.c_void_p), ('space', C.c_void_p), ('signal_embed', C.c_void_p), ('step_embed', C.c_void_p), ('registers', C.c_void_p),
+        ('agent_embed', C.c_void_p), ('task_embed', C.c_void_p), ('action_embed', C.c_void_p), ('action_learned', C.c_void_p),
+        ('signal_levels', C.c_void_p), ('signal_uniform', C.c_int32), ('prev_actions', C.c_void_p), ('prev_cont', C.c_void_p),
+        ('cont_embed', C.c_void_p), ('tasks', C.c_void_p), ('action_offsets', C.c_void_p),
+        ('B', C.c_int32), ('Tq', C.c_int32), ('S', C.c_int32), ('D', C.c_int32), ('ns', C.c_int32), ('nr', C.c_int32), ('na', C.c_int32),
+        ('nc', C.c_int32), ('step_log2', C.c_int32), ('compact', C.c_void_p), ('has_agent', C.c_int32),
+    ]
+
+
 # d4_gemm_run families / d4_gemm_run_pair targets
 GEMM_TILE, GEMM_V2, GEMM_V2_KSPLIT, GEMM_X3, GEMM_X3SK, GEMM_H2, GEMM_SKINNY, GEMM_BF16, GEMM_BF16A = range(9)
 PAIR_SKINNY, PAIR_BF16A, PAIR_V2 = range(3)
@@ -190,6 +202,35 @@ SYMBOLS = {
     'd4_train_attn_core': (_I, [_P, _I] + [_P] * 7 + [_I] * 4 + [_F, _I, _I, _I, _L, _L, _I, _P, _I, _P, C.c_size_t, _P]),
     'd4_train_xattn_core': (_I, [_P, _I, _P, _I] + [_P] * 6 + [_I] * 6 + [_F, _I, _P, C.c_size_t, _P]),
     'd4_rmsnorm_backward': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    'd4_layernorm_rows': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
+    'd4_assemble_tokens': (_I, [C.POINTER(AssembleDesc), _P]),
+    'd4_gather_space_double_norm': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    'd4_colsum': (_I, [_P, _I, _I, _I, _P, _P, C.c_size_t, _P]),
+    'd4_colsum_batch': (_I, [_I, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_P), _P]),
+    'd4_rmsnorm_bwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    'd4_euler_step_rows': (_I, [_P, _I, _P, _I, _I, _I, _F, _F, _P]),
+    'd4_splitk_reduce': (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P]),
+    'd4_mean_tokens': (_I, [_P, _P, _I, _I, _I, _P]),
+    'd4_hl_gauss_scalar_strided': (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    'd4_unary_rows': (_I, [_I, _P, _P, _L, _P]),
+    'd4_fold_rows': (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    'd4_swiglu_pack_rows': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'd4_build_latent_input': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    'd4_copy_rows': (_I, [_P, _I, _P, _I, _I, _I, _P]),
+    'd4_pad_cols': (_I, [_P, _P, _I, _I, _I, _P]),
+    'd4_video_patches': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'd4_cache_transfer': (_I, [_P, _P] + [_I] * 9 + [_P]),
+    'd4_cunembed': (_I, [_I, _P, _P, _I, _I, _I, _P]),
+    'd4_coord_grid': (_I, [_P, _I, _I, _I, _P]),
+    'd4_pack_tokens': (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'd4_prep_eval_inputs': (_I, [_P, _P, _P] + [_I] * 7 + [_P, _P, _I, _P]),
+    'd4_layernorm_silu_bwd': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    'd4_silu_bwd': (_I, [_P, _P, _P, _L, _P]),
+    'd4_swiglu': (_I, [_I, _P, _P, _P, _I, _I, _I, _P]),
+    'd4_multi_copy': (_I, [_I, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64), _P]),
+    'd4_zero_pad_cols': (_I, [_P, _I, _I, _I, _I, _P]),
+    'd4_cvt_pad_bf16': (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
+    'd4_cvt_transpose_bf16': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'd4_hl_gauss_scalar': (_I, [_P, _I, _P, _P, _I, _I, _P]),
     'd4_ppo_policy_loss': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     'd4_gae': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P]),

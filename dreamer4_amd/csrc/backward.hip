@@ -49,6 +49,16 @@ __global__ void swiglu_bwd_kernel(const float* h, const float* du, float* dh, in
     }
 }
 static dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)); }
+static int swiglu_fwd(const float* h, float* u, int rows, int I, int Ip, hipStream_t s) {
+    hipLaunchKernelGGL(swiglu_fwd_kernel, grid_for((int64_t)rows * Ip), dim3(256), 0, s, h, u, rows, I, Ip);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+static int swiglu_bwd(const float* h, const float* du, float* dh, int rows, int I, int Ip, hipStream_t s) {
+    hipLaunchKernelGGL(swiglu_bwd_kernel, grid_for((int64_t)rows * Ip), dim3(256), 0, s, h, du, dh, rows, I, Ip);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
 
 static int gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, int M, int N, int K, int flags, hipStream_t s) {
     GemmArgs g{A, lda, W, ldw, C, ldc, bias, nullptr, 0, M, N, K, flags, 0.f};
@@ -242,9 +252,7 @@ static int ff_recompute(const FfWs& w, const float* x, const float* norm_w, cons
     if ((rc = pad_cols(w_out, w.w2p, D, I, Ip, s))) return rc;
     if ((rc = rmsnorm_rows(x, D, norm_w, w.xn, D, R, D, RMS_EPS, s))) return rc;
     if ((rc = gemm_b(w.xn, D, w.w1p, D, w.h, 2 * Ip, w.b1p, R, 2 * Ip, D, 0, s))) return rc;
-    hipLaunchKernelGGL(swiglu_fwd_kernel, grid_for((int64_t)R * Ip), dim3(256), 0, s, w.h, w.u, R, I, Ip);
-    D4_LAUNCH_CHECK();
-    return 0;
+    return swiglu_fwd(w.h, w.u, R, I, Ip, s);
 }
 
 // ------------------------------------------------------------------------------------------------ attention core backward
@@ -559,6 +567,13 @@ __global__ void zero_pad_cols_kernel(float* x, int rows, int ld, int c0, int c1)
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (int64_t)rows * n; i += (int64_t)gridDim.x * blockDim.x)
         x[(i / n) * ld + c0 + (int)(i % n)] = 0.f;
 }
+// columns c0 .. c1 of x [rows][ld] set to zero (nothing to do for an empty range)
+static int zero_pad_cols(float* x, int rows, int ld, int c0, int c1, hipStream_t s) {
+    if (c1 <= c0 || rows == 0) return 0;
+    hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)rows * (c1 - c0)), dim3(256), 0, s, x, rows, ld, c0, c1);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
 
 struct AttnWs {
     float *xn, *wcat, *bcat, *proj, *dproj, *d_o3, *o3, *dwcat, *tg, *dxn, *gpart, *part, *wt;
@@ -660,8 +675,7 @@ static int ff_backward_impl(const float* x, const float* dy, const float* norm_w
     if ((rc = gemm_dw(dy, D, w.u, Ip, w.dw2p, Ip, D, Ip, R, w.part, s))) return rc;                                    // dW2 = dy^T u
     if ((rc = copy_rows(w.dw2p, Ip, d_w_out, I, D, I, s))) return rc;
     if ((rc = lin_dx(dy, D, w.w2p, Ip, w.du, Ip, R, Ip, D, w.wt, s))) return rc;                                        // du = dy W2
-    hipLaunchKernelGGL(swiglu_bwd_kernel, grid_for((int64_t)R * Ip), dim3(256), 0, s, w.h, w.du, w.dh, R, I, Ip);
-    D4_LAUNCH_CHECK();
+    if ((rc = swiglu_bwd(w.h, w.du, w.dh, R, I, Ip, s))) return rc;
     image_a_written(w.dh);
     // h = xn W1^T + b1
     if ((rc = gemm_dw(w.dh, 2 * Ip, w.xn, D, w.dw1p, D, 2 * Ip, D, R, w.part, s))) return rc;                          // dW1 = dh^T xn
@@ -694,6 +708,27 @@ size_t d4_attn_workspace_bytes(int frames, int tokens, int dim, int heads, int d
     return attn_ws(nullptr, frames * tokens, frames, dim, heads, dim_head, space_tiled(tokens)).total * sizeof(float);
 }
 size_t d4_attn_bf16_scratch_bytes(int rows, int dim, int heads, int dim_head) { return attn_bf16_extra(rows, dim, heads * dim_head); }
+
+// Operator-level test entry points of the glue launchers of this file: the launchers the blocks call.
+int d4_swiglu(int bwd, const float* h, const float* du, float* out, int rows, int inner, int inner_pad, void* stream) {
+    D4_REQUIRE(h && out && rows >= 1 && inner >= 1 && inner_pad >= inner && (bwd == 0 || (bwd == 1 && du)), "d4_swiglu: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return bwd ? swiglu_bwd(h, du, out, rows, inner, inner_pad, s) : swiglu_fwd(h, out, rows, inner, inner_pad, s);
+}
+int d4_multi_copy(int count, float* const* dst, const float* const* src, const int64_t* n, void* stream) {
+    D4_REQUIRE(count >= 0 && count <= MultiCopy::MAX, "multi_copy: too many segments");
+    D4_REQUIRE(count == 0 || (dst && src && n), "d4_multi_copy: bad arguments");
+    MultiCopy mc;
+    for (int i = 0; i < count; ++i) {
+        D4_REQUIRE(n[i] >= 0 && (dst[i] || n[i] == 0), "d4_multi_copy: bad arguments of segment %d", i);
+        mc.add(dst[i], src[i], n[i]);
+    }
+    return multi_copy(mc, static_cast<hipStream_t>(stream));
+}
+int d4_zero_pad_cols(float* x, int rows, int ld, int c0, int c1, void* stream) {
+    D4_REQUIRE(x && rows >= 0 && c0 >= 0 && c1 >= c0 && ld >= c1, "d4_zero_pad_cols: bad arguments");
+    return zero_pad_cols(x, rows, ld, c0, c1, static_cast<hipStream_t>(stream));
+}
 
 }  // extern "C"
 
@@ -769,10 +804,8 @@ int attn_block_backward(const float* x, const float* residual_values, const floa
     if ((rc = attn_core(a, dim_head, s, w.tiled))) return rc;
     image_a_written(w.dproj);
     // the pad columns of the gate / mix logits and of the row carry no gradient
-    if (w.hp4 > heads) hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)R * (w.hp4 - heads)), dim3(256), 0, s, w.dproj, R, w.P, 3 * hd + heads, 3 * hd + w.hp4);
-    if (w.P > 3 * hd + w.hp4 + heads)
-        hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)R * (w.P - (3 * hd + w.hp4 + heads))), dim3(256), 0, s, w.dproj, R, w.P, 3 * hd + w.hp4 + heads, w.P);
-    D4_LAUNCH_CHECK();
+    if ((rc = zero_pad_cols(w.dproj, R, w.P, 3 * hd + heads, 3 * hd + w.hp4, s))) return rc;
+    if ((rc = zero_pad_cols(w.dproj, R, w.P, 3 * hd + w.hp4 + heads, w.P, s))) return rc;
     if ((rc = gemm_dw(dy, D, w.o3, hd, o.d_wo, hd, D, hd, R, w.part, s))) return rc;                                     // dWo = dy^T o3
     // projections: dW = dproj^T xn, dxn = dproj Wcat
     if (!t_bf.a) { if ((rc = gemm_dw(w.dproj, w.P, w.xn, D, w.dwcat, D, w.P, D, R, w.part, s))) return rc; }
@@ -918,10 +951,7 @@ static int cross_attn_backward_impl(const float* q_tokens, const float* ctx, con
     XAttnArgs a{w.projq, w.Pq, w.projk, w.Pk, k_gamma, w.d_o3, w.o3, w.dprojq, w.dprojk, w.gpart, groups, nq, nk, heads, ctx_item_major, softclamp};
     if ((rc = xattn_core(a, dim_head, s, w.tiled))) return rc;
     image_a_written(w.dprojq); image_a_written(w.dprojk);
-    if (w.hp4 > heads) {
-        hipLaunchKernelGGL(zero_pad_cols_kernel, grid_for((int64_t)Rq * (w.hp4 - heads)), dim3(256), 0, s, w.dprojq, Rq, w.Pq, hd + heads, w.Pq);
-        D4_LAUNCH_CHECK();
-    }
+    if (w.hp4 > heads && (rc = zero_pad_cols(w.dprojq, Rq, w.Pq, hd + heads, w.Pq, s))) return rc;
     if ((rc = gemm_dw(dy, D, w.o3, hd, d_wo, hd, D, hd, Rq, w.part, s))) return rc;
     // query side
     if (!t_bf.a) {

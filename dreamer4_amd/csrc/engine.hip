@@ -1717,6 +1717,108 @@ int d4_rmsnorm(const float* x, int ldx, const float* gamma, float* y, int ldy, i
     return d4::rmsnorm_rows(x, ldx, gamma, y, ldy, rows, dim, eps, static_cast<hipStream_t>(stream));
 }
 
+// Operator-level test entry points of the glue launchers of elementwise.hip: each checks its pointers and sizes, fills the launcher's
+// arguments and calls it.
+int d4_layernorm_rows(const float* x, int ldx, const float* g, const float* b, float* y, int ldy, int rows, int dim, float eps, int silu, void* stream) {
+    D4_REQUIRE(x && g && y && rows >= 0 && dim >= 1 && ldx >= dim && ldy >= dim, "d4_layernorm_rows: bad arguments");
+    return d4::layernorm_rows(x, ldx, g, b, y, ldy, rows, dim, eps, silu, static_cast<hipStream_t>(stream));
+}
+int d4_assemble_tokens(const d4_assemble_desc* d, void* stream) {
+    D4_REQUIRE(d && d->tokens && d->signal_embed && d->step_embed && d->agent_embed, "d4_assemble_tokens: null argument");
+    D4_REQUIRE(d->B >= 0 && d->Tq >= 0 && d->D >= 2 && d->D % 2 == 0 && d->ns >= 0 && d->nr >= 0 && d->na >= 0 && d->nc >= 0 && d->step_log2 >= 0 &&
+               (d->has_agent == 0 || d->has_agent == 1), "d4_assemble_tokens: bad sizes");
+    D4_REQUIRE(d->S == 1 + d->ns + d->nr + (d->na > 0 || d->nc > 0 ? 1 : 0) + d->has_agent, "d4_assemble_tokens: S %d is not 1 + ns + nr (+ action) (+ agent)", d->S);
+    D4_REQUIRE((d->ns == 0 || d->space) && (d->nr == 0 || d->registers) && (d->signal_levels || d->signal_uniform >= 0), "d4_assemble_tokens: table missing");
+    D4_REQUIRE((d->na == 0 && d->nc == 0) || d->action_learned, "d4_assemble_tokens: action_learned missing");
+    D4_REQUIRE(d->na == 0 || !d->prev_actions || (d->action_embed && d->action_offsets), "d4_assemble_tokens: action tables missing");
+    D4_REQUIRE(d->nc == 0 || !d->prev_cont || d->cont_embed, "d4_assemble_tokens: cont_embed missing");
+    D4_REQUIRE(!d->tasks || d->task_embed, "d4_assemble_tokens: task_embed missing");
+    d4::AssembleArgs a{};
+    a.tokens = d->tokens; a.space = d->space; a.signal_embed = d->signal_embed; a.step_embed = d->step_embed; a.registers = d->registers;
+    a.agent_embed = d->agent_embed; a.task_embed = d->task_embed; a.action_embed = d->action_embed; a.action_learned = d->action_learned;
+    a.signal_levels = d->signal_levels; a.signal_uniform = d->signal_uniform; a.prev_actions = d->prev_actions; a.prev_cont = d->prev_cont;
+    a.cont_embed = d->cont_embed; a.tasks = d->tasks; a.action_offsets = d->action_offsets;
+    a.B = d->B; a.Tq = d->Tq; a.S = d->S; a.D = d->D; a.ns = d->ns; a.nr = d->nr; a.na = d->na; a.nc = d->nc; a.step_log2 = d->step_log2;
+    a.compact = d->compact; a.has_agent = d->has_agent;
+    return d4::assemble_tokens(a, static_cast<hipStream_t>(stream));
+}
+int d4_gather_space_double_norm(const float* tokens, float* out, const float* g0, const float* g1, int frames, int S, int first, int dim, int ns,
+                                float eps, void* stream) {
+    D4_REQUIRE(tokens && out && g0 && g1 && frames >= 0 && dim >= 1 && ns >= 1 && first >= 0 && first + ns <= S, "d4_gather_space_double_norm: bad arguments");
+    return d4::gather_space_double_norm(tokens, out, g0, g1, frames, S, first, dim, ns, eps, static_cast<hipStream_t>(stream));
+}
+int d4_euler_step_rows(float* x, int ldx, const float* pred, int ldp, int B, int n_el, float one_minus_t, float dt, void* stream) {
+    D4_REQUIRE(x && pred && B >= 0 && n_el >= 0 && ldx >= n_el && ldp >= n_el, "d4_euler_step_rows: bad arguments");
+    return d4::euler_step(x, ldx, pred, ldp, B, n_el, one_minus_t, dt, static_cast<hipStream_t>(stream));
+}
+int d4_splitk_reduce(const float* part, int S, int M, int N, const float* bias, int silu, float* y, int ldy, void* stream) {
+    D4_REQUIRE(part && y && S >= 1 && M >= 0 && N >= 1 && ldy >= N, "d4_splitk_reduce: bad arguments");
+    return d4::splitk_reduce(part, S, M, N, bias, silu, y, ldy, static_cast<hipStream_t>(stream));
+}
+int d4_mean_tokens(const float* x, float* out, int B, int n, int d, void* stream) {
+    D4_REQUIRE(x && out && B >= 0 && n >= 1 && d >= 1, "d4_mean_tokens: bad arguments");
+    return d4::mean_tokens(x, out, B, n, d, static_cast<hipStream_t>(stream));
+}
+int d4_hl_gauss_scalar_strided(const float* logits, int ld, const float* centers, float* out, int out_stride, int rows, int bins, void* stream) {
+    D4_REQUIRE(logits && centers && out && rows >= 0 && bins >= 1 && ld >= bins && out_stride >= 1, "d4_hl_gauss_scalar_strided: bad arguments");
+    return d4::hl_gauss_scalar(logits, ld, centers, out, out_stride, rows, bins, static_cast<hipStream_t>(stream));
+}
+int d4_fold_rows(const float* W, const float* gamma, float* out, int rows, int K, int ld_out, void* stream) {
+    D4_REQUIRE(W && out && rows >= 0 && K >= 1 && ld_out >= K, "d4_fold_rows: bad arguments");
+    return d4::fold_rows(W, gamma, out, rows, K, ld_out, static_cast<hipStream_t>(stream));
+}
+int d4_swiglu_pack_rows(const float* W, const float* bias, const float* gamma, float* Wp, float* bp, int inner, int inner_pad, int K, void* stream) {
+    D4_REQUIRE(W && bias && gamma && Wp && bp && inner >= 1 && inner_pad >= inner && inner_pad % 32 == 0 && K >= 1, "d4_swiglu_pack_rows: bad arguments (inner_pad %% 32)");
+    return d4::swiglu_pack_rows(W, bias, gamma, Wp, bp, inner, inner_pad, K, static_cast<hipStream_t>(stream));
+}
+int d4_build_latent_input(float* out, const float* hist, const float* ctx_noise, const float* x, int B, int Tq, int n_el, int hist_t_stride, float w, void* stream) {
+    D4_REQUIRE(out && x && B >= 0 && Tq >= 1 && n_el >= 0 && (Tq == 1 || (hist && hist_t_stride >= Tq - 1)), "d4_build_latent_input: bad arguments");
+    return d4::build_latent_input(out, hist, ctx_noise, x, B, Tq, n_el, hist_t_stride, w, static_cast<hipStream_t>(stream));
+}
+int d4_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, void* stream) {
+    D4_REQUIRE(src && dst && rows >= 0 && cols >= 0 && lds >= cols && ldd >= cols, "d4_copy_rows: bad arguments");
+    return d4::copy_rows(src, lds, dst, ldd, rows, cols, static_cast<hipStream_t>(stream));
+}
+int d4_pad_cols(const float* W, float* out, int rows, int cols, int cols_pad, void* stream) {
+    D4_REQUIRE(W && out && rows >= 1 && cols >= 1 && cols_pad >= cols, "d4_pad_cols: bad arguments");
+    return d4::pad_cols(W, out, rows, cols, cols_pad, static_cast<hipStream_t>(stream));
+}
+int d4_video_patches(const float* src, float* dst, int B, int C, int T, int nh, int nw, int ps, int to_patches, void* stream) {
+    D4_REQUIRE(src && dst && B >= 0 && C >= 1 && T >= 1 && nh >= 1 && nw >= 1 && ps >= 1, "d4_video_patches: bad arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return to_patches ? d4::video_to_patches(src, dst, B, C, T, nh, nw, ps, s) : d4::patches_to_video(src, dst, B, C, T, nh, nw, ps, s);
+}
+int d4_cache_transfer(float* cache, float* ext, int Lt, int cache_batch, int B, int S, int H, int Tcap, int frames, int to_ext, int dh, void* stream) {
+    D4_REQUIRE(cache && ext && Lt >= 0 && B >= 0 && cache_batch >= B && S >= 1 && H >= 1 && frames >= 0 && Tcap >= frames && dh >= 1, "d4_cache_transfer: bad arguments");
+    return d4::cache_transfer(cache, ext, Lt, cache_batch, B, S, H, Tcap, frames, to_ext, dh, static_cast<hipStream_t>(stream));
+}
+int d4_cunembed(int op, const float* src, float* dst, int nc, int mtp, int d, void* stream) {
+    D4_REQUIRE(src && dst && nc >= 0 && mtp >= 1 && d >= 1 && (op == 0 || op == 1), "d4_cunembed: op 0 (gather) or 1 (scatter the gradient)");
+    return op == 0 ? d4::cunembed_gather(src, dst, nc, mtp, d, static_cast<hipStream_t>(stream)) : d4::cunembed_scatter_grad(src, dst, nc, mtp, d, static_cast<hipStream_t>(stream));
+}
+int d4_coord_grid(float* out, int nh, int nw, int ld, void* stream) {
+    D4_REQUIRE(out && nh >= 1 && nw >= 1 && ld >= 2, "d4_coord_grid: bad arguments");
+    return d4::coord_grid(out, nh, nw, ld, static_cast<hipStream_t>(stream));
+}
+int d4_pack_tokens(int which, float* tokens, float* compact, const float* pos, const float* img, const float* lat, int frames, int P, int n_lat, int n_total,
+                   int D, void* stream) {
+    D4_REQUIRE(tokens && compact && img && lat && frames >= 0 && P >= 0 && n_lat >= 0 && D >= 1 && (which == 0 || which == 1), "d4_pack_tokens: bad arguments");
+    D4_REQUIRE(which == 1 || (pos && n_total >= n_lat), "d4_pack_tokens: the decoder form needs pos and n_total >= n_lat");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return which == 0 ? d4::decoder_pack_tokens(tokens, compact, pos, img, lat, frames, P, n_lat, n_total, D, s)
+                      : d4::encoder_pack_tokens(tokens, compact, img, lat, frames, P, n_lat, D, s);
+}
+int d4_prep_eval_inputs(int32_t* sig, int64_t* pact, const int64_t* actions_hist, int B, int Tq, int na, int frame_base, int hist_stride, int sig_val, int ctx_sig,
+                        float* pcont, const float* cont_hist, int nc, void* stream) {
+    D4_REQUIRE(sig && B >= 1 && Tq >= 1 && na >= 0 && nc >= 0 && frame_base >= 0 && hist_stride >= frame_base + Tq - 1, "d4_prep_eval_inputs: bad arguments");
+    D4_REQUIRE((na == 0 || pact) && (nc == 0 || pcont), "d4_prep_eval_inputs: pact / pcont missing");
+    return d4::prep_eval_inputs(sig, pact, actions_hist, B, Tq, na, frame_base, hist_stride, sig_val, ctx_sig, static_cast<hipStream_t>(stream), pcont, cont_hist, nc);
+}
+int d4_unary_rows(int op, const float* x, float* y, int64_t n, void* stream) {
+    D4_REQUIRE(x && y && n >= 0 && (op == 0 || op == 1), "d4_unary_rows: op 0 (silu) or 1 (tanh)");
+    return op == 0 ? d4::silu_rows(x, y, n, static_cast<hipStream_t>(stream)) : d4::tanh_rows(x, y, n, static_cast<hipStream_t>(stream));
+}
+
 // Operator-level test entry points of the inference attention cores (attn.hip): each fills the launcher's argument struct and calls it.
 static int small_attn_entry(int wide, const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
                   const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,

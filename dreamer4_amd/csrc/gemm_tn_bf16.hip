@@ -242,3 +242,13 @@ extern "C" int d4_gemm_tn_bf16(const uint16_t* A, int lda, const uint16_t* B, in
                                int slices, void* stream) {
     return d4::gemm_tn_bf16(A, lda, B, ldb, C, ldc, M, N, K, part, part ? (size_t)part_floats : 0, static_cast<hipStream_t>(stream), slices);
 }
+
+// Operator-level test entry points of the bf16 image builders above: the launchers check their own arguments.
+extern "C" int d4_cvt_pad_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int rows, int cols, int cols_pad, void* stream) {
+    D4_REQUIRE(rows >= 0 && cols >= 0 && lds >= cols, "d4_cvt_pad_bf16: bad arguments");
+    return d4::cvt_pad_bf16(src, lds, dst, ldd, rows, cols, cols_pad, static_cast<hipStream_t>(stream));
+}
+extern "C" int d4_cvt_transpose_bf16(const float* src, int lds, uint16_t* dst, int ldd, int rows, int cols, int rows_pad, void* stream) {
+    D4_REQUIRE(rows >= 0 && cols >= 0 && lds >= cols, "d4_cvt_transpose_bf16: bad arguments");
+    return d4::cvt_transpose_bf16(src, lds, dst, ldd, rows, cols, rows_pad, static_cast<hipStream_t>(stream));
+}

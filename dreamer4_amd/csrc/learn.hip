@@ -448,6 +448,17 @@ static inline dim3 grid1d(int64_t n) {
     if (g < 1) g = 1;
     return dim3((unsigned)g);
 }
+static int silu_bwd(const float* dy, const float* z, float* dz, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(silu_bwd_kernel, grid1d(n), dim3(256), 0, s, dy, z, dz, n);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+static int layernorm_silu_bwd(const float* z, int ldz, const float* da, const float* g, const float* b, float* tg, float* tb, float* dz, int rows, int d,
+                              float eps, hipStream_t s) {
+    hipLaunchKernelGGL(layernorm_silu_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, z, ldz, da, g, b, tg, tb, dz, rows, d, eps);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
 
 // dW[M][N] = A^T B over R rows (weight gradient of a head Linear)
 static int gemm_dw_l(d4_engine* e, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int R, hipStream_t s) {
@@ -481,14 +492,12 @@ static int mlp_backward(d4_engine* e, const Mlp& m, const float* save, int R, co
             D4_REQUIRE(m.dg[i] && m.dnb[i], "learner: head parameters were bound without gradient buffers");
             const int ldz = m.ldz(i);
             float* tg = dxh; float* tb = dz; float* dzo = e->l_tmp[3];        // cur (= dy, the incoming gradient) stays intact while it is read
-            hipLaunchKernelGGL(layernorm_silu_bwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, sz[i], ldz, cur, m.g[i], m.nb[i], tg, tb, dzo, R, dout_i, 1e-5f);
-            D4_LAUNCH_CHECK();
+            if ((rc = layernorm_silu_bwd(sz[i], ldz, cur, m.g[i], m.nb[i], tg, tb, dzo, R, dout_i, 1e-5f, s))) return rc;
             if ((rc = colsum(tg, dout_i, R, dout_i, m.dg[i], s))) return rc;
             if ((rc = colsum(tb, dout_i, R, dout_i, m.dnb[i], s))) return rc;
             dzp = dzo; ldd = ldz;
         } else {
-            hipLaunchKernelGGL(silu_bwd_kernel, grid1d((int64_t)R * dout_i), dim3(256), 0, s, cur, sz[i], dz, (int64_t)R * dout_i);
-            D4_LAUNCH_CHECK();
+            if ((rc = silu_bwd(cur, sz[i], dz, (int64_t)R * dout_i, s))) return rc;
             dzp = dz;
         }
         if ((rc = colsum(dzp, ldd, R, dout_i, m.db[i], s))) return rc;
@@ -778,6 +787,34 @@ int d4_ppo_policy_loss(const float* logits, int ld, const int64_t* actions, cons
     D4_HIP(hipMemcpyAsync(loss, scratch + 32, sizeof(float), hipMemcpyDeviceToDevice, s));
     D4_LAUNCH_CHECK();
     return 0;
+}
+
+// Operator-level test entry points of the reductions and the RMSNorm backward: the launchers the learner and the blocks call.
+int d4_colsum(const float* x, int ld, int rows, int cols, float* out, float* scratch, size_t scratch_floats, void* stream) {
+    D4_REQUIRE(x && out && rows >= 1 && cols >= 1 && ld >= cols, "d4_colsum: bad arguments");
+    return d4::colsum(x, ld, rows, cols, out, static_cast<hipStream_t>(stream), scratch, scratch_floats);
+}
+int d4_colsum_batch(int n, const float* const* x, const int32_t* ld, const int32_t* rows, const int32_t* cols, float* const* out, void* stream) {
+    D4_REQUIRE(n >= 1 && n <= d4::ColsumBatch::MAX && x && ld && rows && cols && out, "d4_colsum_batch: 1 .. %d sums", (int)d4::ColsumBatch::MAX);
+    d4::ColsumBatch b;
+    for (int i = 0; i < n; ++i) {
+        D4_REQUIRE(x[i] && out[i] && rows[i] >= 1 && cols[i] >= 1 && ld[i] >= cols[i], "d4_colsum_batch: bad arguments of sum %d", i);
+        b.add(x[i], ld[i], rows[i], cols[i], out[i]);
+    }
+    return d4::colsum_batch(b, static_cast<hipStream_t>(stream));
+}
+int d4_rmsnorm_bwd(const float* x, const float* dxhat, const float* gamma, float* tg, float* dx, int rows, int dim, float eps, void* stream) {
+    D4_REQUIRE(x && dxhat && gamma && tg && rows >= 0 && dim >= 1, "d4_rmsnorm_bwd: bad arguments");
+    return d4::rmsnorm_bwd(x, dxhat, gamma, tg, dx, rows, dim, eps, static_cast<hipStream_t>(stream));
+}
+int d4_layernorm_silu_bwd(const float* z, int ldz, const float* da, const float* g, const float* b, float* tg, float* tb, float* dz, int rows, int dim, float eps,
+                          void* stream) {
+    D4_REQUIRE(z && da && g && b && tg && tb && dz && rows >= 1 && dim >= 1 && ldz >= dim, "d4_layernorm_silu_bwd: bad arguments");
+    return d4::layernorm_silu_bwd(z, ldz, da, g, b, tg, tb, dz, rows, dim, eps, static_cast<hipStream_t>(stream));
+}
+int d4_silu_bwd(const float* dy, const float* z, float* dz, int64_t n, void* stream) {
+    D4_REQUIRE(dy && z && dz && n >= 0, "d4_silu_bwd: bad arguments");
+    return d4::silu_bwd(dy, z, dz, n, static_cast<hipStream_t>(stream));
 }
 
 // clip_grad_norm_(params, max_norm) followed by one AdamW step on a flat parameter group

@@ -610,6 +610,98 @@ int d4_frame_pool_tail(const float* u, const float* wv_t, const float* wo_t, int
 
 int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps,
                         void* stream);
+/* Operator-level entry points of the norm, gather, reduction and token-assembly launchers (test / tooling use).  Each fills the
+ * launcher's arguments (csrc/kernels.h) and calls the launcher the engine, the learner and the blocks call; no kernel has a test-only branch.
+ * Leading dimensions in floats.
+ *   d4_layernorm_rows            y = LayerNorm(x) * g + b (b may be null; biased variance), then SiLU when `silu`; dim <= 4096.
+ *   d4_assemble_tokens           the token rows of `B * Tq` frames from the embedding tables; d4_assemble_desc mirrors AssembleArgs field by field.
+ *   d4_gather_space_double_norm  rows first .. first + ns of every frame of S tokens: RMSNorm(g0) then RMSNorm(g1), out [frames * ns][dim].
+ *   d4_colsum                    out[c] = sum_r x[r][c]; scratch (may be null) of at least 16 * cols floats lets rows >= 8192 take the chunked form.
+ *   d4_colsum_batch              1 .. 4 column sums in one launch, each in the order of d4_colsum without scratch.
+ *   d4_rmsnorm_bwd               tg [rows][dim] = dxhat * x * rstd and, unless dx is null, dx [rows][dim].
+ *   d4_euler_step_rows           d4_euler_step on B rows of n_el elements at leading dimensions ldx / ldp.
+ *   d4_splitk_reduce             y [M][ldy] = act(sum_s part[s][M][N] + bias) (bias may be null; SiLU when `silu`), the slices added in order.
+ *   d4_mean_tokens               out [B][d] = mean over the n tokens of x [B][n][d], added in token order.
+ *   d4_hl_gauss_scalar_strided   d4_hl_gauss_scalar with row r written to out[r * out_stride].
+ *   d4_unary_rows                y[i] = SiLU(x[i]) (op 0) or tanh(x[i]) (op 1), n elements.
+ *   d4_copy_rows, d4_pad_cols, d4_video_patches (to_patches 1: 'b c t (h p1) (w p2) -> (b t h w) (p1 p2 c)', 0: its inverse), d4_cache_transfer (engine
+ *                                cache [Lt][2][cache_batch * S][H][Tcap][dh] <-> [Lt][2][B * S][H][frames][dh]; to_ext 1 reads the cache), d4_cunembed (op 0:
+ *                                prediction head 0 of U [nc][mtp][d][2] as rows [2 nc][d]; op 1: the gradient scattered back, other heads zero),
+ *                                d4_coord_grid (out [nh * nw][ld]: the two linspace(-1, 1) coordinates, remaining columns zero), d4_pack_tokens (which 0: the
+ *                                decoder's rows pos + img | the first n_lat of n_total latent rows, patch rows also to `compact`; which 1: the encoder's rows
+ *                                img | latent tokens, latent rows also to `compact`): the index permutations and copies, arguments as the launchers'.
+ *   d4_fold_rows                 out [rows][ld_out] = W [rows][K] * gamma [K] (gamma may be null: a copy).
+ *   d4_swiglu_pack_rows          proj_in [2 inner][K] (value rows, then gate rows) and its bias -> [2 inner_pad][K] in groups of 32 value rows and their 32 gate
+ *                                rows, gamma folded, zero rows and zero bias entries for the padding; inner_pad % 32 == 0.
+ *   d4_build_latent_input        out [B][Tq][n_el]: frames t < Tq - 1 lerp(hist, ctx_noise, w) read at a frame stride of hist_t_stride (ctx_noise may be
+ *                                null: hist itself), the last frame x [B][n_el].
+ *   d4_prep_eval_inputs          per frame i = b * Tq + t: sig[i] = sig_val at the last frame of a batch, ctx_sig elsewhere; pact [B * Tq][na] / pcont [B * Tq][nc]
+ *                                = the history row (b, frame_base + t - 1) of actions_hist / cont_hist [B][hist_stride][.], -1 / NaN at global frame 0 or
+ *                                without a history (either may be null).
+ *   d4_layernorm_silu_bwd        backward of a = SiLU(LayerNorm(z) * g + b) on z [rows][ldz], da [rows][dim]: tg = dy * zhat, tb = dy ([rows][dim]) and
+ *                                dz [rows][ldz].
+ *   d4_silu_bwd                  dz[i] = dy[i] * SiLU'(z[i]), n elements.
+ *   d4_swiglu                    h [rows][2 inner_pad] (value half | gate half).  bwd 0: out [rows][inner_pad] = value * SiLU(gate); bwd 1: out
+ *                                [rows][2 inner_pad] = the gradient of h given du [rows][inner_pad].  Columns inner .. inner_pad are written as zero.
+ *   d4_multi_copy                up to 10 contiguous copies of n[i] floats in one launch (src[i] null: zero fill); an eleventh segment is refused.
+ *   d4_zero_pad_cols             columns c0 .. c1 of x [rows][ld] set to zero.
+ *   d4_cvt_pad_bf16              dst [rows][ldd] = bf16(src [rows][lds]) (round to nearest even), columns cols .. cols_pad zero; cols_pad % 8 == 0,
+ *                                ldd % 8 == 0, dst 16-byte aligned, anything else is refused.
+ *   d4_cvt_transpose_bf16        dst [cols][ldd], dst[c][r] = bf16(src[r][c]) for r < rows, zero for rows <= r < rows_pad. */
+int d4_layernorm_rows(const float* x, int ldx, const float* g, const float* b, float* y, int ldy, int rows, int dim, float eps, int silu, void* stream);
+typedef struct d4_assemble_desc {
+    float* tokens;
+    const float* space;
+    const float* signal_embed;
+    const float* step_embed;
+    const float* registers;
+    const float* agent_embed;
+    const float* task_embed;
+    const float* action_embed;
+    const float* action_learned;
+    const int32_t* signal_levels;
+    int32_t signal_uniform;
+    const int64_t* prev_actions;
+    const float* prev_cont;
+    const float* cont_embed;
+    const int64_t* tasks;
+    const int32_t* action_offsets;
+    int32_t B, Tq, S, D, ns, nr, na, nc, step_log2;
+    float* compact;
+    int32_t has_agent;
+} d4_assemble_desc;
+int d4_assemble_tokens(const d4_assemble_desc* d, void* stream);
+int d4_gather_space_double_norm(const float* tokens, float* out, const float* g0, const float* g1, int frames, int S, int first, int dim, int ns,
+                                float eps, void* stream);
+int d4_colsum(const float* x, int ld, int rows, int cols, float* out, float* scratch, size_t scratch_floats, void* stream);
+int d4_colsum_batch(int n, const float* const* x, const int32_t* ld, const int32_t* rows, const int32_t* cols, float* const* out, void* stream);
+int d4_rmsnorm_bwd(const float* x, const float* dxhat, const float* gamma, float* tg, float* dx, int rows, int dim, float eps, void* stream);
+int d4_euler_step_rows(float* x, int ldx, const float* pred, int ldp, int B, int n_el, float one_minus_t, float dt, void* stream);
+int d4_splitk_reduce(const float* part, int S, int M, int N, const float* bias, int silu, float* y, int ldy, void* stream);
+int d4_mean_tokens(const float* x, float* out, int B, int n, int d, void* stream);
+int d4_hl_gauss_scalar_strided(const float* logits, int ld, const float* centers, float* out, int out_stride, int rows, int bins, void* stream);
+int d4_unary_rows(int op, const float* x, float* y, int64_t n, void* stream);
+int d4_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, void* stream);
+int d4_fold_rows(const float* W, const float* gamma, float* out, int rows, int K, int ld_out, void* stream);
+int d4_swiglu_pack_rows(const float* W, const float* bias, const float* gamma, float* Wp, float* bp, int inner, int inner_pad, int K, void* stream);
+int d4_build_latent_input(float* out, const float* hist, const float* ctx_noise, const float* x, int B, int Tq, int n_el, int hist_t_stride, float w, void* stream);
+int d4_pad_cols(const float* W, float* out, int rows, int cols, int cols_pad, void* stream);
+int d4_video_patches(const float* src, float* dst, int B, int C, int T, int nh, int nw, int ps, int to_patches, void* stream);
+int d4_cache_transfer(float* cache, float* ext, int Lt, int cache_batch, int B, int S, int H, int Tcap, int frames, int to_ext, int dh, void* stream);
+int d4_cunembed(int op, const float* src, float* dst, int nc, int mtp, int d, void* stream);
+int d4_coord_grid(float* out, int nh, int nw, int ld, void* stream);
+int d4_pack_tokens(int which, float* tokens, float* compact, const float* pos, const float* img, const float* lat, int frames, int P, int n_lat, int n_total,
+                   int D, void* stream);
+int d4_prep_eval_inputs(int32_t* sig, int64_t* pact, const int64_t* actions_hist, int B, int Tq, int na, int frame_base, int hist_stride, int sig_val, int ctx_sig,
+                        float* pcont, const float* cont_hist, int nc, void* stream);
+int d4_layernorm_silu_bwd(const float* z, int ldz, const float* da, const float* g, const float* b, float* tg, float* tb, float* dz, int rows, int dim, float eps,
+                          void* stream);
+int d4_silu_bwd(const float* dy, const float* z, float* dz, int64_t n, void* stream);
+int d4_swiglu(int bwd, const float* h, const float* du, float* out, int rows, int inner, int inner_pad, void* stream);
+int d4_multi_copy(int count, float* const* dst, const float* const* src, const int64_t* n, void* stream);
+int d4_zero_pad_cols(float* x, int rows, int ld, int c0, int c1, void* stream);
+int d4_cvt_pad_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int rows, int cols, int cols_pad, void* stream);
+int d4_cvt_transpose_bf16(const float* src, int lds, uint16_t* dst, int ldd, int rows, int cols, int rows_pad, void* stream);
 int d4_hl_gauss_scalar(const float* logits, int ld, const float* centers, float* out, int rows,
                        int bins, void* stream);
 /* MultiCategorical.sample + log_prob of the sample (dreamer4.py:485-497, 1374-1376, 1422-1423), stateless: Gumbel-max per action type from
