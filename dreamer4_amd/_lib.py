@@ -123,6 +123,7 @@ SYMBOLS = {
     'd4_ff_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
     'd4_train_arith_set': (_I, [_I]),
     'd4_train_wide_set': (_I, [_I]),
+    'd4_train_attn_products_set': (_I, [_I]),
     'd4_train_arith_get': (_I, []),
     'd4_train_scratch_bind': (_I, [_P, C.c_size_t]),
     'd4_ff_bf16_scratch_bytes': (C.c_size_t, [_I] * 3),
@@ -201,6 +202,10 @@ SYMBOLS = {
     'd4_train_xattn_core_plane_floats': (C.c_size_t, [_I] * 4),
     'd4_train_attn_core': (_I, [_P, _I] + [_P] * 7 + [_I] * 4 + [_F, _I, _I, _I, _L, _L, _I, _P, _I, _P, C.c_size_t, _P]),
     'd4_train_xattn_core': (_I, [_P, _I, _P, _I] + [_P] * 6 + [_I] * 6 + [_F, _I, _P, C.c_size_t, _P]),
+    'd4_train_attn_core_bf16_plane_floats': (C.c_size_t, [_I] * 4),
+    'd4_train_xattn_core_bf16_plane_floats': (C.c_size_t, [_I] * 5),
+    'd4_train_attn_core_bf16': (_I, [_P, _I] + [_P] * 7 + [_I] * 4 + [_F, _I, _I, _I, _L, _L, _I, _P, _I, _P, C.c_size_t, _P]),
+    'd4_train_xattn_core_bf16': (_I, [_P, _I, _P, _I] + [_P] * 6 + [_I] * 6 + [_F, _I, _P, C.c_size_t, _P]),
     'd4_rmsnorm_backward': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     'd4_layernorm_rows': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     'd4_assemble_tokens': (_I, [C.POINTER(AssembleDesc), _P]),

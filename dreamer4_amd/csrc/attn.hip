@@ -23,7 +23,7 @@ namespace d4 {
 
 // Which kernel form each launcher of this file picked last: a host-side record for the operator tests (d4_debug_last_form / d4_debug_forms in
 // engine.hip).  A plain store on the host; nothing on the device, no launch depends on it.
-enum { FAM_SMALL_ATTN, FAM_POOL_MIX, FAM_TIME_KV_APPEND, FAM_TIME_ATTN, FAM_WIDE_ATTN, FAM_TRAIN_ATTN, FAM_TRAIN_XATTN, FAM_POOL_MIX_DEEP, FAM_WIDE_ATTN_BF16, FAM_N };
+enum { FAM_SMALL_ATTN, FAM_POOL_MIX, FAM_TIME_KV_APPEND, FAM_TIME_ATTN, FAM_WIDE_ATTN, FAM_TRAIN_ATTN, FAM_TRAIN_XATTN, FAM_POOL_MIX_DEEP, FAM_WIDE_ATTN_BF16, FAM_TRAIN_ATTN_BF16, FAM_TRAIN_XATTN_BF16, FAM_N };
 static const char* const k_small_attn_forms[] = {
     "attn_mfma_kernel<1,1>", "attn_mfma_kernel<1,2>", "attn_mfma_kernel<1,4,2>", "attn_mfma_kernel<2,1>", "attn_mfma_kernel<4,1>",
     "space_attn_kernel<64>", "space_attn_kernel<32>", "space_attn_kernel<16>",
@@ -53,13 +53,19 @@ static const char* const k_pool_mix_deep_forms[] = {                            
     "pool_mix_deep_kernel<1>", "pool_mix_deep_kernel<1,bf16>", "pool_mix_deep_kernel<2>", "pool_mix_deep_kernel<2,bf16>", "pool_mix_deep_kernel<4>",
     "pool_mix_deep_kernel<4,bf16>", nullptr};
 static const char* const k_wide_attn_bf16_forms[] = {"wide_attn_bf16_kernel<16>", "wide_attn_bf16_kernel<32>", "wide_attn_bf16_kernel<64>", nullptr};   // attn_wide_bf16.hip
+// the tiled core with its products on the bf16 matrix pipe (attn_tiled_bf16.hip), recorded through note_train_bf16_form
+static const char* const k_train_attn_bf16_forms[] = {
+    "tiled_bf16<time,64>", "tiled_bf16<time,32>", "tiled_bf16<time,16>", "tiled_bf16<frame,64>", "tiled_bf16<frame,32>", "tiled_bf16<frame,16>", nullptr};
+static const char* const k_train_xattn_bf16_forms[] = {"tiled_bf16<cross,64>", "tiled_bf16<cross,32>", "tiled_bf16<cross,16>", nullptr};
 static const char* const k_family_names[FAM_N] = {"small_attn", "pool_mix", "time_kv_append", "time_attn", "wide_attn", "train_attn", "train_xattn", "pool_mix_deep",
-                                                  "wide_attn_bf16"};
+                                                  "wide_attn_bf16", "train_attn_bf16", "train_xattn_bf16"};
 static const char* const* const k_family_forms[FAM_N] = {k_small_attn_forms, k_pool_mix_forms, k_time_kv_append_forms, k_time_attn_forms, k_wide_attn_forms,
-                                                         k_train_attn_forms, k_train_xattn_forms, k_pool_mix_deep_forms, k_wide_attn_bf16_forms};
-static const char* g_last_form[FAM_N] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+                                                         k_train_attn_forms, k_train_xattn_forms, k_pool_mix_deep_forms, k_wide_attn_bf16_forms,
+                                                         k_train_attn_bf16_forms, k_train_xattn_bf16_forms};
+static const char* g_last_form[FAM_N] = {};
 static inline void note_form(int fam, const char* name) { g_last_form[fam] = name; }
 void note_train_form(bool cross, const char* name) { note_form(cross ? FAM_TRAIN_XATTN : FAM_TRAIN_ATTN, name); }
+void note_train_bf16_form(bool cross, const char* name) { note_form(cross ? FAM_TRAIN_XATTN_BF16 : FAM_TRAIN_ATTN_BF16, name); }
 void note_pool_deep_form(const char* name) { note_form(FAM_POOL_MIX_DEEP, name); }
 static int form_family(const char* family) {
     for (int f = 0; f < FAM_N; ++f) if (family && !strcmp(family, k_family_names[f])) return f;

@@ -51,4 +51,11 @@ int attn_tiled_core(const AttnBwdArgs& a, int dh, float* planes, hipStream_t s);
 // the cross geometry: same outputs as xattn_bwd_kernel (o3; with d_o3 also dprojq, dprojk, dgamma_part)
 int attn_tiled_cross_core(const XAttnArgs& a, int dh, float* planes, hipStream_t s);
 
+// The same two cores with their six products on the bf16 matrix pipe (attn_tiled_bf16.hip; d4_train_attn_products_set(1)): the planes above and,
+// behind them, the bf16 images, which depend on the items per problem (the transposed ones are padded to 32 items per problem)
+size_t attn_tiled_bf16_floats(int groups, int items, int heads, int dh);
+size_t attn_tiled_bf16_cross_floats(int groups, int nq, int nk, int heads, int dh);
+int attn_tiled_bf16_core(const AttnBwdArgs& a, int dh, float* planes, hipStream_t s);
+int attn_tiled_bf16_cross_core(const XAttnArgs& a, int dh, float* planes, hipStream_t s);
+
 }  // namespace d4

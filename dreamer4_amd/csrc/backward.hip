@@ -76,6 +76,10 @@ static std::atomic<int> g_train_arith{0};
 // (attn_tiled.hip) where a side has more than 64; at <= 64 items, and with the switch off, nothing changes (kernels, workspace sizes, refusals)
 static std::atomic<int> g_train_wide{0};
 static bool space_tiled(int tokens) { return g_space_attn_tiled != 0 || (g_train_wide.load() && tokens > 64); }
+// d4_train_attn_products_set(1): wherever a launch takes the tiled core it takes the core's bf16-product form (attn_tiled_bf16.hip),
+// whose bf16 images follow the planes in the workspace; the whole-problem-in-LDS kernels, and everything with the switch off, are unchanged
+static std::atomic<int> g_train_attn_products{0};
+static bool attn_bf16() { return g_train_attn_products.load() != 0; }
 static bool cross_tiled(int nq, int nk) { return g_cross_attn_tiled != 0 || (g_train_wide.load() && (nq > 64 || nk > 64)); }
 struct Bf16Ctx {
     uint16_t *a = nullptr, *b = nullptr, *w = nullptr; size_t act = 0, wgt = 0;      // images: two activation-sized, one weight-sized (elements)
@@ -414,7 +418,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(AttnBwdArgs p) {
 // within-frame geometry above AB_S tokens with d4_train_wide_set(1), either at any size when its test hook asks
 static int attn_core(const AttnBwdArgs& a, int dh, hipStream_t s, float* tiled = nullptr) {
     if (a.F * a.heads == 0) return 0;
-    if (tiled) return attn_tiled_core(a, dh, tiled, s);
+    if (tiled) return attn_bf16() ? attn_tiled_bf16_core(a, dh, tiled, s) : attn_tiled_core(a, dh, tiled, s);
     auto lds_of = [](int cap) { return (size_t)(6 * cap * AB_LD + 2 * cap * (cap + 1) + 4 * cap) * sizeof(float); };
     static DeviceOnce attr_set;
     if (attr_set.need()) {
@@ -544,7 +548,7 @@ __global__ __launch_bounds__(256) void xattn_bwd_kernel(XAttnArgs p) {
 // `tiled`: the planes of the tiled core, given when a side has more than XA_N items with d4_train_wide_set(1) (or the test hook asks)
 static int xattn_core(const XAttnArgs& a, int dh, hipStream_t s, float* tiled = nullptr) {
     if (a.G * a.heads == 0) return 0;
-    if (tiled) return attn_tiled_cross_core(a, dh, tiled, s);
+    if (tiled) return attn_bf16() ? attn_tiled_bf16_cross_core(a, dh, tiled, s) : attn_tiled_cross_core(a, dh, tiled, s);
     const size_t lds = sizeof(float) * ((size_t)(3 * a.nk + 4 * a.nq) * AB_LD + a.nk + a.nq + 256);
     static DeviceOnce attr_set;
     if (attr_set.need()) {
@@ -593,7 +597,7 @@ static AttnWs attn_ws(float* base, int R, int F, int D, int heads, int dh, bool 
     w.gpart = take((size_t)F * hd);
     w.part = take(DW_PART_FLOATS);
     w.wt = take((size_t)w.P * D);
-    if (tiled) w.tiled = take(attn_tiled_floats(R, heads, dh));
+    if (tiled) w.tiled = take(attn_bf16() && F > 0 ? attn_tiled_bf16_floats(F, R / F, heads, dh) : attn_tiled_floats(R, heads, dh));
     w.total = off;
     return w;
 }
@@ -638,6 +642,10 @@ int d4_train_scratch_bind(void* scratch, size_t bytes) { t_scratch.p = scratch; 
 int d4_train_arith_set(int arith) { return g_train_arith.exchange(arith ? 1 : 0); }
 int d4_train_arith_get(void) { return g_train_arith.load(); }
 int d4_train_wide_set(int on) { return g_train_wide.exchange(on ? 1 : 0); }
+int d4_train_attn_products_set(int products) {
+    if (products != 0 && products != 1) { set_error("d4_train_attn_products_set: products %d (0: fp32, 1: bf16)", products); return -1; }
+    return g_train_attn_products.exchange(products);
+}
 
 int d4_ff_forward(const float* x, const float* norm_w, const float* w_in, const float* b_in, const float* w_out, const float* b_out,
                   int rows, int dim, int inner, float* y, float* workspace, size_t workspace_bytes, void* stream) {
@@ -851,7 +859,7 @@ XWs x_ws(float* base, int Rq, int Rk, int G, int D, int Dc, int heads, int dh, b
     w.tg = take((size_t)Rq * D); w.dqn = take((size_t)Rq * D); w.tgc = take((size_t)Rk * Dc); w.dcn = take((size_t)Rk * Dc); w.gpart = take((size_t)G * hd);
     w.part = take(DW_PART_FLOATS);
     w.wt = take((size_t)(w.Pk > w.Pq ? w.Pk : w.Pq) * (D > Dc ? D : Dc));
-    if (tiled) w.tiled = take(attn_tiled_cross_floats(Rq, Rk, heads, dh));
+    if (tiled) w.tiled = take(attn_bf16() && G > 0 ? attn_tiled_bf16_cross_floats(G, Rq / G, Rk / G, heads, dh) : attn_tiled_cross_floats(Rq, Rk, heads, dh));
     w.total = off;
     return w;
 }
@@ -1083,61 +1091,97 @@ size_t d4_train_attn_core_plane_floats(int rows, int heads, int dim_head) {
 size_t d4_train_xattn_core_plane_floats(int q_rows, int k_rows, int heads, int dim_head) {
     return q_rows > 0 && k_rows > 0 && heads > 0 && dim_head > 0 ? attn_tiled_cross_floats(q_rows, k_rows, heads, dim_head) : 0;
 }
+// (the bf16-product form of the tiled core: its images are padded per problem, so the size depends on the items and not on the rows alone)
+size_t d4_train_attn_core_bf16_plane_floats(int groups, int items, int heads, int dim_head) {
+    return groups > 0 && items > 0 && heads > 0 && dim_head > 0 ? attn_tiled_bf16_floats(groups, items, heads, dim_head) : 0;
+}
+size_t d4_train_xattn_core_bf16_plane_floats(int groups, int nq, int nk, int heads, int dim_head) {
+    return groups > 0 && nq > 0 && nk > 0 && heads > 0 && dim_head > 0 ? attn_tiled_bf16_cross_floats(groups, nq, nk, heads, dim_head) : 0;
+}
 
-int d4_train_attn_core(const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3,
-                       float* o3, float* dproj, float* d_rv, float* dgamma_part,
-                       int groups, int items, int heads, int dim_head, float softclamp, int num_special, int belief,
-                       int g_inner, int64_t g_outer_stride, int64_t item_stride, int causal, const float* inv_freq,
-                       int core, float* planes, size_t plane_floats, void* stream) {
-    D4_REQUIRE(proj && gamma && o3, "d4_train_attn_core: null proj, gamma or o3");
-    D4_REQUIRE(!d_o3 || (dproj && dgamma_part), "d4_train_attn_core: d_o3 given with null dproj or dgamma_part");
-    D4_REQUIRE(!d_o3 || !rv || d_rv, "d4_train_attn_core: d_o3 and rv given with null d_rv");
-    D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "d4_train_attn_core: dim_head %d (16, 32 or 64)", dim_head);
-    D4_REQUIRE(groups >= 1 && heads >= 1, "d4_train_attn_core: groups %d, heads %d (at least 1)", groups, heads);
-    D4_REQUIRE(items >= 1, "d4_train_attn_core: items %d (at least 1)", items);
-    D4_REQUIRE(core == 0 || core == 1, "d4_train_attn_core: core %d (0: LDS kernel, 1: tiled)", core);
-    D4_REQUIRE(core != 0 || items <= AB_S, "d4_train_attn_core: items %d with core 0 (max %d)", items, AB_S);
-    D4_REQUIRE(core != 1 || items <= ATT_MAX_FRAMES, "d4_train_attn_core: items %d with core 1 (max %d)", items, ATT_MAX_FRAMES);
+}  // extern "C"
+
+// `who`: the entry's name in its refusals; bf16: the entry of the tiled core's bf16-product form (core 1 only)
+static int train_attn_core_entry(const char* who, bool bf16, const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3,
+                                 float* o3, float* dproj, float* d_rv, float* dgamma_part,
+                                 int groups, int items, int heads, int dim_head, float softclamp, int num_special, int belief,
+                                 int g_inner, int64_t g_outer_stride, int64_t item_stride, int causal, const float* inv_freq,
+                                 int core, float* planes, size_t plane_floats, void* stream) {
+    D4_REQUIRE(proj && gamma && o3, "%s: null proj, gamma or o3", who);
+    D4_REQUIRE(!d_o3 || (dproj && dgamma_part), "%s: d_o3 given with null dproj or dgamma_part", who);
+    D4_REQUIRE(!d_o3 || !rv || d_rv, "%s: d_o3 and rv given with null d_rv", who);
+    D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "%s: dim_head %d (16, 32 or 64)", who, dim_head);
+    D4_REQUIRE(groups >= 1 && heads >= 1, "%s: groups %d, heads %d (at least 1)", who, groups, heads);
+    D4_REQUIRE(items >= 1, "%s: items %d (at least 1)", who, items);
+    D4_REQUIRE(!bf16 || core != 0, "%s: core 0 (the whole-problem-in-LDS kernels have no bf16 form; 1: tiled)", who);
+    D4_REQUIRE(bf16 ? core == 1 : (core == 0 || core == 1), bf16 ? "%s: core %d (1: tiled)" : "%s: core %d (0: LDS kernel, 1: tiled)", who, core);
+    D4_REQUIRE(core != 0 || items <= AB_S, "%s: items %d with core 0 (max %d)", who, items, AB_S);
+    D4_REQUIRE(core != 1 || items <= ATT_MAX_FRAMES, "%s: items %d with core 1 (max %d)", who, items, ATT_MAX_FRAMES);
     const int hd = heads * dim_head, hp4 = (heads + 3) / 4 * 4;
-    D4_REQUIRE(ldp >= 3 * hd + hp4 + heads, "d4_train_attn_core: ldp %d below 3 * heads * dim_head + hp4 + heads = %d", ldp, 3 * hd + hp4 + heads);
-    D4_REQUIRE((causal != 0) == (inv_freq != nullptr), "d4_train_attn_core: causal and inv_freq go together (the time geometry) or are both absent");
-    D4_REQUIRE(num_special >= 0 && num_special <= items, "d4_train_attn_core: num_special %d outside 0..items (%d)", num_special, items);
-    D4_REQUIRE(num_special == 0 || !causal, "d4_train_attn_core: num_special %d with causal", num_special);
-    D4_REQUIRE(g_inner >= 1 && g_outer_stride >= 0 && item_stride >= 1, "d4_train_attn_core: g_inner %d, g_outer_stride %lld, item_stride %lld",
-               g_inner, (long long)g_outer_stride, (long long)item_stride);
+    D4_REQUIRE(ldp >= 3 * hd + hp4 + heads, "%s: ldp %d below 3 * heads * dim_head + hp4 + heads = %d", who, ldp, 3 * hd + hp4 + heads);
+    D4_REQUIRE((causal != 0) == (inv_freq != nullptr), "%s: causal and inv_freq go together (the time geometry) or are both absent", who);
+    D4_REQUIRE(num_special >= 0 && num_special <= items, "%s: num_special %d outside 0..items (%d)", who, num_special, items);
+    D4_REQUIRE(num_special == 0 || !causal, "%s: num_special %d with causal", who, num_special);
+    D4_REQUIRE(g_inner >= 1 && g_outer_stride >= 0 && item_stride >= 1, "%s: g_inner %d, g_outer_stride %lld, item_stride %lld",
+               who, g_inner, (long long)g_outer_stride, (long long)item_stride);
     if (core == 1) {
-        D4_REQUIRE(planes && ((uintptr_t)planes % 16) == 0, "d4_train_attn_core: core 1 needs planes (16-byte aligned)");
-        const size_t need = attn_tiled_floats(groups * items, heads, dim_head);
-        D4_REQUIRE(plane_floats >= need, "d4_train_attn_core: plane_floats %zu below d4_train_attn_core_plane_floats = %zu", plane_floats, need);
+        D4_REQUIRE(planes && ((uintptr_t)planes % 16) == 0, "%s: core 1 needs planes (16-byte aligned)", who);
+        const size_t need = bf16 ? attn_tiled_bf16_floats(groups, items, heads, dim_head) : attn_tiled_floats(groups * items, heads, dim_head);
+        D4_REQUIRE(plane_floats >= need, "%s: plane_floats %zu below %s_plane_floats = %zu", who, plane_floats, who, need);
     }
     AttnBwdArgs a{proj, ldp, rv, gamma, d_o3, o3, dproj, d_rv, dgamma_part, groups, items, heads, hp4, softclamp, num_special, belief ? 1 : 0};
     a.g_inner = g_inner; a.g_outer_stride = g_outer_stride; a.item_stride = item_stride; a.causal = causal ? 1 : 0; a.inv_freq = inv_freq;
-    return attn_core(a, dim_head, static_cast<hipStream_t>(stream), core == 1 ? planes : nullptr);
+    // the form is the entry's, whatever d4_train_attn_products_set says: `planes` was sized and checked for it
+    if (bf16) return attn_tiled_bf16_core(a, dim_head, planes, static_cast<hipStream_t>(stream));
+    if (core == 1) return attn_tiled_core(a, dim_head, planes, static_cast<hipStream_t>(stream));
+    return attn_core(a, dim_head, static_cast<hipStream_t>(stream));
 }
 
-int d4_train_xattn_core(const float* projq, int ldq, const float* projk, int ldk, const float* gamma, const float* d_o3,
-                        float* o3, float* dprojq, float* dprojk, float* dgamma_part,
-                        int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,
-                        int core, float* planes, size_t plane_floats, void* stream) {
-    D4_REQUIRE(projq && projk && gamma && o3, "d4_train_xattn_core: null projq, projk, gamma or o3");
-    D4_REQUIRE(!d_o3 || (dprojq && dprojk && dgamma_part), "d4_train_xattn_core: d_o3 given with null dprojq, dprojk or dgamma_part");
-    D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "d4_train_xattn_core: dim_head %d (16, 32 or 64)", dim_head);
-    D4_REQUIRE(groups >= 1 && heads >= 1, "d4_train_xattn_core: groups %d, heads %d (at least 1)", groups, heads);
-    D4_REQUIRE(nq >= 1, "d4_train_xattn_core: nq %d (at least 1)", nq);
-    D4_REQUIRE(nk >= 1, "d4_train_xattn_core: nk %d (at least 1)", nk);
-    D4_REQUIRE(core == 0 || core == 1, "d4_train_xattn_core: core %d (0: LDS kernel, 1: tiled)", core);
-    D4_REQUIRE(core != 0 || (nq <= XA_N && nk <= XA_N), "d4_train_xattn_core: nq %d / nk %d with core 0 (max %d)", nq, nk, XA_N);
-    D4_REQUIRE(core != 1 || (nq <= ATT_MAX_FRAMES && nk <= ATT_MAX_FRAMES), "d4_train_xattn_core: nq %d / nk %d with core 1 (max %d)", nq, nk, ATT_MAX_FRAMES);
+static int train_xattn_core_entry(const char* who, bool bf16, const float* projq, int ldq, const float* projk, int ldk, const float* gamma, const float* d_o3,
+                                  float* o3, float* dprojq, float* dprojk, float* dgamma_part,
+                                  int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,
+                                  int core, float* planes, size_t plane_floats, void* stream) {
+    D4_REQUIRE(projq && projk && gamma && o3, "%s: null projq, projk, gamma or o3", who);
+    D4_REQUIRE(!d_o3 || (dprojq && dprojk && dgamma_part), "%s: d_o3 given with null dprojq, dprojk or dgamma_part", who);
+    D4_REQUIRE(dim_head == 16 || dim_head == 32 || dim_head == 64, "%s: dim_head %d (16, 32 or 64)", who, dim_head);
+    D4_REQUIRE(groups >= 1 && heads >= 1, "%s: groups %d, heads %d (at least 1)", who, groups, heads);
+    D4_REQUIRE(nq >= 1, "%s: nq %d (at least 1)", who, nq);
+    D4_REQUIRE(nk >= 1, "%s: nk %d (at least 1)", who, nk);
+    D4_REQUIRE(!bf16 || core != 0, "%s: core 0 (the whole-problem-in-LDS kernels have no bf16 form; 1: tiled)", who);
+    D4_REQUIRE(bf16 ? core == 1 : (core == 0 || core == 1), bf16 ? "%s: core %d (1: tiled)" : "%s: core %d (0: LDS kernel, 1: tiled)", who, core);
+    D4_REQUIRE(core != 0 || (nq <= XA_N && nk <= XA_N), "%s: nq %d / nk %d with core 0 (max %d)", who, nq, nk, XA_N);
+    D4_REQUIRE(core != 1 || (nq <= ATT_MAX_FRAMES && nk <= ATT_MAX_FRAMES), "%s: nq %d / nk %d with core 1 (max %d)", who, nq, nk, ATT_MAX_FRAMES);
     const int hd = heads * dim_head;
-    D4_REQUIRE(ldq >= hd + heads, "d4_train_xattn_core: ldq %d below heads * dim_head + heads = %d", ldq, hd + heads);
-    D4_REQUIRE(ldk >= 2 * hd, "d4_train_xattn_core: ldk %d below 2 * heads * dim_head = %d", ldk, 2 * hd);
+    D4_REQUIRE(ldq >= hd + heads, "%s: ldq %d below heads * dim_head + heads = %d", who, ldq, hd + heads);
+    D4_REQUIRE(ldk >= 2 * hd, "%s: ldk %d below 2 * heads * dim_head = %d", who, ldk, 2 * hd);
     if (core == 1) {
-        D4_REQUIRE(planes && ((uintptr_t)planes % 16) == 0, "d4_train_xattn_core: core 1 needs planes (16-byte aligned)");
-        const size_t need = attn_tiled_cross_floats(groups * nq, groups * nk, heads, dim_head);
-        D4_REQUIRE(plane_floats >= need, "d4_train_xattn_core: plane_floats %zu below d4_train_xattn_core_plane_floats = %zu", plane_floats, need);
+        D4_REQUIRE(planes && ((uintptr_t)planes % 16) == 0, "%s: core 1 needs planes (16-byte aligned)", who);
+        const size_t need = bf16 ? attn_tiled_bf16_cross_floats(groups, nq, nk, heads, dim_head) : attn_tiled_cross_floats(groups * nq, groups * nk, heads, dim_head);
+        D4_REQUIRE(plane_floats >= need, "%s: plane_floats %zu below %s_plane_floats = %zu", who, plane_floats, who, need);
     }
     XAttnArgs a{projq, ldq, projk, ldk, gamma, d_o3, o3, dprojq, dprojk, dgamma_part, groups, nq, nk, heads, item_major ? 1 : 0, softclamp};
-    return xattn_core(a, dim_head, static_cast<hipStream_t>(stream), core == 1 ? planes : nullptr);
+    if (bf16) return attn_tiled_bf16_cross_core(a, dim_head, planes, static_cast<hipStream_t>(stream));
+    if (core == 1) return attn_tiled_cross_core(a, dim_head, planes, static_cast<hipStream_t>(stream));
+    return xattn_core(a, dim_head, static_cast<hipStream_t>(stream));
 }
+
+#define D4_CORE_PARAMS const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3, float* o3, float* dproj, float* d_rv,           \
+                       float* dgamma_part, int groups, int items, int heads, int dim_head, float softclamp, int num_special, int belief, int g_inner,     \
+                       int64_t g_outer_stride, int64_t item_stride, int causal, const float* inv_freq, int core, float* planes, size_t plane_floats,      \
+                       void* stream
+#define D4_CORE_ARGS proj, ldp, rv, gamma, d_o3, o3, dproj, d_rv, dgamma_part, groups, items, heads, dim_head, softclamp, num_special, belief, g_inner, \
+                     g_outer_stride, item_stride, causal, inv_freq, core, planes, plane_floats, stream
+#define D4_XCORE_PARAMS const float* projq, int ldq, const float* projk, int ldk, const float* gamma, const float* d_o3, float* o3, float* dprojq,         \
+                        float* dprojk, float* dgamma_part, int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,          \
+                        int core, float* planes, size_t plane_floats, void* stream
+#define D4_XCORE_ARGS projq, ldq, projk, ldk, gamma, d_o3, o3, dprojq, dprojk, dgamma_part, groups, nq, nk, heads, dim_head, item_major, softclamp, core, \
+                      planes, plane_floats, stream
+
+extern "C" {
+
+int d4_train_attn_core(D4_CORE_PARAMS) { return train_attn_core_entry("d4_train_attn_core", false, D4_CORE_ARGS); }
+int d4_train_attn_core_bf16(D4_CORE_PARAMS) { return train_attn_core_entry("d4_train_attn_core_bf16", true, D4_CORE_ARGS); }
+int d4_train_xattn_core(D4_XCORE_PARAMS) { return train_xattn_core_entry("d4_train_xattn_core", false, D4_XCORE_ARGS); }
+int d4_train_xattn_core_bf16(D4_XCORE_PARAMS) { return train_xattn_core_entry("d4_train_xattn_core_bf16", true, D4_XCORE_ARGS); }
 
 }  // extern "C"

@@ -235,6 +235,7 @@ int time_attn_append(const TimeAttnArgs& p, hipStream_t stream); // both; ONE la
 // (families "train_attn", "train_xattn": tests/test_gpu_train_cores.py) through note_train_form, where they choose the launch; the chunked pool mix
 // (family "pool_mix_deep": tests/test_gpu_deep_pool.py) through note_pool_deep_form.
 void note_train_form(bool cross, const char* name);
+void note_train_bf16_form(bool cross, const char* name);      // families "train_attn_bf16", "train_xattn_bf16": the tiled core on the bf16 matrix pipe
 const char* attn_last_form(const char* family);                  // nullptr: unknown family or nothing launched yet
 int attn_form_name(const char* family, int i, const char** name); // number of forms of the family (-1: unknown); *name = form i or nullptr
 

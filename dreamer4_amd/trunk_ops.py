@@ -57,6 +57,7 @@ def via_dispatcher():
 
 
 ARITHS = ('fp32', 'bf16')
+ATTN_PRODUCTS = ('fp32', 'bf16')
 
 
 def arith_id(arith):
@@ -66,34 +67,47 @@ def arith_id(arith):
     return ARITHS.index(arith)
 
 
+def products_id(attn_products):
+    """'fp32' -> 0, 'bf16' -> 1 (the argument of d4_train_attn_products_set); anything else is a ValueError."""
+    if attn_products not in ATTN_PRODUCTS:
+        raise ValueError(f"attn_products must be one of {ATTN_PRODUCTS}, got {attn_products!r}")
+    return ATTN_PRODUCTS.index(attn_products)
+
+
 class _arith_mode:
     """The block arithmetic of libd4hip is process-wide: every forward / backward call of a block sets its own immediately before the C call
     (autograd runs the backward on another thread, and a saved workspace must meet the arithmetic it was written in) and puts the previous
     one back.  In bf16 mode the call also gets a scratch for its bf16 operand images (`scratch_bytes`), bound to this thread for the call and
     released with it: nothing of it is kept between the forward and the backward.
     `wide` (None: leave it alone) is the other process-wide switch, d4_train_wide_set, handled the same way for the same reason: the
-    workspace size query, the forward and the backward of a space / cross block must all meet the setting the block was called with."""
-    def __init__(self, lib, a, scratch_bytes=0, device=None, wide=None):
-        self.lib, self.a, self.wide = lib, a, wide
+    workspace size query, the forward and the backward of a space / cross block must all meet the setting the block was called with.
+    `products` (None: leave it alone) is the third, d4_train_attn_products_set (the products of the tiled attention core: 0 fp32, 1 bf16,
+    DESIGN.md 18), handled like `wide`: it changes the workspace size wherever the block takes the tiled core."""
+    def __init__(self, lib, a, scratch_bytes=0, device=None, wide=None, products=None):
+        self.lib, self.a, self.wide, self.products = lib, a, wide, products
         self.scratch = _workspace(scratch_bytes, device) if a else None
 
     def __enter__(self):
         self.prev = self.lib.d4_train_arith_set(self.a)
         if self.wide is not None:
             self.prev_wide = self.lib.d4_train_wide_set(self.wide)
+        if self.products is not None:
+            self.prev_products = self.lib.d4_train_attn_products_set(self.products)
         if self.scratch is not None:
             self.lib.d4_train_scratch_bind(self.scratch[1], self.scratch[0].numel() - 256)
 
     def __exit__(self, *exc):
         if self.scratch is not None:
             self.lib.d4_train_scratch_bind(None, 0)
+        if self.products is not None:
+            self.lib.d4_train_attn_products_set(self.prev_products)
         if self.wide is not None:
             self.lib.d4_train_wide_set(self.prev_wide)
         self.lib.d4_train_arith_set(self.prev)
         return False
 
 
-def _no_dispatcher(arith, wide=False):
+def _no_dispatcher(arith, wide=False, attn_products='fp32'):
     if arith != 'fp32':
         arith_id(arith)
         raise NotImplementedError(f"D4_TRUNK_DISPATCHER=1 does not carry arith={arith!r}: the torch.ops.d4hip block registrations are fp32 only "
@@ -101,6 +115,10 @@ def _no_dispatcher(arith, wide=False):
     if wide:
         raise NotImplementedError("D4_TRUNK_DISPATCHER=1 does not carry wide=True: the torch.ops.d4hip block registrations stop at 64 items per "
                                   "group (run wide frames on the default autograd.Function route)")
+    if attn_products != 'fp32':
+        products_id(attn_products)
+        raise NotImplementedError(f"D4_TRUNK_DISPATCHER=1 does not carry attn_products={attn_products!r}: the torch.ops.d4hip block registrations "
+                                  "run the attention cores' fp32 products only (use the default autograd.Function route)")
 
 
 def _workspace(nbytes, device):
@@ -150,7 +168,7 @@ class _FeedForward(torch.autograd.Function):
 
 class _SpaceAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, softclamp, num_special, belief, arith=0, wide=0):
+    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, softclamp, num_special, belief, arith=0, wide=0, products=0):
         x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma = _prep(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma)
         assert x.ndim == 3, 'x must be (frames, tokens, dim)'
         F_, S, D = x.shape
@@ -159,13 +177,13 @@ class _SpaceAttention(torch.autograd.Function):
         assert rv is None or rv.shape == (F_, S, heads, dh)
         lib = _lib.load()
         y = torch.empty_like(x)
-        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if arith else 0, x.device, wide):
+        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if arith else 0, x.device, wide, products):
             nbytes = lib.d4_attn_workspace_bytes(F_, S, D, heads, dh)
             ws, wp = _workspace(nbytes, x.device)
             _lib.check(lib.d4_space_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
                                                  _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh,
                                                  float(softclamp or 0.), int(num_special), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
-        ctx.arith, ctx.wide = arith, wide
+        ctx.arith, ctx.wide, ctx.products = arith, wide, products
         ctx.save_for_backward(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma)
         ctx.cfg = (float(softclamp or 0.), int(num_special), int(bool(belief)))
         ctx.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx.needs_input_grad) else None
@@ -181,7 +199,7 @@ class _SpaceAttention(torch.autograd.Function):
         e = torch.empty_like
         dx, dn, dq, dk, dv, do, dg, dgam = e(x), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         drv, dwm, dbm = (e(rv), e(wm), e(bm)) if rv is not None else (None, None, None)
-        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if ctx.arith else 0, x.device, ctx.wide):
+        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(F_ * S, D, heads, dh) if ctx.arith else 0, x.device, ctx.wide, ctx.products):
             if ctx.fwd_ws is not None:
                 (ws, wp, nbytes), fn = ctx.fwd_ws, lib.d4_space_attn_backward_saved
             else:
@@ -192,12 +210,12 @@ class _SpaceAttention(torch.autograd.Function):
                 _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), F_, S, D, heads, dh, *ctx.cfg,
                 _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
                 _lib.ptr(dgam), wp, nbytes, _stream(x)))
-        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None, None
+        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None, None, None
 
 
 class _TimeAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq, softclamp, belief, arith=0):
+    def forward(ctx, x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq, softclamp, belief, arith=0, products=0):
         x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq = _prep(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq)
         assert x.ndim == 4, 'x must be (batch, frames, tokens, dim)'
         B, T, S, D = x.shape
@@ -205,14 +223,14 @@ class _TimeAttention(torch.autograd.Function):
         assert wq.shape == (heads * dh, D) and wo.shape == (D, heads * dh) and wg.shape == (heads, D) and inv_freq.shape == (dh // 2,)
         assert rv is None or rv.shape == (B, T, S, heads, dh)
         lib = _lib.load()
-        nbytes = lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
-        ws, wp = _workspace(nbytes, x.device)
         y = torch.empty_like(x)
-        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(B * T * S, D, heads, dh) if arith else 0, x.device):
+        with _arith_mode(lib, arith, lib.d4_attn_bf16_scratch_bytes(B * T * S, D, heads, dh) if arith else 0, x.device, None, products):
+            nbytes = lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
+            ws, wp = _workspace(nbytes, x.device)
             _lib.check(lib.d4_time_attn_forward(_lib.ptr(x), _lib.ptr(rv), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo),
                                                 _lib.ptr(wg), _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), _lib.ptr(inv_freq), B, T, S, D, heads, dh,
                                                 float(softclamp or 0.), int(bool(belief)), _lib.ptr(y), wp, nbytes, _stream(x)))
-        ctx.arith = arith
+        ctx.arith, ctx.products = arith, products
         ctx.save_for_backward(x, rv, norm_w, wq, wk, wv, wo, wg, wm, bm, gamma, inv_freq)
         ctx.cfg = (float(softclamp or 0.), int(bool(belief)))
         ctx.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx.needs_input_grad) else None
@@ -225,26 +243,26 @@ class _TimeAttention(torch.autograd.Function):
         B, T, S, D = x.shape
         heads, dh = gamma.shape
         lib = _lib.load()
-        if ctx.fwd_ws is not None:
-            (ws, wp, nbytes), fn = ctx.fwd_ws, lib.d4_time_attn_backward_saved
-        else:
-            nbytes = lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
-            (ws, wp), fn = _workspace(nbytes, x.device), lib.d4_time_attn_backward
         e = torch.empty_like
         dx, dn, dq, dk, dv, do, dg, dgam = e(x), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         drv, dwm, dbm = (e(rv), e(wm), e(bm)) if rv is not None else (None, None, None)
-        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(B * T * S, D, heads, dh) if ctx.arith else 0, x.device):
+        with _arith_mode(lib, ctx.arith, lib.d4_attn_bf16_scratch_bytes(B * T * S, D, heads, dh) if ctx.arith else 0, x.device, None, ctx.products):
+            if ctx.fwd_ws is not None:
+                (ws, wp, nbytes), fn = ctx.fwd_ws, lib.d4_time_attn_backward_saved
+            else:
+                nbytes = lib.d4_time_attn_workspace_bytes(B, T, S, D, heads, dh)
+                (ws, wp), fn = _workspace(nbytes, x.device), lib.d4_time_attn_backward
             _lib.check(fn(
                 _lib.ptr(x), _lib.ptr(rv), _lib.ptr(dy), _lib.ptr(norm_w), _lib.ptr(wq), _lib.ptr(wk), _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg),
                 _lib.ptr(wm), _lib.ptr(bm), _lib.ptr(gamma), _lib.ptr(inv_freq), B, T, S, D, heads, dh, *ctx.cfg,
                 _lib.ptr(dx), _lib.ptr(drv), _lib.ptr(dn), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dwm), _lib.ptr(dbm),
                 _lib.ptr(dgam), wp, nbytes, _stream(x)))
-        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None
+        return dx, drv, dn, dq, dk, dv, do, dg, dwm, dbm, dgam, None, None, None, None, None
 
 
 class _CrossAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx_, q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma, item_major, softclamp, arith=0, wide=0):
+    def forward(ctx_, q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma, item_major, softclamp, arith=0, wide=0, products=0):
         q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma = _prep(q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma)
         assert q_tokens.ndim == 3 and context.ndim == 3
         G, nq, D = q_tokens.shape
@@ -254,13 +272,13 @@ class _CrossAttention(torch.autograd.Function):
         assert wq.shape == (heads * dh, D) and wk.shape == (heads * dh, Dc) and wv.shape == (heads * dh, Dc) and wo.shape == (D, heads * dh)
         lib = _lib.load()
         y = torch.empty_like(q_tokens)
-        with _arith_mode(lib, arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if arith else 0, q_tokens.device, wide):
+        with _arith_mode(lib, arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if arith else 0, q_tokens.device, wide, products):
             nbytes = lib.d4_cross_attn_workspace_bytes(G, nq, nk, D, Dc, heads, dh)
             ws, wp = _workspace(nbytes, q_tokens.device)
             _lib.check(lib.d4_cross_attn_forward(_lib.ptr(q_tokens), _lib.ptr(context), _lib.ptr(norm_w), _lib.ptr(norm_ctx_w), _lib.ptr(wq), _lib.ptr(wk),
                                                  _lib.ptr(wv), _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, int(bool(item_major)), D, Dc, heads, dh,
                                                  float(softclamp or 0.), _lib.ptr(y), wp, nbytes, _stream(q_tokens)))
-        ctx_.arith, ctx_.wide = arith, wide
+        ctx_.arith, ctx_.wide, ctx_.products = arith, wide, products
         ctx_.save_for_backward(q_tokens, context, norm_w, norm_ctx_w, wq, wk, wv, wo, wg, gamma)
         ctx_.cfg = (G, nq, nk, int(bool(item_major)), D, Dc, heads, dh, float(softclamp or 0.))
         ctx_.fwd_ws = (ws, wp, nbytes) if save_forward_workspace() and any(ctx_.needs_input_grad) else None
@@ -275,7 +293,7 @@ class _CrossAttention(torch.autograd.Function):
         e = torch.empty_like
         dq_t, dc, dn, dq, dk, dv, do, dg, dgam = e(q_tokens), e(context), e(norm_w), e(wq), e(wk), e(wv), e(wo), e(wg), e(gamma)
         dnc = e(norm_ctx_w) if norm_ctx_w is not None else None
-        with _arith_mode(lib, ctx_.arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if ctx_.arith else 0, q_tokens.device, ctx_.wide):
+        with _arith_mode(lib, ctx_.arith, lib.d4_cross_attn_bf16_scratch_bytes(G, nq, nk, D, Dc, heads, dh) if ctx_.arith else 0, q_tokens.device, ctx_.wide, ctx_.products):
             if ctx_.fwd_ws is not None:
                 (ws, wp, nbytes), fn = ctx_.fwd_ws, lib.d4_cross_attn_backward_saved
             else:
@@ -286,7 +304,7 @@ class _CrossAttention(torch.autograd.Function):
                 _lib.ptr(wo), _lib.ptr(wg), _lib.ptr(gamma), G, nq, nk, item_major, D, Dc, heads, dh, softclamp,
                 _lib.ptr(dq_t), _lib.ptr(dc), _lib.ptr(dn), _lib.ptr(dnc), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(do), _lib.ptr(dg), _lib.ptr(dgam),
                 wp, nbytes, _stream(q_tokens)))
-        return dq_t, dc, dn, dnc, dq, dk, dv, do, dg, dgam, None, None, None, None
+        return dq_t, dc, dn, dnc, dq, dk, dv, do, dg, dgam, None, None, None, None, None
 
 
 def _dev(*ts):
@@ -306,49 +324,55 @@ def feedforward(x, norm_weight, proj_in_weight, proj_in_bias, proj_out_weight, p
 
 
 def space_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, *, residual_values=None, mix_weight=None, mix_bias=None,
-                    softclamp_value=50., num_special=1, belief=True, arith='fp32', wide=False):
+                    softclamp_value=50., num_special=1, belief=True, arith='fp32', wide=False, attn_products='fp32'):
     """Attention.forward (dreamer4.py:1968-2075), self attention within each frame: x (frames, tokens, dim) -> (frames, tokens, dim).
     `residual_values` (frames, tokens, heads, dim_head) with `mix_weight` / `mix_bias` = to_learned_value_residual_mix.0 (every layer
     but the first); `num_special` trailing tokens are hidden from ordinary queries (dreamer4.py:1769-1783).  tokens <= 64; with `wide=True`
     <= 1024 (above 64 the tiled core of csrc/attn_tiled.hip; at <= 64 the same kernel and the same bits as without).
-    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_space, not with `wide`.)"""
+    `attn_products='bf16'`: where the block takes the tiled core, the core's products run on the bf16 matrix pipe.
+    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_space, not with `wide` or bf16 products.)"""
+    products_id(attn_products)
     _dev(x)
     assert x.ndim == 3, 'x must be (frames, tokens, dim)'
     if not via_dispatcher():
         return _SpaceAttention.apply(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma,
-                                     softclamp_value, num_special, belief, arith_id(arith), int(bool(wide)))
-    _no_dispatcher(arith, wide)
+                                     softclamp_value, num_special, belief, arith_id(arith), int(bool(wide)), products_id(attn_products))
+    _no_dispatcher(arith, wide, attn_products)
     return torch.ops.d4hip.attn_block_space(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma,
                                             float(softclamp_value or 0.), int(num_special), bool(belief))[0]
 
 
 def time_attention(x, norm_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, inv_freq, *, residual_values=None, mix_weight=None,
-                   mix_bias=None, softclamp_value=50., belief=True, arith='fp32'):
+                   mix_bias=None, softclamp_value=50., belief=True, arith='fp32', attn_products='fp32'):
     """The trunk's time layers (dreamer4.py:3176-3215): causal attention along time for every token column, rotary positions
     (`inv_freq` = time_rotary.inv_freq), no KV cache (the training form).  x (batch, frames, tokens, dim), frames <= 1024
-    (above 64 frames the tiled core of csrc/attn_tiled.hip: workspace linear in the frames); `residual_values` (batch, frames, tokens, heads, dim_head).  (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_time.)"""
+    (above 64 frames the tiled core of csrc/attn_tiled.hip: workspace linear in the frames; with `attn_products='bf16'` its products run on
+    the bf16 matrix pipe); `residual_values` (batch, frames, tokens, heads, dim_head).  (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_time.)"""
+    products_id(attn_products)
     _dev(x)
     assert x.ndim == 4, 'x must be (batch, frames, tokens, dim)'
     if not via_dispatcher():
         return _TimeAttention.apply(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma, inv_freq,
-                                    softclamp_value, belief, arith_id(arith))
-    _no_dispatcher(arith)
+                                    softclamp_value, belief, arith_id(arith), products_id(attn_products))
+    _no_dispatcher(arith, False, attn_products)
     return torch.ops.d4hip.attn_block_time(x, residual_values, norm_weight, to_q, to_k, to_v, to_out, to_gates, mix_weight, mix_bias, k_gamma, inv_freq,
                                            float(softclamp_value or 0.), bool(belief))[0]
 
 
 def cross_attention(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma, *,
-                    context_item_major=False, softclamp_value=None, arith='fp32', wide=False):
+                    context_item_major=False, softclamp_value=None, arith='fp32', wide=False, attn_products='fp32'):
     """Attention.forward with a context (dreamer4.py:1968-2075): q_tokens (groups, nq, dim); context (groups, nk, dim_ctx), or
     (nk, groups, dim_ctx) with `context_item_major` (the stack of layer hiddens of the AttentionPool).  nq, nk <= 64; with `wide=True`
     nq, nk <= 1024 (the tiled core of csrc/attn_tiled.hip as soon as either exceeds 64; otherwise the same kernel and bits).
-    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_cross, not with `wide`.)"""
+    `attn_products='bf16'`: the tiled core's products on the bf16 matrix pipe.
+    (D4_TRUNK_DISPATCHER=1: torch.ops.d4hip.attn_block_cross, not with `wide` or bf16 products.)"""
+    products_id(attn_products)
     _dev(q_tokens)
     assert q_tokens.ndim == 3 and context.ndim == 3
     if not via_dispatcher():
         return _CrossAttention.apply(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
-                                     context_item_major, softclamp_value, arith_id(arith), int(bool(wide)))
-    _no_dispatcher(arith, wide)
+                                     context_item_major, softclamp_value, arith_id(arith), int(bool(wide)), products_id(attn_products))
+    _no_dispatcher(arith, wide, attn_products)
     return torch.ops.d4hip.attn_block_cross(q_tokens, context, norm_weight, norm_context_weight, to_q, to_k, to_v, to_out, to_gates, k_gamma,
                                             bool(context_item_major), float(softclamp_value or 0.))[0]
 
@@ -370,7 +394,7 @@ def _ff(W, pre, x, arith='fp32'):
                        arith=arith)
 
 
-def _pool(W, pre, x, hiddens, arith='fp32', wide=False):
+def _pool(W, pre, x, hiddens, arith='fp32', wide=False, attn_products='fp32'):
     """Residual(AttentionPool) (dreamer4.py:2143-2177 + 1869): one query per token over the stack of layer hiddens.
     hiddens: a list of layer hiddens, or the stack itself (L, rows, D) — `transformer` grows ONE stack by concatenation, so that in the
     backward every pool's context gradient meets the previous pools' as one (L, rows, D) sum instead of L per-hidden sums per pool."""
@@ -378,18 +402,20 @@ def _pool(W, pre, x, hiddens, arith='fp32', wide=False):
     ctx = hiddens if torch.is_tensor(hiddens) else torch.stack([h.reshape(-1, shape[-1]) for h in hiddens], dim=0)     # (L, rows, D): item major
     p = pre + 'fn.attn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, p)
-    out = cross_attention(x.reshape(-1, 1, shape[-1]), ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, context_item_major=True, arith=arith, wide=wide)
+    out = cross_attention(x.reshape(-1, 1, shape[-1]), ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, context_item_major=True, arith=arith, wide=wide, attn_products=attn_products)
     return x + out.reshape(shape)
 
 
-def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='transformer.', arith='fp32', wide=False):
+def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='transformer.', arith='fp32', wide=False, attn_products='fp32'):
     """AxialSpaceTimeTransformer.forward (dreamer4.py:2927-3267, defaults: value residual, attention pools, final special cross
     attention; final RMSNorm when the weights hold one) for training: no KV cache, every block a HIP forward + backward operator;
     only the residual adds, reshapes and the two bare RMSNorm + Linear pieces (value residual projection, final norm) are torch ops.
     W: the reference's trunk parameters by state_dict key (with the prefix `pre`); tokens (batch, frames, tokens, dim); is_time: per
     layer.  Differentiable with respect to tokens and every parameter.  `wide=True`: up to 1024 tokens per frame and pooled hiddens (space
-    blocks, attention pools and the final special cross attention take `wide`)."""
+    blocks, attention pools and the final special cross attention take `wide`).  `attn_products='bf16'`: every attention
+    that takes the tiled core (time layers above 64 frames; with `wide`, the others above 64 items) runs its products on the bf16 pipe."""
     from torch.nn import functional as F
+    products_id(attn_products)
     b, t, s, d = tokens.shape
     gamma0 = W[pre + 'layers.0.2.fn.k_heads_rmsnorm.gamma']
     h, dh = gamma0.shape
@@ -404,33 +430,34 @@ def transformer(W, tokens, *, is_time, softclamp_value=50., num_special=1, pre='
         mw, mb = W[ap + 'to_learned_value_residual_mix.0.weight'], W[ap + 'to_learned_value_residual_mix.0.bias']
         if tl:
             out = time_attention(tokens, nw, wq, wk, wv, wo, wg, gam, W[pre + 'time_rotary.inv_freq'], residual_values=vres, mix_weight=mw,
-                                 mix_bias=mb, softclamp_value=softclamp_value, arith=arith)
+                                 mix_bias=mb, softclamp_value=softclamp_value, arith=arith, attn_products=attn_products)
         else:
             out = space_attention(tokens.reshape(b * t, s, d), nw, wq, wk, wv, wo, wg, gam, residual_values=vres.reshape(b * t, s, h, dh),
-                                  mix_weight=mw, mix_bias=mb, softclamp_value=softclamp_value, num_special=num_special, arith=arith, wide=wide).reshape(b, t, s, d)
+                                  mix_weight=mw, mix_bias=mb, softclamp_value=softclamp_value, num_special=num_special, arith=arith, wide=wide,
+                                  attn_products=attn_products).reshape(b, t, s, d)
         tokens = tokens + out
         after_attn = tokens
         tokens = tokens + _ff(W, f'{pre}layers.{i}.3.fn.', tokens, arith)
         hiddens = torch.cat((hiddens, after_attn.reshape(1, -1, d), tokens.reshape(1, -1, d)), dim=0)
         if i != depth - 1:
-            tokens = _pool(W, f'{pre}attn_pools.{i}.', tokens, hiddens, arith, wide)
+            tokens = _pool(W, f'{pre}attn_pools.{i}.', tokens, hiddens, arith, wide, attn_products)
     # the special tokens cross-attend the ordinary tokens of their frame, then their own feedforward   dreamer4.py:3227-3238
     non_special, special = tokens[:, :, :-num_special], tokens[:, :, -num_special:]
     cp = pre + 'final_special_cross_attn.fn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, cp)
     out = cross_attention(special.reshape(b * t, num_special, d), non_special.reshape(b * t, s - num_special, d), nw, W[cp + 'norm_context.weight'],
-                          wq, wk, wv, wo, wg, gam, arith=arith, wide=wide)
+                          wq, wk, wv, wo, wg, gam, arith=arith, wide=wide, attn_products=attn_products)
     special = special + out.reshape(b, t, num_special, d)
     special = special + _ff(W, pre + 'final_special_ff.fn.', special, arith)
     tokens = torch.cat((non_special, special), dim=2)
-    tokens = _pool(W, pre + 'final_attn_pool.', tokens, hiddens, arith, wide)
+    tokens = _pool(W, pre + 'final_attn_pool.', tokens, hiddens, arith, wide, attn_products)
     if pre + 'final_norm.weight' in W:
         tokens = torch.ops.d4hip.rmsnorm(tokens, W[pre + 'final_norm.weight'], eps)
     return tokens
 
 
 # ------------------------------------------------------------------------------------------------ the dynamics model, training form
-def _lq_pool(W, pre, x, arith='fp32', wide=False):
+def _lq_pool(W, pre, x, arith='fp32', wide=False, attn_products='fp32'):
     """LearnedQueriesAttentionPool (dreamer4.py:2179-2210): x (..., n, d_ctx) -> (..., num_queries, dim)."""
     lead = x.shape[:-2]
     ctx = x.reshape(-1, *x.shape[-2:])
@@ -438,13 +465,13 @@ def _lq_pool(W, pre, x, arith='fp32', wide=False):
     q = queries[None].expand(ctx.shape[0], -1, -1)
     p = pre + 'attn.'
     nw, wq, wk, wv, wo, wg, gam = _attn_w(W, p)
-    out = cross_attention(q, ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, arith=arith, wide=wide)
+    out = cross_attention(q, ctx, nw, W[p + 'norm_context.weight'], wq, wk, wv, wo, wg, gam, arith=arith, wide=wide, attn_products=attn_products)
     return out.reshape(*lead, *out.shape[-2:])
 
 
 def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *, is_time, num_spatial_tokens, num_register_tokens,
                            num_discrete_actions=(), discrete_actions=None, continuous_actions=None, tasks=None, softclamp_value=50., arith='fp32',
-                           wide=False):
+                           wide=False, attn_products='fp32'):
     """DynamicsWorldModel's `get_prediction` (dreamer4.py:7156-7287) for training: noised latents (b, t, n, dl), signal_levels (b, t),
     step_sizes_log2 (b,) -> (latent prediction (b, t, n, dl), agent embedding (b, t, dim)).  Token packing, embeddings and the bare
     RMSNorm + Linear of the latent head are torch ops; the trunk and the learned-query pools are the HIP forward + backward blocks.
@@ -459,7 +486,7 @@ def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *,
     if num_spatial_tokens == n:
         space = torch.ops.d4hip.linear(noised_latents, W['latents_to_spatial_tokens.weight'], W['latents_to_spatial_tokens.bias'], None, 0, 0.)
     else:
-        space = _lq_pool(W, 'latents_to_spatial_tokens.', noised_latents, arith, wide)
+        space = _lq_pool(W, 'latents_to_spatial_tokens.', noised_latents, arith, wide, attn_products)
     sig = W['signal_levels_embed.weight'][signal_levels]
     stp = W['step_size_embed.weight'][step_sizes_log2][:, None].expand(b, t, -1)
     flow_tok = torch.cat((sig, stp), dim=-1)[:, :, None]
@@ -486,11 +513,12 @@ def world_model_prediction(W, noised_latents, signal_levels, step_sizes_log2, *,
             act = F.pad(emb, (0, 0, 1, 0), value=0.)
         parts.append(act[:, :, None])
     parts.append(agent)
-    tokens = transformer(W, torch.cat(parts, dim=2), is_time=is_time, softclamp_value=softclamp_value, arith=arith, wide=wide)
+    tokens = transformer(W, torch.cat(parts, dim=2), is_time=is_time, softclamp_value=softclamp_value, arith=arith, wide=wide,
+                         attn_products=attn_products)
     space_out, agent_embed = tokens[:, :, 1:1 + num_spatial_tokens], tokens[:, :, -1]
     x = torch.ops.d4hip.rmsnorm(space_out, W['to_latent_pred.0.weight'], eps)
     if num_spatial_tokens != n:
-        x = _lq_pool(W, 'to_latent_pred.1.', x, arith, wide)
+        x = _lq_pool(W, 'to_latent_pred.1.', x, arith, wide, attn_products)
     return torch.ops.d4hip.linear(x, W['to_latent_pred.2.weight'], None, None, 0, 0.), agent_embed
 
 
@@ -512,7 +540,7 @@ def dynamics_flow_losses(W, latents, noise, signal_levels, step_sizes_log2, shor
     """The flow and shortcut-consistency losses of the dynamics training forward (dreamer4.py:6990-7003, 7335-7431; x-space prediction,
     ramp loss weight, no proprio / variable lengths / loss normalisers: the reference defaults).  `model`: the keyword arguments of
     `world_model_prediction` (among them `arith='fp32' | 'bf16'`, the arithmetic of the blocks' Linears in all three predictions, and `wide=True`
-    for more than 64 tokens per frame, latents or pooled hiddens).  Returns (flow_loss, shortcut_loss[, agent_embed of the main prediction]); backward runs through the HIP blocks."""
+    for more than 64 tokens per frame, latents or pooled hiddens, and `attn_products='fp32' | 'bf16'`, the products of the tiled attention core).  Returns (flow_loss, shortcut_loss[, agent_embed of the main prediction]); backward runs through the HIP blocks."""
     from torch.nn import functional as F
     times = signal_levels.float() / max_steps
     tt = times[:, :, None, None]

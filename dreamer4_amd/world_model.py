@@ -175,6 +175,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         matmul_dtype='fp32',
         train_matmul_dtype='fp32',
         train_wide_frames=False,
+        train_attn_products='fp32',
         wide_frames=False,
         attn_products='fp32',
         use_loss_normalization=False,
@@ -226,6 +227,16 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         # True: up to 1024 of each, on the tiled attention core (csrc/attn_tiled.hip) wherever a problem side exceeds 64 — smaller problems
         # run the same kernels with the same bits as with False.  Training only: the inference engine has its own option, `wide_frames`.
         self.train_wide_frames = bool(train_wide_frames)
+        # (not a reference argument) products of the TRAINING forward's tiled attention core, independent of `train_matmul_dtype`,
+        # `train_wide_frames`, `matmul_dtype`, `wide_frames` and `attn_products` (the inference option), and in need of none of them:
+        #   'fp32' (default)  all six products (q k'^T, p v, dO v^T, dS k', dS^T q, P^T dO) on the f32-input MFMA, as ever, bit for bit
+        #   'bf16'            wherever an attention takes the tiled core — the time layers above 64 frames, and with `train_wide_frames` the
+        #                     others above 64 items per side — the six products run on the bf16 MFMA on bf16-rounded q, k', v, dO, P and dS
+        #                     with fp32 accumulation; key norm, rotary, soft clamp, softmax, belief projection, gate and their backward stay
+        #                     fp32.  Attentions of at most 64 items keep their kernels and bits.
+        if train_attn_products not in ('fp32', 'bf16'):
+            raise ValueError("train_attn_products must be 'fp32' or 'bf16'")
+        self.train_attn_products = train_attn_products
         # (not a reference argument) wide frames in the inference engine, independent of `train_wide_frames`: False (default)
         # at most 64 latent tokens, spatial tokens and tokens per frame (a larger model's generate() / inference forward() raise D4Error at
         # d4_engine_create); True: up to 1024 of each, on the tiled matrix-pipe attention core (csrc/attn_wide_mfma.hip) wherever an
@@ -841,7 +852,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             discrete_actions=discrete_actions.to(dev).long() if discrete_actions is not None else None,
             continuous_actions=continuous_actions.to(dev).float() if continuous_actions is not None else None,
             tasks=tasks.to(dev).long() if tasks is not None else None, softclamp_value=self.attn_softclamp_value, arith=self.train_matmul_dtype,
-            wide=self.train_wide_frames)
+            wide=self.train_wide_frames, attn_products=self.train_attn_products)
         rew = rewards.to(dev).float() if rewards is not None else None
         if rew is not None and rew.shape[1] == T - 1:
             rew = torch.nn.functional.pad(rew, (1, 0), value=0.)                                           # dreamer4.py:6905-6907

@@ -400,6 +400,18 @@ int d4_train_arith_get(void);
  * setting of its forward) and restores it after.  Process-wide like d4_train_arith_set; returns the previous value.  The inference engine is
  * not concerned: its own option is d4_config.wide_frames (up to 1024 tokens per frame; more than 64 pooled hiddens stay refused). */
 int d4_train_wide_set(int on);
+/* Products of the tiled attention core of the training path: 0 (default) fp32, all six on the f32-input MFMA as ever; 1 bf16:
+ * every block launch that takes the tiled core (the time layers above 64 frames, space / cross attention under the d4_train_wide_set(1) rule,
+ * any of the three under its d4_debug_switch hook) runs the core's bf16-product form (csrc/attn_tiled_bf16.hip: bf16-rounded q, k', v, dO, P
+ * and dS on the bf16 MFMA, fp32 accumulate, everything else fp32).  The whole-problem-in-LDS kernels at <= 64 items are not concerned.  The
+ * three workspace size queries answer for the CURRENT setting (the bf16 images follow the unchanged carve-up wherever the tiled core runs), so
+ * a caller sets the switch around the size query and EACH forward / backward call alike, like d4_train_wide_set.  Process-wide; returns the
+ * previous value; any other value returns -1, changes nothing and is named in d4_last_error.
+ * What follows the switch: d4_time_attn_*, d4_space_attn_*, d4_cross_attn_* (forward, backward, backward_saved) and their three workspace size
+ * queries.  What does not: the operator entries below.  d4_train_attn_core / d4_train_xattn_core run the LDS kernel (core 0) or the fp32 tiled
+ * core (core 1) on planes of d4_train_*_core_plane_floats floats whatever the switch says, and d4_train_attn_core_bf16 /
+ * d4_train_xattn_core_bf16 always run the bf16 form. */
+int d4_train_attn_products_set(int products);
 int d4_train_scratch_bind(void* scratch, size_t bytes);
 size_t d4_ff_bf16_scratch_bytes(int rows, int dim, int inner);
 size_t d4_attn_bf16_scratch_bytes(int rows, int dim, int heads, int dim_head);
@@ -533,7 +545,8 @@ int d4_debug_forms(const char* family, int i, const char** name);
  * aligned; rows = groups * items, q_rows = groups * nq, k_rows = groups * nk).  d_o3 null: forward only, o3 alone is written.  With d_o3 the
  * self core writes the q / k / v, gate and mix columns of dproj (mix: +0 without rv), d_rv (with rv) and dgamma_part [groups][heads * dim_head]; the cross
  * core the q and gate columns of dprojq, the k / v columns of dprojk, and dgamma_part.  Nothing else is written.  Forms are recorded under the
- * families "train_attn" and "train_xattn" (by the block calls too). */
+ * families "train_attn" and "train_xattn" (by the block calls too).  These two entries do not follow d4_train_attn_products_set: core 1 is
+ * always the fp32 form, on planes of the size below. */
 size_t d4_train_attn_core_plane_floats(int rows, int heads, int dim_head);
 size_t d4_train_xattn_core_plane_floats(int q_rows, int k_rows, int heads, int dim_head);
 int d4_train_attn_core(const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3,
@@ -545,6 +558,21 @@ int d4_train_xattn_core(const float* projq, int ldq, const float* projk, int ldk
                         float* o3, float* dprojq, float* dprojk, float* dgamma_part,
                         int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,
                         int core, float* planes, size_t plane_floats, void* stream);
+/* The same two cores in the bf16-product form of the tiled core (csrc/attn_tiled_bf16.hip), whatever d4_train_attn_products_set says: the
+ * parameter lists, outputs, refusals and texts above, but `core` must be 1 (the whole-problem-in-LDS kernels have no bf16 form) and `planes`
+ * holds the bf16 images too: their transposed copies are padded to 32 items per problem, so the size depends on the items per problem and not
+ * on the rows alone.  Forms are recorded under the families "train_attn_bf16" and "train_xattn_bf16" (by the block calls too). */
+size_t d4_train_attn_core_bf16_plane_floats(int groups, int items, int heads, int dim_head);
+size_t d4_train_xattn_core_bf16_plane_floats(int groups, int nq, int nk, int heads, int dim_head);
+int d4_train_attn_core_bf16(const float* proj, int ldp, const float* rv, const float* gamma, const float* d_o3,
+                            float* o3, float* dproj, float* d_rv, float* dgamma_part,
+                            int groups, int items, int heads, int dim_head, float softclamp, int num_special, int belief,
+                            int g_inner, int64_t g_outer_stride, int64_t item_stride, int causal, const float* inv_freq,
+                            int core, float* planes, size_t plane_floats, void* stream);
+int d4_train_xattn_core_bf16(const float* projq, int ldq, const float* projk, int ldk, const float* gamma, const float* d_o3,
+                             float* o3, float* dprojq, float* dprojk, float* dgamma_part,
+                             int groups, int nq, int nk, int heads, int dim_head, int item_major, float softclamp,
+                             int core, float* planes, size_t plane_floats, void* stream);
 
 /* Operator-level entry points of the launches only the engine reaches otherwise (test / tooling use): one GEMM family and configuration chosen by
  * the caller, the pair launches, and the per-frame fused block tails of csrc/frame_fused.hip.  Each fills the launcher's argument struct
