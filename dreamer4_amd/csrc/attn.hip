@@ -710,7 +710,7 @@ int pool_mix(const PoolMixArgs& p, hipStream_t stream) {
     // M = 1280 (the final stage's compacted rows) 24.1 -> 14.3 us, M = 3584 25.3 -> 27.8 us (the wave-per-row form wins once it fills the chip)
     constexpr int rows_max = 2048;
     const bool kb = p.k_b != nullptr;                // bf16 engine: keys from their bf16 image (template flag of both kernels)
-    if (p.M <= rows_max && p.D <= 512) {
+    if ((p.rule_M > 0 ? p.rule_M : p.M) <= rows_max && p.D <= 512) {
         note_form(FAM_POOL_MIX, p.D <= 256 ? (kb ? "pool_mix_rows_kernel<1,bf16>" : "pool_mix_rows_kernel<1>") : (kb ? "pool_mix_rows_kernel<2,bf16>" : "pool_mix_rows_kernel<2>"));
         const double rb = 4.0 * p.M * ((double)p.L * (p.D + p.ldk) + p.ldq + p.D + (double)p.heads * p.D);
         if (p.D <= 256) { if (kb) hipLaunchKernelGGL((pool_mix_rows_kernel<1, true>), dim3(p.M), block, 0, stream, p); else hipLaunchKernelGGL(pool_mix_rows_kernel<1>, dim3(p.M), block, 0, stream, p); }

@@ -29,7 +29,14 @@ int hip_fail(hipError_t e, const char* what);
         }                                     \
     } while (0)
 
-#define D4_LAUNCH_CHECK() D4_HIP(hipGetLastError())
+// every kernel launch is followed by this check; it also counts them (test hook d4_debug_switch("launch_count"): two paths that must enqueue the
+// same number of kernels are compared by it)
+extern unsigned g_launch_count;
+#define D4_LAUNCH_CHECK()               \
+    do {                                \
+        ++d4::g_launch_count;           \
+        D4_HIP(hipGetLastError());      \
+    } while (0)
 
 // ---- wave64 reductions -----------------------------------------------------------------------
 // Row (16-lane) butterfly with DPP, then the four row totals are combined through readlane.

@@ -223,8 +223,9 @@ __global__ void assemble_kernel(AssembleArgs p) {
         }
         p.tokens[i] = v;
         if (p.compact) {
-            const int rank = (s >= 1 && s <= p.ns) ? s - 1 : ((p.has_agent && s == p.S - 1) ? p.ns : -1);
-            if (rank >= 0) p.compact[(f * (p.ns + p.has_agent) + rank) * D + d] = v;
+            const int cns = p.compact_spatial ? p.ns : 0;
+            const int rank = (s >= 1 && s <= cns) ? s - 1 : ((p.has_agent && s == p.S - 1) ? cns : -1);
+            if (rank >= 0) p.compact[(f * (cns + p.has_agent) + rank) * D + d] = v;
         }
     }
 }
@@ -276,8 +277,9 @@ __global__ __launch_bounds__(256) void assemble4_kernel(AssembleArgs p) {
         }
         *reinterpret_cast<f32x4*>(p.tokens + i * 4) = v;
         if (p.compact) {
-            const int rank = (s >= 1 && s <= p.ns) ? s - 1 : ((p.has_agent && s == p.S - 1) ? p.ns : -1);
-            if (rank >= 0) *reinterpret_cast<f32x4*>(p.compact + (f * (p.ns + p.has_agent) + rank) * p.D + d) = v;
+            const int cns = p.compact_spatial ? p.ns : 0;
+            const int rank = (s >= 1 && s <= cns) ? s - 1 : ((p.has_agent && s == p.S - 1) ? cns : -1);
+            if (rank >= 0) *reinterpret_cast<f32x4*>(p.compact + (f * (cns + p.has_agent) + rank) * p.D + d) = v;
         }
     }
 }

@@ -66,7 +66,7 @@ struct d4_engine {
     // captured decode frames: key = (batch, num_steps, step_log2, has_tasks, history bucket) -> executable graph of the K+1 evaluations.
     // The history bucket (d4::time_history_bucket of the frame offset) is part of the key because the time-attention launcher picks its
     // kernel by it: a replayed frame runs exactly the kernels the same frame runs when enqueued eagerly.
-    struct FrameGraph { int B, K, sl, tasks, bucket; hipGraphExec_t exec; };
+    struct FrameGraph { int B, K, sl, tasks, bucket, lean; hipGraphExec_t exec; };      // lean: the clean evaluation kept the agent row alone (engine_forward: need_pred)
     std::vector<FrameGraph> graphs;
     int graph_max_rows = 4096;
     bool warm = false;
@@ -158,6 +158,10 @@ struct d4_engine {
     int64_t* tasks_dev;                    // engine-owned copy of the task ids (stable address for captured graphs)
     float* cache;
     float *agent_c, *hbuf[2], *hnorm, *rlogits, *term_pool, *term_logit, *l_dwpart = nullptr;
+    // rollout, value / reward heads once per call over every (trajectory, frame) row: scratch of up to head_rows rows (hb_* as hbuf / hnorm / rlogits), the
+    // scalars of a chunk before they are scattered to the caller's stride, and the engine's own agent history [B][F][D] for callers that pass none
+    int head_rows = 0; size_t hist_rows = 0;
+    float *hb_buf[2], *hb_norm, *hb_rlogits, *hb_scal, *agent_hist;
 
     // ---- learner (workspace; sized by max_learn_rows)
     int LR = 0;
@@ -171,11 +175,14 @@ namespace d4 {
 int engine_layout(d4_engine* e, bool assign);
 int engine_resolve(d4_engine* e);
 int engine_prepare(d4_engine* e, hipStream_t s);
+// need_pred = false (with need_agent; the rollout's clean evaluation): the latent prediction is not wanted — to_latent_pred is skipped and, where
+// engine_clean_agent_only(e), the final stage runs on the agent row alone: e->xfc is then [B*Tq][1][D] and e->pred is left as it was
 int engine_forward(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev = nullptr);
+                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev = nullptr, bool need_pred = true);
+bool engine_clean_agent_only(const d4_engine* e);
 void engine_drop_graphs(d4_engine* e);
 int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, float* out, int ldo,
-                float* save, hipStream_t s);
+                float* save, hipStream_t s, float* const* hbuf = nullptr, float* hnorm = nullptr);
 int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s);
 const char* last_error();
 }  // namespace d4

@@ -203,6 +203,18 @@ int engine_layout(d4_engine* e, bool assign) {
     e->rlogits = fl((size_t)e->maxB * c.reward_num_bins);
     e->term_pool = fl((size_t)e->maxB * dl);
     e->term_logit = fl(e->maxB);
+    // value / reward heads of a rollout, once per call over every (trajectory, frame) row in chunks of at most 4096 rows (dynamics engines only)
+    e->head_rows = 0; e->hist_rows = 0;
+    if (!e->decoder && !e->encoder) {
+        const size_t all = (size_t)e->maxB * e->Tcap;
+        e->head_rows = (int)(all < 4096 ? all : 4096);
+        e->hist_rows = all;
+        const size_t hr = e->head_rows;
+        e->hb_buf[0] = fl(hr * maxdim); e->hb_buf[1] = fl(hr * maxdim); e->hb_norm = fl(hr * maxdim);
+        e->hb_rlogits = fl(hr * c.reward_num_bins);
+        e->hb_scal = fl(hr);
+        e->agent_hist = fl(all * D);
+    }
 
     // learner
     e->LR = c.max_learn_rows;
@@ -404,6 +416,7 @@ int engine_resolve(d4_engine* e) {
 static thread_local d4_engine* t_bf16 = nullptr;
 static thread_local int t_sig_uniform = -1;    // >= 0: every frame of the next engine_forward is at this signal level (decode loop: no fill kernel)
 static thread_local int t_keep_lo = 1;         // first token row of a frame the compacted copies keep (set by engine_forward)
+static thread_local int t_keep_hi = 1;         // ... and one past the last (== t_keep_lo: the compacted copies keep the agent row alone)
 
 static int mirror_weight(d4_engine* e, const float* src, size_t rows, int ld, hipStream_t s) {
     size_t n = rows * (size_t)ld;
@@ -732,13 +745,18 @@ static int ff_block(d4_engine* e, const FfPrep& fp, const float* out_b, const fl
     if ((rc = engine_gemm(g1, s))) return rc;
     GemmArgs g2{e->ffh, e->inner_pad, fp.w2, e->inner_pad, y, ldy, out_b, x, ldx, rows, e->D, e->inner_pad, 0, RMS_EPS,
                 2.0 * rows * (double)e->D * e->inner};
-    if (y_compact) { g2.C2 = y_compact; g2.ldc2 = e->D; g2.c2_S = S; g2.c2_lo = e->keep_lo; g2.c2_hi = e->keep_hi; g2.c2_last = has_agent; }
+    if (y_compact) { g2.C2 = y_compact; g2.ldc2 = e->D; g2.c2_S = S; g2.c2_lo = t_keep_lo; g2.c2_hi = t_keep_hi; g2.c2_last = has_agent; }
     return engine_gemm(g2, s);
 }
 
 int g_pool_wide_keys = 1;             // test hook d4_debug_switch("pool_wide_keys")
+int g_rollout_clean_agent_row = 1;    // test hook d4_debug_switch("rollout_clean_agent_row"): 0 = the rollout's clean evaluation computes the latent prediction too
+int g_rollout_batched_heads = 1;      // test hook d4_debug_switch("rollout_batched_heads"): 0 = value and reward heads after every frame
+unsigned g_launch_count = 0;          // kernel launches so far (common.h: D4_LAUNCH_CHECK; read / reset through d4_debug_switch("launch_count"))
+// rule_M > 0 (the final pool of an evaluation that keeps the agent row alone): the rows the same pool has when the spatial rows are kept too — every
+// product and the mix are dispatched as for that row count (GemmArgs::rule_M), so the rows computed carry the bits they have there
 static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int M, hipStream_t s, const float* hiddens = nullptr,
-                      float* y_compact = nullptr, int S = 0, int has_agent = 1) {
+                      float* y_compact = nullptr, int S = 0, int has_agent = 1, int rule_M = 0) {
     if (!hiddens) hiddens = e->slabs;
     const d4_config& c = e->c;
     const int D = e->D, hp = e->hp;
@@ -746,7 +764,8 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
     int rc;
     const bool mix_path = c.pool_heads == 4 && D <= 1024;
     // (mix path: the head-gate logits are computed inside pool_mix; hp = 256 columns are exactly two / four tile columns)
-    const GemmArgs gq{x, D, e->pq_w[p], D, e->pool_q, e->ldpq, nullptr, nullptr, 0, M, mix_path ? hp : hp + e->php, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+    GemmArgs gq{x, D, e->pq_w[p], D, e->pool_q, e->ldpq, nullptr, nullptr, 0, M, mix_path ? hp : hp + e->php, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+    gq.rule_M = rule_M;
     if (mix_path) {
         // keys only: [L*M][hp]; values come from ONE per-head projection of the softmax-weighted normalised hiddens
         // bf16 engine, in-loop pools: the hiddens produced since the previous pool (slabs 2p+1, 2p+2; pool 0: slab 0 too) are projected ONCE, onto the
@@ -765,12 +784,13 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
             pm.k = nullptr; pm.k_b = e->kall_b + (size_t)p * hp; pm.ldk = ld;
             pm.q = nullptr; pm.q_b = e->kall_b + (size_t)(L - 1) * M * ld + (size_t)(c.depth - 1) * hp; pm.ldq = ld;
         } else {
-        const GemmArgs gk{hiddens, D, e->pkv_w[p], D, e->pool_kv, hp, nullptr, nullptr, 0, L * M, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+        GemmArgs gk{hiddens, D, e->pkv_w[p], D, e->pool_kv, hp, nullptr, nullptr, 0, L * M, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+        gk.rule_M = L * rule_M;
         if ((rc = gemm_two(gq, gk, s))) return rc;
         if (t_bf16) pm.k_b = t_bf16->shadow_of(e->pool_kv);               // bf16 keys (the only copy of them in this mode)
         }
         pm.x = x; pm.ldx = D; pm.gate_w = e->pq_w[p] + (size_t)hp * D; pm.hid = hiddens; pm.D = D; pm.k_gamma = a.k_gamma;
-        pm.u = e->pool_u; pm.M = M; pm.L = L; pm.heads = c.pool_heads; pm.eps = RMS_EPS;
+        pm.u = e->pool_u; pm.M = M; pm.L = L; pm.heads = c.pool_heads; pm.eps = RMS_EPS; pm.rule_M = rule_M;
         if (t_bf16 && D > 512) pm.hid_b = t_bf16->shadow_of(hiddens);     // (D <= 512 may take the block-per-row form, which reads fp32)
         if (t_bf16) if (uint16_t* ub = t_bf16->shadow_of(e->pool_u)) { pm.u_b = ub; if (t_bf16->shadow_only(e->pool_u)) pm.u = nullptr; }   // only the value GEMM reads the mixes
         // per-frame fused form (mix -> value projection -> output projection + residual in one kernel) where a frame per workgroup fills the chip;
@@ -780,13 +800,13 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
         const bool deep = L > 64 || g_pool_mix_deep;
         if (S > 0 && M % S == 0 && !e->pv_t.empty() && (!t_bf16 || t_bf16->fp32_planes()) && frame_pool_tail_applicable(M / S, S, D, c.pool_heads)) {
             const bool tail_only = deep || frame_fused_mode() == 2;
-            if (!tail_only) return frame_pool(pm, e->pv_t[p], e->po_t[p], M / S, S, x, D, y, D, y_compact, D, e->keep_lo, e->keep_hi, has_agent, s);
+            if (!tail_only) return frame_pool(pm, e->pv_t[p], e->po_t[p], M / S, S, x, D, y, D, y_compact, D, t_keep_lo, t_keep_hi, has_agent, s);
             if ((rc = deep ? pool_mix_deep(pm, s) : pool_mix(pm, s))) return rc;
-            return frame_pool_tail(e->pool_u, e->pv_t[p], e->po_t[p], M / S, S, D, c.pool_heads, x, D, y, D, y_compact, D, e->keep_lo, e->keep_hi, has_agent, s);
+            return frame_pool_tail(e->pool_u, e->pv_t[p], e->po_t[p], M / S, S, D, c.pool_heads, x, D, y, D, y_compact, D, t_keep_lo, t_keep_hi, has_agent, s);
         }
         if ((rc = deep ? pool_mix_deep(pm, s) : pool_mix(pm, s))) return rc;
         GemmArgs gv{e->pool_u, c.pool_heads * D, e->pkv_w[p] + (size_t)hp * D, D, e->pool_att, hp, nullptr, nullptr, 0, M, 64, D, 0, RMS_EPS};
-        gv.batch = c.pool_heads; gv.strideA = D; gv.strideW = (int64_t)64 * D; gv.strideC = 64;
+        gv.batch = c.pool_heads; gv.strideA = D; gv.strideW = (int64_t)64 * D; gv.strideC = 64; gv.rule_M = rule_M;
         if ((rc = engine_gemm(gv, s))) return rc;
     } else {
     const GemmArgs gkv{hiddens, D, e->pkv_w[p], D, e->pool_kv, 2 * hp, nullptr, nullptr, 0, L * M, 2 * hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
@@ -803,31 +823,43 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
     sa.out_b = t_bf16 ? t_bf16->shadow_of(e->pool_att) : nullptr;
     if ((rc = small_attn(sa, s))) return rc;
     }
-    if (y_compact) return gemm_c2(e->pool_att, hp, a.to_out, hp, y, D, M, D, hp, 0, nullptr, x, D, y_compact, S, e->keep_hi - e->keep_lo, has_agent, s);
-    return gemm_simple(e->pool_att, hp, a.to_out, hp, y, D, M, D, hp, 0, nullptr, x, D, s);
+    if (y_compact) return gemm_c2(e->pool_att, hp, a.to_out, hp, y, D, M, D, hp, 0, nullptr, x, D, y_compact, S, t_keep_hi - t_keep_lo, has_agent, s);
+    GemmArgs go{e->pool_att, hp, a.to_out, hp, y, D, nullptr, x, D, M, D, hp, 0, RMS_EPS};
+    go.rule_M = rule_M;
+    return engine_gemm(go, s);
 }
 
 // Inputs expected in e->sig / e->pact (device).  Results: e->pred [B*Tq][n][dl], e->xfc [B*Tq][ns+1][D] (agent = row ns;
-// only valid when need_agent).
+// only valid when need_agent).  need_pred = false: no e->pred, and e->xfc is [B*Tq][1][D] where engine_clean_agent_only(e).
 void engine_drop_graphs(d4_engine* e) {
     for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
     e->graphs.clear();
 }
 
 static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                               const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev);
+                               const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred, bool agent_only);
+
+// The engines whose clean evaluation can keep the agent row alone: the final pool's products are then pinned (GemmArgs::rule_M) to the kernel
+// family they have with the spatial rows present, which the f32-input families and the pool's mix path provide (row-count rules by shape only, every
+// configuration of a family the same bits).  The bf16-image and fp16x2 engines, pools of other than 4 heads and dim > 1024 keep the ns + 1 rows.
+bool engine_clean_agent_only(const d4_engine* e) {
+    return !e->encoder && !e->decoder && (!e->bf16 || e->split) && e->c.pool_heads == 4 && e->D <= 1024;
+}
 
 int engine_forward(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev) {
+                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred) {
     t_bf16 = e->bf16 ? e : nullptr;           // the trunk's GEMMs below pick their bf16 weight mirrors; heads and learner stay fp32
+    need_pred = need_pred || !need_agent || e->encoder || e->decoder;
+    const bool agent_only = !need_pred && engine_clean_agent_only(e);
     t_keep_lo = e->keep_lo;
-    const int rc = engine_forward_impl(e, latents, B, Tq, t0, step_log2, tasks, need_agent, s, t0_dev);
+    t_keep_hi = agent_only ? e->keep_lo : e->keep_hi;
+    const int rc = engine_forward_impl(e, latents, B, Tq, t0, step_log2, tasks, need_agent, s, t0_dev, need_pred, agent_only);
     t_bf16 = nullptr;
     return rc;
 }
 
 static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                               const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev) {
+                               const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred, bool agent_only) {
     const d4_config& c = e->c;
     D4_REQUIRE(e->prepared, "engine not prepared");
     D4_REQUIRE(B >= 1 && B <= e->maxB, "batch %d exceeds max_batch %d", B, e->maxB);
@@ -849,7 +881,8 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
 
     float* slab0 = e->slabs;
     auto slab = [&](int j) { return e->slabs + (size_t)j * M * D; };
-    const int nkeep = e->decoder ? e->P : (e->encoder ? n : ns + has_agent), Mc = Fr * nkeep;          // rows the final stage reads
+    const int ck = agent_only ? 0 : ns;                                                                 // spatial rows the compacted copies keep
+    const int nkeep = e->decoder ? e->P : (e->encoder ? n : ck + has_agent), Mc = Fr * nkeep;          // rows the final stage reads
     auto cslab = [&](int j) { return e->cslabs + (size_t)j * Mc * D; };
     const bool same_len = ns == n;
     if (e->encoder) {
@@ -898,7 +931,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         a.prev_cont = e->nc > 0 ? e->pcont : nullptr; a.cont_embed = e->cont_embed; a.nc = e->nc;
         a.action_offsets = e->action_offsets;
         a.B = B; a.Tq = Tq; a.S = S; a.D = D; a.ns = ns; a.nr = c.num_register_tokens; a.na = e->na; a.step_log2 = step_log2;
-        a.compact = e->cslabs; a.has_agent = has_agent;
+        a.compact = e->cslabs; a.has_agent = has_agent; a.compact_spatial = agent_only ? 0 : 1;
         D4_REQUIRE(tasks == nullptr || c.num_tasks > 0, "tasks given but num_tasks == 0");
         if ((rc = assemble_tokens(a, s))) return rc;
     }
@@ -948,11 +981,11 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             // per-frame fused form: attention of all heads of a frame, then its output projection + residual, in one kernel
             const bool tail_compact = denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8;
             if (!tail_compact && !e->wo_t.empty() && (!t_bf16 || t_bf16->fp32_planes()) && frame_attn_out_applicable(sa, D)) {
-                if ((rc = frame_attn_out(sa, e->wo_t[l], D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, e->keep_lo, e->keep_hi, has_agent, s))) return rc;
+                if ((rc = frame_attn_out(sa, e->wo_t[l], D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, t_keep_lo, t_keep_hi, has_agent, s))) return rc;
                 fused_out = true;
             } else if (!tail_compact && hd == 512 && (!t_bf16 || t_bf16->fp32_planes()) && attn_out_cols_applicable(sa, D)) {
                 // few frames (launch-bound decode): attention recomputed inside every column workgroup of the output projection, one launch for two
-                if ((rc = attn_out_cols(sa, a.to_out, hd, D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, e->keep_lo, e->keep_hi, has_agent, s))) return rc;
+                if ((rc = attn_out_cols(sa, a.to_out, hd, D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, t_keep_lo, t_keep_hi, has_agent, s))) return rc;
                 fused_out = true;
             } else
             if ((rc = small_attn(sa, s))) return rc;
@@ -967,7 +1000,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         }
         float* h1 = slab(2 * l + 1);
         float* h2 = slab(2 * l + 2);
-        if (!fused_out && (rc = gemm_c2(e->att, hd, a.to_out, hd, h1, D, M, D, hd, 0, nullptr, x_in, D, cslab(2 * l + 1), S, e->keep_hi - e->keep_lo, has_agent, s))) return rc;
+        if (!fused_out && (rc = gemm_c2(e->att, hd, a.to_out, hd, h1, D, M, D, hd, 0, nullptr, x_in, D, cslab(2 * l + 1), S, t_keep_hi - t_keep_lo, has_agent, s))) return rc;
         if ((rc = ff_block(e, e->ffp[l], e->layer_ff[l].out_b, h1, D, h2, D, M, s, cslab(2 * l + 2), S, has_agent))) return rc;
         if (l != c.depth - 1) {
             float* xc = (denoise_only && l == c.depth - 2 && !e->is_time[c.depth - 1] && S <= 16 && S >= 8) ? e->xpool_c : nullptr;
@@ -980,6 +1013,8 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     // (-> heads) of each frame are consumed downstream, and every remaining op is per token, so the final attention
     // pool runs on (ns + 1) of the S rows per frame — the K/V projection of its 2*depth+1 hiddens is the largest
     // single GEMM of an evaluation.  xfc [Fr][ns+1][D]: rows 0..ns-1 spatial tokens, row ns the agent token.
+    // agent_only (the rollout's clean evaluation: nobody reads its latent prediction): the compacted copies hold the agent row alone, xfc is
+    // [Fr][1][D], and the pool's products run on Fr rows in the kernel family they have at Fr * (ns + 1) rows (pool_block: rule_M).
     float* xfc = e->xfc;
     const float* last = slab(2 * c.depth);
     if ((rc = copy_rows(cslab(2 * c.depth), D, xfc, D, Mc, D, s))) return rc;
@@ -1016,7 +1051,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     if (need_agent) {
         // agent token cross-attends the non-special tokens of its frame, then its own feedforward (D4:3227-3238)
         const float* agent_in = last + (size_t)(S - 1) * D;
-        float* agent_rows = xfc + (size_t)ns * D;
+        float* agent_rows = xfc + (size_t)ck * D;
         const int lda = S * D, ldc = nkeep * D;
         {
             const GemmArgs gq{agent_in, lda, e->cq_w, D, e->cq, e->ldcq, nullptr, nullptr, 0, Fr, hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
@@ -1038,7 +1073,8 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, agent_rows, ldc, agent_rows, ldc, Fr, s))) return rc;
     }
     // ---- final attention pool over every layer hidden (D4:3242-3243), compact rows
-    if ((rc = pool_block(e, c.depth - 1, xfc, xfc, e->nslab, Mc, s, e->cslabs))) return rc;
+    if ((rc = pool_block(e, c.depth - 1, xfc, xfc, e->nslab, Mc, s, e->cslabs, nullptr, 0, 1, agent_only ? Fr * (ns + 1) : 0))) return rc;
+    if (!need_pred) return 0;                 // the clean step of a rollout: the prediction is never read (d4_rollout breaks before the Euler step)
 
     // ---- to_latent_pred: RMSNorm -> LQAP (n queries over the ns spatial tokens) -> Linear  (D4:7251)
     if (same_len) {
@@ -1069,8 +1105,10 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
 static constexpr float LN_EPS = 1e-5f;      // nn.LayerNorm default
 
 int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, float* out, int ldo,
-                float* save, hipStream_t s) {
+                float* save, hipStream_t s, float* const* hbuf, float* hnorm) {
     int rc;
+    if (!hbuf) hbuf = e->hbuf;                // (the rollout's batched heads bring their own, larger scratch)
+    if (!hnorm) hnorm = e->hnorm;
     const float* cur = x;
     int ld = ldx;
     const bool pre = m.recipe == D4_MLP_PRE_RMS;
@@ -1102,13 +1140,13 @@ int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, f
             }
             continue;
         }
-        float* y = last ? out : e->hbuf[i & 1];
+        float* y = last ? out : hbuf[i & 1];
         const int ldy = last ? ldo : dout;
         const float* lin_in = cur;
         int ld_in = ld;
         if (pre) {
-            if ((rc = rmsnorm_rows(cur, ld, m.g[i], e->hnorm, din, rows, din, RMS_EPS, s))) return rc;
-            lin_in = e->hnorm; ld_in = din;
+            if ((rc = rmsnorm_rows(cur, ld, m.g[i], hnorm, din, rows, din, RMS_EPS, s))) return rc;
+            lin_in = hnorm; ld_in = din;
         }
         const int act = (!last && !post) ? 1 : 0;          // SiLU fused into the linear's epilogue unless a LayerNorm sits in between
         // ONE launch per layer (bias + SiLU in the epilogue).  Rounds 1-4 sliced K over the grid and combined the slices in a reduce kernel (few rows x
@@ -1117,6 +1155,41 @@ int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, f
         if ((rc = gemm_simple(lin_in, ld_in, m.w[i], din, y, ldy, rows, dout, din, act ? GEMM_SILU : 0, m.b[i], nullptr, 0, s))) return rc;
         if (post && (rc = layernorm_rows(y, ldy, m.g[i], m.nb[i], y, ldy, rows, dout, LN_EPS, 1, s))) return rc;
         cur = y; ld = ldy;
+    }
+    return 0;
+}
+
+// Value and reward heads of a rollout over all B * F agent rows of its history `hist` ([B][F][D], contiguous), after the frame loop: nothing inside
+// the loop reads values or rewards, and at B * F rows the 4 dim x 4 dim layers run as matrix products instead of streaming their weights once per
+// frame.  Whole trajectories per chunk, at most e->head_rows rows.  F == 1 (one new frame per call: the env-step pattern) makes the per-frame launches.
+static int rollout_heads_batched(d4_engine* e, const d4_rollout_io* io, const float* hist, int B, int F, int P, int T, hipStream_t s) {
+    const d4_config& c = e->c;
+    const int D = e->D, rb = c.reward_num_bins, vbins = c.value_num_bins;
+    int rc;
+    if (F == 1) {
+        if ((rc = rmsnorm_rows(hist, D, e->reward_norm, e->hnorm, D, B, D, RMS_EPS, s))) return rc;
+        if ((rc = gemm_simple(e->hnorm, D, e->reward_w, D, e->rlogits, rb, B, rb, D, 0, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = hl_gauss_scalar(e->rlogits, rb, e->reward_centers, io->rewards + P, T, B, rb, s))) return rc;
+        if (!io->sample_actions) return 0;
+        float* vb = e->hbuf[(e->value.nl - 1) & 1];
+        if ((rc = mlp_forward(e, e->value, hist, D, B, vb, vbins, nullptr, s))) return rc;
+        return hl_gauss_scalar(vb, vbins, e->value_centers, io->values, 1, B, vbins, s);
+    }
+    const int nb_max = e->head_rows / F;
+    D4_REQUIRE(nb_max >= 1, "rollout: %d frames exceed the %d rows of the batched heads' scratch", F, e->head_rows);
+    for (int b0 = 0; b0 < B; b0 += nb_max) {
+        const int nb = B - b0 < nb_max ? B - b0 : nb_max, rows = nb * F;
+        const float* x = hist + (size_t)b0 * F * D;
+        // reward: Ensemble member 0 of [RMSNorm -> Linear]                     D4:6598-6601
+        if ((rc = rmsnorm_rows(x, D, e->reward_norm, e->hb_norm, D, rows, D, RMS_EPS, s))) return rc;
+        if ((rc = gemm_simple(e->hb_norm, D, e->reward_w, D, e->hb_rlogits, rb, rows, rb, D, 0, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = hl_gauss_scalar(e->hb_rlogits, rb, e->reward_centers, e->hb_scal, 1, rows, rb, s))) return rc;
+        if ((rc = copy_rows(e->hb_scal, F, io->rewards + (size_t)b0 * T + P, T, nb, F, s))) return rc;      // [nb][F] -> frames P .. T-1 of [B][T]
+        if (!io->sample_actions) continue;
+        // value                                                                    D4:6659-6662
+        float* vb = e->hb_buf[(e->value.nl - 1) & 1];
+        if ((rc = mlp_forward(e, e->value, x, D, rows, vb, vbins, nullptr, s, e->hb_buf, e->hb_norm))) return rc;
+        if ((rc = hl_gauss_scalar(vb, vbins, e->value_centers, io->values + (size_t)b0 * F, 1, rows, vbins, s))) return rc;
     }
     return 0;
 }
@@ -1393,6 +1466,19 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
     const int n_el = c.num_latent_tokens * c.dim_latent;
     const int D = e->D, S = e->S, A = e->A, na = e->na, nc = e->nc;
     if (!io->use_time_cache) e->cache_frames = 0;
+    // The clean evaluation of a frame (step == K) feeds the heads alone: its latent prediction is never read, so it is not computed, and the final
+    // stage keeps the agent row only where the engine can (engine_clean_agent_only); lean_keep = token rows per frame of e->xfc after it.
+    const bool lean = d4::g_rollout_clean_agent_row != 0;
+    const int lean_keep = (lean && d4::engine_clean_agent_only(e)) ? 1 : c.num_spatial_tokens + 1;
+    // Only the sampled action (policy head) and the terminal feed the next frame; values and rewards are outputs nobody reads inside the loop: they
+    // are computed once after it, over the whole agent history [B][F][D] — the caller's, else the engine's own (one frame: the frame's rows).
+    const float* hist = nullptr;
+    if (d4::g_rollout_batched_heads && F >= 1 && F <= e->head_rows) {
+        if (io->agent_embed) hist = io->agent_embed;
+        else if (F == 1) hist = e->agent_c;
+        else if ((size_t)B * F <= e->hist_rows) hist = e->agent_hist;
+    }
+    const bool heads_after = hist != nullptr;
 
     for (int f = 0; f < F; ++f) {
         const int cur = P + f;                       // frames of history in this call
@@ -1418,7 +1504,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
             }
             hipGraphExec_t exec = nullptr;
             const int bucket = e->Lt > 0 ? d4::time_history_bucket(t0) : 0;
-            for (auto& g : e->graphs) if (g.B == B && g.K == K && g.sl == sl && g.tasks == (tasks != nullptr) && g.bucket == bucket) exec = g.exec;
+            for (auto& g : e->graphs) if (g.B == B && g.K == K && g.sl == sl && g.tasks == (tasks != nullptr) && g.bucket == bucket && g.lean == (int)lean) exec = g.exec;
             if (!exec) {
                 if (!e->warm) {
                     // first decode frame of this engine: run it eagerly once (function attributes, lazy module load)
@@ -1434,7 +1520,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                     for (int step = 0; step <= K && !crc; ++step) {
                         const int sig_val = step * step_size < c.max_steps - 1 ? step * step_size : c.max_steps - 1;
                         d4::t_sig_uniform = sig_val;
-                        crc = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, cs, e->fstate);
+                        crc = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, cs, e->fstate, !(step == K && lean));
                         d4::t_sig_uniform = -1;
                         if (crc) break;
                         if (step == K) break;
@@ -1446,7 +1532,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                     D4_HIP(ce);
                     D4_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                     (void)hipGraphDestroy(graph);
-                    e->graphs.push_back({B, K, sl, tasks != nullptr, bucket, exec});
+                    e->graphs.push_back({B, K, sl, tasks != nullptr, bucket, (int)lean, exec});
                 }
             }
             if (exec) {
@@ -1455,7 +1541,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                 for (int step = 0; step <= K; ++step) {
                     const int sig_val = step * step_size < c.max_steps - 1 ? step * step_size : c.max_steps - 1;
                     d4::t_sig_uniform = sig_val;
-                    rc = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, s, e->fstate);
+                    rc = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, s, e->fstate, !(step == K && lean));
                     d4::t_sig_uniform = -1;
                     if (rc) return rc;
                     if (step == K) break;
@@ -1475,7 +1561,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                 lat = e->lat_in;
             }
             if ((rc = d4::prep_eval_inputs(e->sig, e->pact, io->actions, B, Tq, na, cur + 1 - Tq, T, sig_val, c.max_steps - 1, s, nc > 0 ? e->pcont : nullptr, io->actions_cont, nc))) return rc;
-            if ((rc = d4::engine_forward(e, lat, B, Tq, t0, sl, io->tasks, last, s))) return rc;
+            if ((rc = d4::engine_forward(e, lat, B, Tq, t0, sl, io->tasks, last, s, nullptr, !(last && lean)))) return rc;
             if (last) { if (commit) e->cache_frames = t0 + Tq; break; }
             const float tt = (float)sig_val / (float)c.max_steps;
             if ((rc = d4::euler_step(e->x_lat, n_el, e->pred + (size_t)(Tq - 1) * n_el, Tq * n_el, B, n_el,
@@ -1483,14 +1569,17 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
         }
 
         // ---- heads on the agent embedding of the clean step (D4:6595-6662)
-        const int nkeep = c.num_spatial_tokens + 1;
+        const int nkeep = lean_keep;
         const float* agent_row = e->xfc + ((size_t)(Tq - 1) * nkeep + (nkeep - 1)) * D;
         if ((rc = d4::copy_rows(agent_row, Tq * nkeep * D, e->agent_c, D, B, D, s))) return rc;
         if (io->agent_embed && (rc = d4::copy_rows(e->agent_c, D, io->agent_embed + (size_t)f * D, F * D, B, D, s))) return rc;
+        if (hist == e->agent_hist && (rc = d4::copy_rows(e->agent_c, D, e->agent_hist + (size_t)f * D, F * D, B, D, s))) return rc;
+        if (!heads_after) {
         // reward: Ensemble member 0 of [RMSNorm -> Linear]                     D4:6598-6601
         if ((rc = d4::rmsnorm_rows(e->agent_c, D, e->reward_norm, e->hnorm, D, B, D, d4::RMS_EPS, s))) return rc;
         if ((rc = d4::gemm_simple(e->hnorm, D, e->reward_w, D, e->rlogits, c.reward_num_bins, B, c.reward_num_bins, D, 0, nullptr, nullptr, 0, s))) return rc;
         if ((rc = d4::hl_gauss_scalar(e->rlogits, c.reward_num_bins, e->reward_centers, io->rewards + cur, T, B, c.reward_num_bins, s))) return rc;
+        }
         // terminal logit from the mean-pooled denoised latent                    D4:6605-6607
         const float* term_logit = nullptr;
         if (io->sample_terminals) {
@@ -1512,9 +1601,11 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                 if ((rc = d4::gemm_simple(pe, 4 * D, e->cu_w, 4 * D, cparams, F * nc * 2, B, 2 * nc, 4 * D, 0, nullptr, nullptr, 0, s))) return rc;
             }
             // value                                                                    D4:6659-6662
+            if (!heads_after) {
             float* vb = e->hbuf[(e->value.nl - 1) & 1];
             if ((rc = d4::mlp_forward(e, e->value, e->agent_c, D, B, vb, c.value_num_bins, nullptr, s))) return rc;
             if ((rc = d4::hl_gauss_scalar(vb, c.value_num_bins, e->value_centers, io->values + f, F, B, c.value_num_bins, s))) return rc;
+            }
             // sample action, log-prob, terminal                                        D4:6611-6616, 6637-6657
             d4::SampleArgs sa{};
             sa.logits = logits; sa.ld = F * A;
@@ -1543,6 +1634,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
         if (io->ctx_hist && io->noise_context &&
             (rc = d4::copy_rows(io->noise_context + (size_t)f * B * n_el, n_el, io->ctx_hist + (size_t)cur * n_el, T * n_el, B, n_el, s))) return rc;
     }
+    if (heads_after && (rc = d4::rollout_heads_batched(e, io, hist, B, F, P, T, s))) return rc;
     return 0;
 }
 
@@ -1560,7 +1652,14 @@ int d4_frame_fused_set(int mode) { return d4::frame_fused_set(mode); }
 
 int d4_debug_switch(const char* name, int value) {
     int* sw = nullptr;
+    if (name && !strcmp(name, "launch_count")) {        // kernel launches since the counter was last set (host side; the launches inside a replayed graph are not seen)
+        const int old = (int)(d4::g_launch_count & 0x7fffffffu);
+        d4::g_launch_count = (unsigned)value;
+        return old;
+    }
     if (name && !strcmp(name, "time_attn_fused_append")) sw = &d4::g_time_attn_fused_append;
+    else if (name && !strcmp(name, "rollout_clean_agent_row")) sw = &d4::g_rollout_clean_agent_row;
+    else if (name && !strcmp(name, "rollout_batched_heads")) sw = &d4::g_rollout_batched_heads;
     else if (name && !strcmp(name, "attn_out_cols")) sw = &d4::g_attn_out_cols;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
     else if (name && !strcmp(name, "pool_mix_deep")) sw = &d4::g_pool_mix_deep;

@@ -462,8 +462,9 @@ bool gemm2_ksplit_applicable(const GemmArgs& p) {               // what the kern
 }
 bool gemm2_ksplit_rule(const GemmArgs& p) {
     if (!gemm2_ksplit_applicable(p)) return false;
-    const int64_t tiles = (int64_t)cdiv(p.M, KS_BM) * cdiv(p.N, KS_BN);
-    if (p.M <= 256) return p.K >= 1024 && tiles >= 64 && tiles <= 1024;
+    const int M = p.rule_M > 0 ? p.rule_M : p.M;
+    const int64_t tiles = (int64_t)cdiv(M, KS_BM) * cdiv(p.N, KS_BN);
+    if (M <= 256) return p.K >= 1024 && tiles >= 64 && tiles <= 1024;
     return false;
 }
 

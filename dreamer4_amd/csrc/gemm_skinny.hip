@@ -161,8 +161,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_pair_kernel(GemmArgs a, G
 // never by timing.
 bool gemm_skinny_applicable(const GemmArgs& p) {
     constexpr int max_tiles = 64, max_m = 32;
-    const bool few = p.M <= max_m || (int64_t)cdiv(p.M, 64) * cdiv(p.N, 64) * (p.batch > 0 ? p.batch : 1) < max_tiles;
-    return p.M >= 1 && p.M <= 256 && few &&
+    const int M = p.rule_M > 0 ? p.rule_M : p.M;                  // (a subset of a product's rows is judged as the whole product)
+    const bool few = M <= max_m || (int64_t)cdiv(M, 64) * cdiv(p.N, 64) * (p.batch > 0 ? p.batch : 1) < max_tiles;
+    return p.M >= 1 && M <= 256 && few &&
            !(p.flags & (GEMM_TRANS_A | GEMM_TRANS_B)) && (p.K % 4) == 0 && (p.C2 == nullptr || p.batch <= 1);
 }
 

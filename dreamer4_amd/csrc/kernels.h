@@ -43,6 +43,8 @@ struct GemmArgs {
                                        // power of two that undoes row n's scale -> fp32 GEMM on the fp16 matrix cores, three products (gemm_h2.hip)
     int64_t strideWs = 0;              // ... batch stride of wscale (elements)
     const int* aexp = nullptr;         // optional (gemm_h2.hip): scale exponent of every A row ([batch][M]) from a producer that knows it; null: the kernel finds it
+    int rule_M = 0;                    // > 0: the row count the dispatcher's FAMILY rules see instead of M (few-row kernel, k-split form) — a caller that runs
+                                       // a subset of a product's rows keeps the family, and so the bits, of the whole product (engine.hip: the rollout's clean evaluation)
 };
 
 int gemm(const GemmArgs& p, hipStream_t stream);
@@ -174,6 +176,7 @@ struct PoolMixArgs {
     const uint16_t* q_b = nullptr;     // ... and of the projected queries ([M][ldq]; only with k_b): read instead of `q`
     const uint16_t* hid_b = nullptr;   // optional bf16 image of the hiddens (bf16 engine): read instead of `hid` by the one-wave-per-row form — the
                                        // values the pool's key GEMM consumed, at half the bytes of the kernel's dominant stream
+    int rule_M = 0;                    // > 0: the row count the form rule (block per row / wave per row) sees instead of M (see GemmArgs::rule_M)
 };
 int pool_mix(const PoolMixArgs& p, hipStream_t stream);
 // The same core over up to POOL_DEEP_MAX hiddens (pool_mix_deep.hip): the hiddens are walked in chunks of POOL_DEEP_CHUNK with an online-softmax
@@ -278,6 +281,7 @@ struct AssembleArgs {
     int B, Tq, S, D, ns, nr, na, nc, step_log2;
     float* compact;                // optional [B*Tq][ns (+ 1)][D]: spatial (+ agent) rows only
     int has_agent;                 // 0: the frame is packed without its trailing agent token (S = tokens actually present)
+    int compact_spatial = 1;       // 0: the compact copy keeps the agent row alone ([B*Tq][1][D]; the rollout's clean evaluation)
 };
 int assemble_tokens(const AssembleArgs& p, hipStream_t s);
 

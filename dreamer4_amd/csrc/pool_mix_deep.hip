@@ -350,7 +350,7 @@ int pool_mix_deep(const PoolMixArgs& p, hipStream_t stream) {
     if (p.M == 0) return 0;
     const bool kb = p.k_b != nullptr;
     const dim3 block(256);
-    if (p.M <= 2048 && p.D <= 512) {                      // the rule of pool_mix: by M and D alone, so a shape always takes the same arithmetic path
+    if ((p.rule_M > 0 ? p.rule_M : p.M) <= 2048 && p.D <= 512) {      // the rule of pool_mix: by M and D alone, so a shape always takes the same arithmetic path
         const dim3 grid(p.M);
         if (p.D <= 256) {
             note_pool_deep_form(kb ? "pool_mix_deep_rows_kernel<1,bf16>" : "pool_mix_deep_rows_kernel<1>");

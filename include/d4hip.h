@@ -184,7 +184,7 @@ typedef struct d4_rollout_io {
     float* log_probs;              /* [batch][F][action_types] */
     float* log_probs_cont;         /* [batch][F][nc] */
     float* cont_params;            /* [batch][F][nc][2] raw Beta parameters (old_action_unembeds.continuous, D4:6749-6750) */
-    float* values;                 /* [batch][F] */
+    float* values;                 /* [batch][F]; written, like `rewards`, once after the last frame (nothing inside the rollout reads them) */
     float* action_logits;          /* [batch][F][A]   (old_action_unembeds, D4:6749-6750) */
     int64_t* lens;                 /* [batch]  pre-filled with time_steps */
     uint8_t* terminals;            /* [batch]  pre-filled with 0 */
@@ -289,7 +289,15 @@ int d4_frame_fused_set(int mode);
  * option, d4_small_attn_wide_bf16 / wide_frames 3: that form of the core).  Read when a frame is enqueued, like "pool_wide_keys".
  * "pool_mix_deep" (engine attention pools, csrc/pool_mix_deep.hip; NOT bit-identical: another summation order): 0 (default) a pool takes the
  * chunked mix above 64 hiddens only (d4_config.wide_frames, depth >= 32), 1 every pool of the mix path does, as its own kernel in front of the
- * fused tail where that applies.  Read when a frame is enqueued. */
+ * fused tail where that applies.  Read when a frame is enqueued.
+ * "rollout_clean_agent_row" (d4_rollout; bit-identical): 1 (default) the clean evaluation of a frame — the one that feeds the heads; its latent
+ * prediction is never read — skips to_latent_pred and, on the fp32 engines with 4 pool heads and dim <= 1024, runs its final stage on the agent
+ * row alone; 0 it computes the prediction as d4_wm_forward does.  Part of the key of a captured frame graph.
+ * "rollout_batched_heads" (d4_rollout): 1 (default) the value and reward heads run once after the frame loop over all batch * F agent rows
+ * (values / rewards: fp32 rounding apart from the per-frame path at F > 1, bit-identical with the same launches at F == 1; everything else
+ * bit-identical); 0 after every frame.
+ * "launch_count" (not a switch): returns the number of kernel launches the library has enqueued since the counter was last set, and sets it to
+ * `value` (launches inside a replayed hipGraph are not seen). */
 int d4_debug_switch(const char* name, int value);
 int d4_gemm_force_config(int id);
 
