@@ -241,6 +241,12 @@ SYMBOLS = {
     'd4_gae': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P]),
     'd4_categorical_sample_logp': (_I, [_P, _I, _P, _I, _P, _I, _I, _F, _P, _P, _P]),
     'd4_hl_gauss_ce': (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
+    'd4_flow_noised_patches': (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    'd4_tok_rows_part_floats': (C.c_size_t, [_I, _I]),
+    'd4_layernorm_rows_bwd': (_I, [_P, _I, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _F, _P]),
+    'd4_mask_rows_fwd': (_I, [_P] * 4 + [_I, _I, _P]),
+    'd4_mask_rows_bwd': (_I, [_P] * 5 + [C.c_size_t, _I, _I, _P]),
+    'd4_recon_loss_fwd_bwd': (_I, [_P] * 4 + [_I] * 7 + [_P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

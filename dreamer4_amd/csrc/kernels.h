@@ -356,5 +356,16 @@ int encoder_pack_tokens(float* tokens, float* compact, const float* img, const f
 int tanh_rows(const float* x, float* y, int64_t n, hipStream_t s);
 int cunembed_gather(const float* U, float* w, int nc, int mtp, int d, hipStream_t s);
 int cunembed_scatter_grad(const float* g, float* dU, int nc, int mtp, int d, hipStream_t s);
+// pixel-side operators of the tokenizer's training forward (tok_train.hip).  Column sums and the loss sum: per-block partials in `part`
+// (tok_rows_part_floats(rows, dim) floats for the row operators, TOK_LOSS_PARTS for the loss), then one fixed-order reduction; no float atomics.
+static constexpr int TOK_ROW_TILE = 8;                 // rows per block of layernorm_rows_bwd / mask_rows_bwd (2 per wave)
+static constexpr int TOK_LOSS_PARTS = 1024;            // most blocks (= partial sums) of recon_loss_fwd_bwd
+size_t tok_rows_part_floats(int rows, int dim);
+int flow_noised_patches(const float* video, const float* noise, const float* t, float* rows, int B, int C, int T, int nh, int nw, int ps, hipStream_t s);
+int layernorm_rows_bwd(const float* x, int ldx, const float* dy, const float* g, float* dx, float* dg, float* part, int rows, int dim, float eps, hipStream_t s);
+int mask_rows_fwd(const float* x, const uint8_t* mask, const float* token, float* y, int rows, int dim, hipStream_t s);
+int mask_rows_bwd(const float* dy, const uint8_t* mask, float* dx, float* dtoken, float* part, int rows, int dim, hipStream_t s);
+int recon_loss_fwd_bwd(const float* recon, const float* video, const float* noise, const float* t, int B, int C, int T, int nh, int nw, int ps, int v_space,
+                       float* loss, float* d_rows, float* part, hipStream_t s);
 
 }  // namespace d4

@@ -7,6 +7,8 @@ current stream.  There is no CPU implementation: on a CPU tensor they raise (the
     out = torch.ops.d4hip.linear(x, weight, bias, residual, flags, eps) Linear with the fused epilogues     (d4_gemm; flags: _lib.GEMM_*)
     v   = torch.ops.d4hip.hl_gauss_to_scalar(logits, centers)           HLGaussRewardEncoder.bins_to_scalar_value  D4:1088-1096
     ret = torch.ops.d4hip.gae(rewards, values, lens, is_truncated, terminals, gamma, lam)     calc_gae + masks  D4:1566-1600, 5943-5971
+    torch.ops.d4hip.{video_to_patches, patches_to_video, flow_noised_patches, layernorm_nobias, mask_rows, recon_loss}
+                                                                        the pixel side of VideoTokenizer.forward  (csrc/tok_train.hip)
 
 The stateful calls (rollout, learner) keep their engine handle and therefore stay methods of DynamicsWorldModel."""
 from __future__ import annotations
@@ -613,6 +615,243 @@ def _ppo_bwd(ctx, d_loss, _d_dl):
 
 
 ppo_policy_loss.register_autograd(_ppo_bwd, setup_context=_ppo_setup)
+
+
+# ------------------------------------------------------------------------------------------------ tokenizer training forward, pixel side
+# The passes of VideoTokenizer.forward that touch B T H W C floats (D4:4239-4603; csrc/tok_train.hip).  Patch rows are
+# (b, t, nh, nw, p1 p2 c) of a video (b, c, t, H, W).  Every op is a plain `*_impl` function (what trunk_ops' autograd.Functions call on the default
+# route: less host dispatch time) registered with the dispatcher under the same name.
+def _video_geom(video, patch_size):
+    B, Cc, T, H, W = video.shape
+    if H % patch_size or W % patch_size:
+        raise _lib.D4Error(f'a {H} x {W} frame is not divisible into patches of {patch_size}')
+    return B, Cc, T, H // patch_size, W // patch_size
+
+
+def video_to_patches_impl(video, patch_size):
+    """'b c t (h p1) (w p2) -> b t h w (p1 p2 c)' (D4:3838-3844, 3896; d4_flow_noised_patches without noise).  Data only: no gradient."""
+    _need_gpu(video)
+    (video,) = _f32c(video)
+    B, Cc, T, nh, nw = _video_geom(video, patch_size)
+    rows = video.new_empty(B, T, nh, nw, patch_size * patch_size * Cc)
+    _lib.check(_lib.load().d4_flow_noised_patches(_lib.ptr(video), None, None, _lib.ptr(rows), B, Cc, T, nh, nw, patch_size, _stream(video)))
+    return rows
+
+
+@custom_op('d4hip::video_to_patches', mutates_args=())
+def video_to_patches(video: torch.Tensor, patch_size: int) -> torch.Tensor:
+    return video_to_patches_impl(video, patch_size)
+
+
+@video_to_patches.register_fake
+def _(video, patch_size):
+    B, Cc, T, H, W = video.shape
+    return video.new_empty(B, T, H // patch_size, W // patch_size, patch_size * patch_size * Cc, dtype=torch.float32)
+
+
+def patches_to_video_impl(rows, channels, patch_size):
+    """'b t h w (p1 p2 c) -> b c t (h p1) (w p2)' (D4:3556; d4_video_patches).  Used for the returned reconstruction only: no gradient."""
+    _need_gpu(rows)
+    (rows,) = _f32c(rows)
+    B, T, nh, nw, dp = rows.shape
+    assert dp == channels * patch_size * patch_size
+    video = rows.new_empty(B, channels, T, nh * patch_size, nw * patch_size)
+    _lib.check(_lib.load().d4_video_patches(_lib.ptr(rows), _lib.ptr(video), B, channels, T, nh, nw, patch_size, 0, _stream(rows)))
+    return video
+
+
+@custom_op('d4hip::patches_to_video', mutates_args=())
+def patches_to_video(rows: torch.Tensor, channels: int, patch_size: int) -> torch.Tensor:
+    return patches_to_video_impl(rows, channels, patch_size)
+
+
+@patches_to_video.register_fake
+def _(rows, channels, patch_size):
+    B, T, nh, nw, dp = rows.shape
+    return rows.new_empty(B, channels, T, nh * patch_size, nw * patch_size, dtype=torch.float32)
+
+
+def flow_noised_patches_impl(video, noise, times, patch_size):
+    """Patch rows of noise.lerp(video, times[b]) in one pass (D4:4457 + 3896; d4_flow_noised_patches).  Both inputs are data: no gradient."""
+    _need_gpu(video, noise, times)
+    video, noise, times = _f32c(video, noise, times)
+    B, Cc, T, nh, nw = _video_geom(video, patch_size)
+    assert noise.shape == video.shape and times.shape == (B,)
+    rows = video.new_empty(B, T, nh, nw, patch_size * patch_size * Cc)
+    _lib.check(_lib.load().d4_flow_noised_patches(_lib.ptr(video), _lib.ptr(noise), _lib.ptr(times), _lib.ptr(rows), B, Cc, T, nh, nw, patch_size, _stream(video)))
+    return rows
+
+
+@custom_op('d4hip::flow_noised_patches', mutates_args=())
+def flow_noised_patches(video: torch.Tensor, noise: torch.Tensor, times: torch.Tensor, patch_size: int) -> torch.Tensor:
+    return flow_noised_patches_impl(video, noise, times, patch_size)
+
+
+@flow_noised_patches.register_fake
+def _(video, noise, times, patch_size):
+    B, Cc, T, H, W = video.shape
+    return video.new_empty(B, T, H // patch_size, W // patch_size, patch_size * patch_size * Cc, dtype=torch.float32)
+
+
+def _rows_part(lib, rows, dim, device):
+    n = lib.d4_tok_rows_part_floats(rows, dim)
+    return torch.empty(n, device=device), n
+
+
+def layernorm_nobias_impl(x, weight, eps):
+    """nn.LayerNorm(dim, bias=False) (D4:114; d4_layernorm_rows), backward d4_layernorm_rows_bwd."""
+    _need_gpu(x, weight)
+    x, weight = _f32c(x, weight)
+    D = x.shape[-1]
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().d4_layernorm_rows(_lib.ptr(x), D, _lib.ptr(weight), None, _lib.ptr(y), D, x.numel() // D, D, eps, 0, _stream(x)))
+    return y
+
+
+@custom_op('d4hip::layernorm_nobias', mutates_args=())
+def layernorm_nobias(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
+    return layernorm_nobias_impl(x, weight, eps)
+
+
+@layernorm_nobias.register_fake
+def _(x, weight, eps):
+    return torch.empty_like(x, dtype=torch.float32)
+
+
+def layernorm_nobias_backward_impl(x, dy, weight, eps):
+    _need_gpu(x, dy, weight)
+    x, dy, weight = _f32c(x, dy, weight)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    lib = _lib.load()
+    dx, dw = torch.empty_like(x), torch.empty_like(weight)
+    part, n = _rows_part(lib, rows, D, x.device)
+    _lib.check(lib.d4_layernorm_rows_bwd(_lib.ptr(x), D, _lib.ptr(dy), _lib.ptr(weight), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(part), n, rows, D, eps, _stream(x)))
+    return dx, dw
+
+
+@custom_op('d4hip::layernorm_nobias_backward', mutates_args=())
+def layernorm_nobias_backward(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor, eps: float) -> tuple[torch.Tensor, torch.Tensor]:
+    return layernorm_nobias_backward_impl(x, dy, weight, eps)
+
+
+@layernorm_nobias_backward.register_fake
+def _(x, dy, weight, eps):
+    return torch.empty_like(x, dtype=torch.float32), torch.empty_like(weight, dtype=torch.float32)
+
+
+def _ln_setup(ctx, inputs, output):
+    x, weight, eps = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.eps = eps
+
+
+def _ln_bwd(ctx, dy):
+    x, weight = ctx.saved_tensors
+    dx, dw = torch.ops.d4hip.layernorm_nobias_backward(x, dy, weight, ctx.eps)
+    return dx, dw, None
+
+
+layernorm_nobias.register_autograd(_ln_bwd, setup_context=_ln_setup)
+
+
+def mask_rows_impl(tokens, mask, token):
+    """MAE masking (D4:4344): the rows of `tokens` (..., dim) whose `mask` (...) entry is set are replaced by `token` (dim,)."""
+    _need_gpu(tokens, mask, token)
+    tokens, token = _f32c(tokens, token)
+    m = mask.to(torch.uint8).contiguous()
+    D = tokens.shape[-1]
+    assert m.shape == tokens.shape[:-1] and token.shape == (D,)
+    y = torch.empty_like(tokens)
+    _lib.check(_lib.load().d4_mask_rows_fwd(_lib.ptr(tokens), _lib.ptr(m), _lib.ptr(token), _lib.ptr(y), tokens.numel() // D, D, _stream(tokens)))
+    return y
+
+
+@custom_op('d4hip::mask_rows', mutates_args=())
+def mask_rows(tokens: torch.Tensor, mask: torch.Tensor, token: torch.Tensor) -> torch.Tensor:
+    return mask_rows_impl(tokens, mask, token)
+
+
+@mask_rows.register_fake
+def _(tokens, mask, token):
+    return torch.empty_like(tokens, dtype=torch.float32)
+
+
+def mask_rows_backward_impl(dy, mask):
+    _need_gpu(dy, mask)
+    (dy,) = _f32c(dy)
+    m = mask.to(torch.uint8).contiguous()
+    D = dy.shape[-1]
+    rows = dy.numel() // D
+    lib = _lib.load()
+    dx, dtok = torch.empty_like(dy), dy.new_empty(D)
+    part, n = _rows_part(lib, rows, D, dy.device)
+    _lib.check(lib.d4_mask_rows_bwd(_lib.ptr(dy), _lib.ptr(m), _lib.ptr(dx), _lib.ptr(dtok), _lib.ptr(part), n, rows, D, _stream(dy)))
+    return dx, dtok
+
+
+@custom_op('d4hip::mask_rows_backward', mutates_args=())
+def mask_rows_backward(dy: torch.Tensor, mask: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    return mask_rows_backward_impl(dy, mask)
+
+
+@mask_rows_backward.register_fake
+def _(dy, mask):
+    return torch.empty_like(dy, dtype=torch.float32), dy.new_empty(dy.shape[-1], dtype=torch.float32)
+
+
+def _mask_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+
+
+def _mask_bwd(ctx, dy):
+    (mask,) = ctx.saved_tensors
+    dx, dtok = torch.ops.d4hip.mask_rows_backward(dy, mask)
+    return dx, None, dtok
+
+
+mask_rows.register_autograd(_mask_bwd, setup_context=_mask_setup)
+
+RECON_LOSS_PARTS = 1024           # scratch floats of d4_recon_loss_fwd_bwd (include/d4hip.h)
+
+
+def recon_loss_impl(recon_rows, video, noise, times, patch_size, v_space):
+    """The tokenizer's reconstruction loss (D4:4469-4474, 4516) on the decoder's patch rows (b, t, nh, nw, p1 p2 c): the video is read through
+    the patch permutation.  v_space: mse((recon - noise.lerp(video, t)) / (1 - t), video - noise); otherwise mse(recon, video).  Returns
+    (loss, d loss / d recon_rows); differentiable in `recon_rows` through the second output (d4_recon_loss_fwd_bwd)."""
+    _need_gpu(recon_rows, video, noise, times)
+    recon_rows, video, noise, times = _f32c(recon_rows, video, noise, times)
+    B, Cc, T, nh, nw = _video_geom(video, patch_size)
+    assert recon_rows.shape == (B, T, nh, nw, patch_size * patch_size * Cc)
+    assert not v_space or (noise is not None and noise.shape == video.shape and times is not None and times.shape == (B,))
+    loss, d_rows = video.new_empty(1), torch.empty_like(recon_rows)
+    part = video.new_empty(RECON_LOSS_PARTS)
+    _lib.check(_lib.load().d4_recon_loss_fwd_bwd(_lib.ptr(recon_rows), _lib.ptr(video), _lib.ptr(noise), _lib.ptr(times), B, Cc, T, nh, nw, patch_size,
+                                                 int(v_space), _lib.ptr(loss), _lib.ptr(d_rows), _lib.ptr(part), RECON_LOSS_PARTS, _stream(video)))
+    return loss.view(()), d_rows
+
+
+@custom_op('d4hip::recon_loss', mutates_args=())
+def recon_loss(recon_rows: torch.Tensor, video: torch.Tensor, noise: torch.Tensor | None, times: torch.Tensor | None, patch_size: int,
+               v_space: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    return recon_loss_impl(recon_rows, video, noise, times, patch_size, v_space)
+
+
+@recon_loss.register_fake
+def _(recon_rows, video, noise, times, patch_size, v_space):
+    return video.new_empty((), dtype=torch.float32), torch.empty_like(recon_rows, dtype=torch.float32)
+
+
+def _recon_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _recon_bwd(ctx, d_loss, _d_rows):
+    (d_rows,) = ctx.saved_tensors
+    return d_rows * d_loss, None, None, None, None, None
+
+
+recon_loss.register_autograd(_recon_bwd, setup_context=_recon_setup)
 
 
 def attn_pool(x: torch.Tensor, hiddens: torch.Tensor, norm_w: torch.Tensor, norm_ctx_w: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor,

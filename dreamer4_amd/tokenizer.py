@@ -8,12 +8,18 @@ Same constructor keyword names as the reference (dreamer4.py:3686-3764), the sam
 `encoder_transformer.*`, `encoded_to_latents.*`), so a reference tokenizer checkpoint loads with `load_state_dict`.  The compute is
 the HIP engine in decoder / encoder mode (include/d4hip.h `d4_decoder_forward`, `d4_encoder_forward`): the dynamics model's trunk
 kernels over [patches | latent tokens] per frame, a wide attention kernel for the ~100-token space layers, patchify / un-patchify
-kernels.  The training forward (reconstruction / LPIPS / time-decorrelation losses) is out of scope and raises.  Supported subset =
-the reference defaults: flow decoder with `decoder_flow_steps` Euler steps, no slot attention, causal conv, MOSS, aug conditioning,
-PoPE, separate flow decoder, BYOL."""
+kernels.  Supported subset = the reference defaults: flow decoder with `decoder_flow_steps` Euler steps, no slot attention, causal conv,
+MOSS, aug conditioning, PoPE, separate flow decoder, BYOL.
+
+`forward(video_or_image, ...)` is the training forward (dreamer4.py:4239-4603) for the same subset: MAE masking, encoder, tanh bottleneck,
+one flow-decoder step at a drawn time, the v-space or x-space reconstruction loss with the reference's loss normalisation, autograd to
+every parameter the loss reaches.  It runs `trunk_ops.tokenizer_losses`: both trunks on the differentiable HIP blocks, the passes over
+pixels on the operators of csrc/tok_train.hip.  LPIPS (no VGG weights), the auxiliary losses, `time_lens`, time caches,
+aug conditioning and BYOL are outside the subset and raise."""
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -21,6 +27,10 @@ from torch import nn
 from dreamer4_amd import _lib
 from dreamer4_amd.checkpoint import SaveLoad
 from dreamer4_amd.world_model import MLP_RECIPES, _linear_b, _linear_w, _register, mlp_param_specs, mlp_widths
+
+TokenizerLosses = namedtuple('TokenizerLosses', ('recon', 'flow_recon', 'lpips', 'time_decorr', 'space_decorr', 'latent_ortho', 'latent_ar', 'latent_ar_sigreg',
+                                                 'latent_consistency', 'latent_sigreg', 'h_net', 'byol'))       # dreamer4.py:118
+VideoTokenizerIntermediates = namedtuple('VideoTokenizerIntermediates', ('losses', 'recon'))
 
 _UNSUPPORTED = dict(
     latent_init_patch_size=None, encoder_full_spatial_attn=False, decoder_full_spatial_attn=False, attn_kwargs={}, ff_kwargs={},
@@ -31,18 +41,24 @@ _UNSUPPORTED = dict(
 )
 
 
+_NORMALIZER_KEY = 'recon_loss_normalizer.exp_avg_sq'
+
+
 class VideoTokenizer(SaveLoad, nn.Module):
     def __init__(self, dim, dim_latent, patch_size, image_size=None, image_height=None, image_width=None, num_latent_tokens=64,
                  encoder_depth=4, decoder_depth=4, time_block_every=4, attn_dim_head=64, attn_heads=8, decoder_pos_mlp_depth=2,
                  channels=3, decoder_flow_steps=1, head_mlp_recipe='pre_rms', wide_frames=False, attn_products='fp32',
-                 **kwargs):
+                 train_wide_frames=False, lpips_loss_weight=0.2, decoder_v_space_loss=True, **kwargs):
         """`wide_frames` is not a reference argument: False (default) the decoder and encoder engines take at most 160 tokens (patches +
         latents) and 64 latent tokens per frame; True up to 1024 of each, on the tiled attention core of csrc/attn_wide_mfma.hip above 64
         items per side, and encoder / decoder trunks of depth >= 32 (up to 1024 pooled layer hiddens, the chunked pool mix of
         csrc/pool_mix_deep.hip; refused without the option).
         `attn_products` is not a reference argument either: 'fp32' (default) the wide core's two products on the f32-input MFMA, as ever;
         'bf16' (needs `wide_frames=True`) on the bf16 MFMA with bf16-rounded q, k', v' and softmax numerators and fp32 accumulation
-        (csrc/attn_wide_bf16.hip).  Attentions of at most 64 items per side keep their kernels and bits."""
+        (csrc/attn_wide_bf16.hip).  Attentions of at most 64 items per side keep their kernels and bits.
+        `train_wide_frames` (not a reference argument, the meaning it has on DynamicsWorldModel): False (default) the training forward takes at
+        most 64 tokens (patches + latents) per frame; True up to 1024, on the tiled training attention core.
+        `lpips_loss_weight` and `decoder_v_space_loss` are the reference's; the first is only stored (any value constructs, `forward` needs 0.)."""
         config = dict(locals())
         super().__init__()
         self._record_config(config)
@@ -50,8 +66,8 @@ class VideoTokenizer(SaveLoad, nn.Module):
             if k in _UNSUPPORTED:
                 if v != _UNSUPPORTED[k]:
                     raise NotImplementedError(f'{k}={v!r} is outside the supported decode subset (reference defaults only)')
-            elif k not in ('lpips_loss_network', 'lpips_loss_weight', 'per_image_patch_mask_prob', 'use_loss_normalization'):
-                raise NotImplementedError(f'{k!r}: the tokenizer mirror implements the decode path only')
+            elif k not in ('lpips_loss_network', 'per_image_patch_mask_prob', 'use_loss_normalization'):
+                raise NotImplementedError(f'{k!r}: outside the subset the tokenizer mirror implements')
         assert image_size is not None or (image_height is not None and image_width is not None), \
             'either image_size or both image_height and image_width must be provided'
         if decoder_flow_steps < 1:
@@ -67,6 +83,10 @@ class VideoTokenizer(SaveLoad, nn.Module):
         self.decoder_pos_mlp_depth, self.decoder_flow_steps = decoder_pos_mlp_depth, decoder_flow_steps
         self.head_mlp_recipe = head_mlp_recipe
         self.wide_frames = bool(wide_frames)
+        self.train_wide_frames = bool(train_wide_frames)
+        self.lpips_loss_weight, self.decoder_v_space_loss = float(lpips_loss_weight), bool(decoder_v_space_loss)
+        self.use_loss_normalization = bool(kwargs.get('use_loss_normalization', True))
+        self.per_image_patch_mask_prob = tuple(kwargs.get('per_image_patch_mask_prob', (0., 0.9)))
         if attn_products not in ('fp32', 'bf16'):
             raise ValueError("attn_products must be 'fp32' or 'bf16'")
         if attn_products == 'bf16' and not self.wide_frames:
@@ -141,6 +161,19 @@ class VideoTokenizer(SaveLoad, nn.Module):
         trunk('encoder_transformer.', self.encoder_depth)
         reg('encoded_to_latents.weight', _linear_w(dl, D))
         _register(self, 'zero', torch.tensor(0.), buffer=True, persistent=False)
+        # LossNormalizer state of the training forward (dreamer4.py:629-669, 4037).  NOT persistent, unlike the reference's: the mirror's
+        # state_dict stays the parameter set the inference paths load; load_state_dict still takes the key from a reference checkpoint
+        if self.use_loss_normalization:
+            _register(self, _NORMALIZER_KEY, torch.ones(1), buffer=True, persistent=False)
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        if _NORMALIZER_KEY in state_dict:
+            state_dict = dict(state_dict)
+            state = state_dict.pop(_NORMALIZER_KEY)
+            if self.use_loss_normalization:
+                with torch.no_grad():
+                    self.recon_loss_normalizer.exp_avg_sq.copy_(torch.as_tensor(state).reshape(1))
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     @property
     def device(self):
@@ -154,7 +187,7 @@ class VideoTokenizer(SaveLoad, nn.Module):
     def _engine_tensors(self, mode):
         out = {}
         for k, v in list(self.named_parameters()) + list(self.named_buffers()):
-            if k in ('zero', 'mask_token'):
+            if k in ('zero', 'mask_token', _NORMALIZER_KEY):
                 continue
             enc = k.startswith(self._ENCODER_KEYS)
             if mode == 2 and enc:
@@ -292,6 +325,85 @@ class VideoTokenizer(SaveLoad, nn.Module):
             _lib.check(lib.d4_encoder_forward(eng, _lib.ptr(video[b0:b1]), b1 - b0, T, _lib.ptr(out[b0:b1]), self._stream()))
         return out
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError('the tokenizer mirror implements tokenize / decode; its training forward (reconstruction, LPIPS and '
-                                  'time-decorrelation losses, dreamer4.py:4239-4560) is out of scope')
+    # ------------------------------------------------------------------------------------------ training forward
+    def _train_weights(self):
+        return {**dict(self.named_parameters()), **{k: v for k, v in self.named_buffers() if k.endswith('inv_freq')}}
+
+    def _is_time(self, depth):
+        return [((i + 1) % self.time_block_every) == 0 for i in range(depth)]
+
+    def _normalize_recon(self, loss, update_ema, beta=0.95, eps=1e-6):
+        """LossNormalizer.forward (dreamer4.py:645-669), the arithmetic of DynamicsWorldModel._normalize_loss."""
+        if not self.use_loss_normalization:
+            return loss
+        buf = self.recon_loss_normalizer.exp_avg_sq
+        rms = buf.sqrt()
+        if update_ema:
+            with torch.no_grad():
+                buf.lerp_(loss.detach().reshape(buf.shape).square(), 1. - beta)
+        return loss / rms.clamp(min=eps).reshape(loss.shape)
+
+    def forward(self, video_or_image, return_latents=False, mask_patches=None, patch_mask=None, return_intermediates=False, update_loss_ema=None,
+                time_cache=None, return_time_cache=False, time_lens=None, aug_id=None, cfg_dropout_aug=None, byol_target_latents=None, *,
+                draws=None, generator=None):
+        """VideoTokenizer.forward (dreamer4.py:4239-4603) for the supported subset: video (b, c, t, h, w) or images (b, c, h, w) -> total loss, or
+        (total, (TokenizerLosses, reconstruction)) with `return_intermediates`, or the latents (with gradient) with `return_latents`.
+        `draws` = dict(patch_mask=, time_indices=, noise=) injects the random draws (parity runs; a missing entry is drawn); otherwise they
+        come from `generator` on the device.  More than 64 tokens per frame need `train_wide_frames=True`."""
+        from dreamer4_amd import trunk_ops
+        for name, val in (('time_lens', time_lens), ('time_cache', time_cache), ('byol_target_latents', byol_target_latents)):
+            if val is not None:
+                raise NotImplementedError(f'{name}= is outside the subset of the tokenizer training forward')
+        if return_time_cache:
+            raise NotImplementedError('return_time_cache= is outside the subset of the tokenizer training forward')
+        if aug_id not in (None, 0, False):
+            raise NotImplementedError('aug_id=: aug conditioning is not implemented')
+        if not return_latents and self.lpips_loss_weight > 0.:
+            raise NotImplementedError(f'lpips_loss_weight={self.lpips_loss_weight}: the LPIPS loss needs VGG weights this package does not carry; '
+                                      'construct the tokenizer with lpips_loss_weight=0.')
+        dev = self.device
+        if dev.type != 'cuda' or video_or_image.device.type != 'cuda':
+            raise _lib.D4Error('VideoTokenizer runs only on an MI355X (HIP) device: there is no CPU fallback')
+        mask_patches = (self.training and not return_latents) if mask_patches is None else mask_patches
+        is_image = video_or_image.ndim == 4
+        video = video_or_image.unsqueeze(2) if is_image else video_or_image
+        assert video.ndim == 5, 'video must be (batch, channels, time, height, width)'
+        video = video.float().contiguous()
+        B, Cc, T, H, W = video.shape
+        assert Cc == self.channels, f'expected {self.channels} channels, got {Cc}'
+        if (H, W) != (self.image_height, self.image_width):
+            raise NotImplementedError('training at a resolution other than the one given to the constructor is not implemented')
+        ps = self.patch_size
+        nh, nw = H // ps, W // ps
+        draws = dict(draws or {})
+        if patch_mask is None:
+            patch_mask = draws.get('patch_mask')
+        if patch_mask is None and mask_patches:                                # dreamer4.py:4336-4342
+            lo, hi = self.per_image_patch_mask_prob
+            prob = torch.rand(B, T, device=dev, generator=generator) * (hi - lo) + lo
+            patch_mask = torch.bernoulli(prob[:, :, None, None].expand(B, T, nh, nw), generator=generator) == 1.
+        if patch_mask is not None:
+            patch_mask = patch_mask.to(dev).bool()
+            assert patch_mask.shape == (B, T, nh, nw), f'patch_mask must be {(B, T, nh, nw)}'
+        Wt = self._train_weights()
+        cfg = dict(patch_size=ps, num_latent_tokens=self.num_latent_tokens, encoder_is_time=self._is_time(self.encoder_depth), wide=self.train_wide_frames)
+        if return_latents:
+            return trunk_ops.tokenizer_latents(Wt, video, patch_mask=patch_mask, **cfg)
+        time_indices, noise = draws.get('time_indices'), draws.get('noise')
+        if time_indices is None:
+            time_indices = torch.randint(0, self.decoder_flow_steps, (B,), device=dev, generator=generator)
+        if noise is None:
+            noise = torch.randn(video.shape, device=dev, generator=generator)
+        noise = noise.to(dev).float().reshape(video.shape).contiguous()
+        recon, latents, recon_video = trunk_ops.tokenizer_losses(
+            Wt, video, draws=dict(patch_mask=patch_mask, time_indices=time_indices.to(dev).long(), noise=noise), decoder_is_time=self._is_time(self.decoder_depth),
+            decoder_flow_steps=self.decoder_flow_steps, decoder_pos_mlp_depth=self.decoder_pos_mlp_depth, head_mlp_recipe=self.head_mlp_recipe,
+            v_space=self.decoder_v_space_loss, return_recon_video=return_intermediates, **cfg)
+        recon = self._normalize_recon(recon, self.training if update_loss_ema is None else update_loss_ema)
+        total = recon                                                          # every other term of dreamer4.py:4576-4589 is zero in the subset
+        if not return_intermediates:
+            return total
+        z = self.zero
+        if is_image:
+            recon_video = recon_video.squeeze(2)
+        return total, VideoTokenizerIntermediates(TokenizerLosses(recon, z, z, z, z, z, z, z, z, z, z, z), recon_video)

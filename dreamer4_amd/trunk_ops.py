@@ -11,7 +11,8 @@ implementations + registered autograd, same C-ABI operators, same results).  The
 block keeps the workspace its forward ran in and the backward (`*_backward_saved`) recomputes nothing; with D4_TRUNK_SAVE_FORWARD=0 the
 backward recomputes the forward intermediates and nothing but the inputs is kept alive between the two passes.  `transformer` composes
 the AxialSpaceTimeTransformer (dreamer4.py:2927-3267), `world_model_prediction` the dynamics model's `get_prediction`
-(dreamer4.py:7156-7287), `dynamics_flow_losses` / `dynamics_agent_losses` the losses of the training forward (dreamer4.py:7335-7598).
+(dreamer4.py:7156-7287), `dynamics_flow_losses` / `dynamics_agent_losses` the losses of the training forward (dreamer4.py:7335-7598), `tokenizer_latents` /
+`tokenizer_losses` the VideoTokenizer's training forward (dreamer4.py:4239-4603) on the pixel-side operators of csrc/tok_train.hip.
 fp32, HIP device only — there is no CPU fallback.  Not used by the imagination path."""
 from __future__ import annotations
 
@@ -569,6 +570,144 @@ def dynamics_flow_losses(W, latents, noise, signal_levels, step_sizes_log2, shor
     shortcut_losses = F.mse_loss(shortcut_pred, target, reduction='none') * (1. - tt) ** 2
     fl, sh = sel(flow_losses).mean(), sel(shortcut_losses).mean()
     return (fl, sh, agent_embed) if return_agent_embed else (fl, sh)
+
+
+# ------------------------------------------------------------------------------------------------ the video tokenizer, training form
+def _lin(x, w, b=None):
+    return torch.ops.d4hip.linear(x, w, b, None, 0, 0.)
+
+
+# The pixel-side operators (csrc/tok_train.hip) on the route the blocks take: plain autograd.Functions over the implementations of dreamer4_amd/ops.py
+# by default, their `torch.ops.d4hip.*` registrations with D4_TRUNK_DISPATCHER=1 (same C entry points, same results).
+class _LayerNormNoBias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, eps):
+        ctx.save_for_backward(x, weight)
+        ctx.eps = eps
+        return _ops.layernorm_nobias_impl(x, weight, eps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dx, dw = _ops.layernorm_nobias_backward_impl(x, dy, weight, ctx.eps)
+        return dx, dw, None
+
+
+class _MaskRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tokens, mask, token):
+        ctx.save_for_backward(mask)
+        return _ops.mask_rows_impl(tokens, mask, token)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dtok = _ops.mask_rows_backward_impl(dy, ctx.saved_tensors[0])
+        return dx, None, dtok
+
+
+class _ReconLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, recon_rows, video, noise, times, patch_size, v_space):
+        loss, d_rows = _ops.recon_loss_impl(recon_rows, video, noise, times, patch_size, v_space)
+        ctx.save_for_backward(d_rows)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        return ctx.saved_tensors[0] * d_loss, None, None, None, None, None
+
+
+def video_to_patches(video, patch_size):
+    """'b c t (h p1) (w p2) -> b t h w (p1 p2 c)' (dreamer4.py:3838-3844, 3896); data, no gradient."""
+    return torch.ops.d4hip.video_to_patches(video, patch_size) if via_dispatcher() else _ops.video_to_patches_impl(video, patch_size)
+
+
+def flow_noised_patches(video, noise, times, patch_size):
+    """Patch rows of noise.lerp(video, times[b]) in one pass (dreamer4.py:4457 + 3896); data, no gradient."""
+    return torch.ops.d4hip.flow_noised_patches(video, noise, times, patch_size) if via_dispatcher() else _ops.flow_noised_patches_impl(video, noise, times, patch_size)
+
+
+def layernorm_nobias(x, weight, eps=1e-5):
+    """nn.LayerNorm(dim, bias=False) (dreamer4.py:114), differentiable in x and weight."""
+    return torch.ops.d4hip.layernorm_nobias(x, weight, eps) if via_dispatcher() else _LayerNormNoBias.apply(x, weight, eps)
+
+
+def mask_rows(tokens, mask, token):
+    """Rows of `tokens` whose `mask` entry is set replaced by `token` (dreamer4.py:4344), differentiable in tokens and token."""
+    return torch.ops.d4hip.mask_rows(tokens, mask, token) if via_dispatcher() else _MaskRows.apply(tokens, mask, token)
+
+
+def recon_loss(recon_rows, video, noise, times, patch_size, v_space=True):
+    """The reconstruction loss on the decoder's patch rows (dreamer4.py:4469-4474, 4516), differentiable in recon_rows."""
+    if via_dispatcher():
+        return torch.ops.d4hip.recon_loss(recon_rows, video, noise, times, patch_size, bool(v_space))[0]
+    return _ReconLoss.apply(recon_rows, video, noise, times, patch_size, bool(v_space))
+
+
+def _decoder_pos_embedding(W, nh, nw, n_layers, recipe, dev):
+    """to_decoder_pos_emb on the linspace(-1, 1) grid of patch coordinates (dreamer4.py:3617-3625): (nh * nw, dim).  Parameter-sized work: the
+    2-wide input of the first layer is normalised elementwise and zero-padded to the 4-float granularity of the HIP Linear."""
+    from torch.nn import functional as F
+    eps = torch.finfo(torch.float32).eps
+    pre = 'decoder.to_decoder_pos_emb.'
+    gy, gx = torch.meshgrid(torch.linspace(-1., 1., nh, device=dev), torch.linspace(-1., 1., nw, device=dev), indexing='ij')
+    x = torch.stack((gy, gx), dim=-1).reshape(nh * nw, 2)
+    pad_lin = lambda t, w, b: _lin(F.pad(t, (0, 2)), F.pad(w, (0, 2)), b)
+    for i in range(n_layers):
+        last, lin = i == n_layers - 1, (pad_lin if i == 0 else _lin)
+        if recipe == 'pre_rms':
+            nw_ = W[f'{pre}layers.{i}.0.weight']
+            x = x * torch.rsqrt(x.square().mean(dim=-1, keepdim=True) + eps) * nw_ if i == 0 else torch.ops.d4hip.rmsnorm(x, nw_, eps)
+            x = lin(x, W[f'{pre}layers.{i}.1.weight'], W[f'{pre}layers.{i}.1.bias'])
+            if not last:
+                x = F.silu(x)
+        elif last:
+            x = lin(x, W[f'{pre}layers.{i}.weight'], W[f'{pre}layers.{i}.bias'])
+        else:
+            x = lin(x, W[f'{pre}layers.{i}.0.weight'], W[f'{pre}layers.{i}.0.bias'])
+            x = F.silu(F.layer_norm(x, x.shape[-1:], W[f'{pre}layers.{i}.1.weight'], W[f'{pre}layers.{i}.1.bias'], 1e-5))
+    return x
+
+
+def tokenizer_latents(W, video, *, patch_size, num_latent_tokens, encoder_is_time, patch_mask=None, wide=False):
+    """The encoder half of VideoTokenizer.forward (dreamer4.py:4309-4425) for training: video (b, c, t, H, W) -> latents (b, t, n, dim_latent) in
+    (-1, 1), differentiable in every encoder parameter.  `patch_mask` (b, t, nh, nw) bool: those patch tokens are replaced by `mask_token`."""
+    b, _, t = video.shape[:3]
+    rows = video_to_patches(video, patch_size)
+    x = layernorm_nobias(_lin(rows, W['patch_to_tokens.1.weight'], W['patch_to_tokens.1.bias']), W['patch_to_tokens.2.weight'], 1e-5)
+    if patch_mask is not None:
+        x = mask_rows(x, patch_mask, W['mask_token'])
+    d = x.shape[-1]
+    tokens = torch.cat((x.reshape(b, t, -1, d), W['latent_tokens'].expand(b, t, -1, -1)), dim=2)                 # [patches | latents]  dreamer4.py:4375
+    tokens = transformer(W, tokens, is_time=encoder_is_time, num_special=num_latent_tokens, pre='encoder_transformer.', wide=wide)
+    return _lin(tokens[:, :, -num_latent_tokens:], W['encoded_to_latents.weight']).tanh()
+
+
+def tokenizer_losses(W, video, *, draws, patch_size, num_latent_tokens, encoder_is_time, decoder_is_time, decoder_flow_steps, decoder_pos_mlp_depth,
+                     head_mlp_recipe='pre_rms', v_space=True, wide=False, return_recon_video=False):
+    """The reconstruction loss of VideoTokenizer.forward (dreamer4.py:4309-4516: flow decoder, no LPIPS / auxiliary losses) with backward through both
+    trunks.  W: the tokenizer's parameters by reference state_dict key; video (b, c, t, H, W); draws = dict(patch_mask (b, t, nh, nw) bool or None,
+    time_indices (b,) in [0, decoder_flow_steps), noise like the video).  The passes over pixels are the operators of csrc/tok_train.hip: patch rows of
+    the video and of noise.lerp(video, t), the LayerNorm of both patch embeddings, the mask rows, and the fused loss, which reads the video through the
+    patch permutation (nothing is un-patchified).  Returns (recon_loss, latents, recon_video or None)."""
+    b, c, t, H, Wd = video.shape
+    nh, nw = H // patch_size, Wd // patch_size
+    latents = tokenizer_latents(W, video, patch_size=patch_size, num_latent_tokens=num_latent_tokens, encoder_is_time=encoder_is_time,
+                                patch_mask=draws.get('patch_mask'), wide=wide)
+    time_indices, noise = draws['time_indices'], draws['noise']
+    times = time_indices.float() / decoder_flow_steps
+    lat = _lin(latents, W['latents_to_decoder.weight']) + W['time_embed.weight'][time_indices][:, None, None]      # dreamer4.py:4151-4157
+    rows = flow_noised_patches(video, noise, times, patch_size)
+    img = layernorm_nobias(_lin(rows, W['noised_patch_to_tokens.1.weight'], W['noised_patch_to_tokens.1.bias']),
+                                           W['noised_patch_to_tokens.2.weight'], 1e-5)
+    pos = _decoder_pos_embedding(W, nh, nw, decoder_pos_mlp_depth + 2, head_mlp_recipe, video.device)
+    d = img.shape[-1]
+    tokens = torch.cat((img.reshape(b, t, nh * nw, d) + pos, lat), dim=2)                                         # [patches | latents]  dreamer4.py:3654
+    tokens = transformer(W, tokens, is_time=decoder_is_time, num_special=1, pre='decoder.transformer.', wide=wide)
+    recon_rows = _lin(tokens[:, :, :nh * nw], W['decoder.tokens_to_patch.0.weight'], W['decoder.tokens_to_patch.0.bias']).reshape(b, t, nh, nw, -1)
+    loss = recon_loss(recon_rows, video, noise, times, patch_size, v_space)
+    recon_video = _ops.patches_to_video_impl(recon_rows.detach(), c, patch_size) if return_recon_video else None
+    return loss, latents, recon_video
 
 
 # ------------------------------------------------------------------------------------------------ agent-token losses of the training forward

@@ -761,6 +761,28 @@ int d4_ppo_policy_loss(const float* logits, int ld, const int64_t* actions, cons
 int d4_gae(const float* rewards, const float* values, const int64_t* lens, const uint8_t* is_truncated,
            const uint8_t* terminals, float gamma, float lam, int batch, int time, float* returns,
            void* stream);
+/* Pixel-side operators of the VideoTokenizer training forward (dreamer4.py:4239-4603; csrc/tok_train.hip).  Patch rows are
+ * [(b t nh nw)][(p1 p2 c)] of a video (b c t (nh p1) (nw p2)); the patch row C * ps * ps and every `dim` must be multiples of 4, row pointers 16-byte
+ * aligned.  No allocation, no host synchronisation; column sums and the loss sum go through per-block partials in the caller's `part` and one
+ * fixed-order reduction (no float atomics): equal inputs give equal bits.
+ *   d4_flow_noised_patches   rows = patch rows of noise.lerp(video, t[b]) (torch's lerp: t = 1 gives d4_video_patches' bits, t = 0 the noise's).
+ *                            noise and t both null: the video's own patch rows, d4_video_patches' bits.
+ *   d4_tok_rows_part_floats  floats of `part` the two row backward operators need for `rows` rows of `dim`.
+ *   d4_layernorm_rows_bwd    backward of y = LayerNorm(x) * g (no bias, biased variance) on x [rows][ldx], dy [rows][dim]: dx [rows][ldx] and
+ *                            dg [dim] = sum over rows of dy * xhat.  dim <= 1024.
+ *   d4_mask_rows_fwd         y [rows][dim] = token where mask[row] != 0, x elsewhere.
+ *   d4_mask_rows_bwd         dx = dy on unmasked rows, 0 on masked rows; dtoken [dim] = sum of dy over the masked rows.  dim <= 1024.
+ *   d4_recon_loss_fwd_bwd    loss[0] = mean((pred - target)^2) over all B C T H W elements and d_rows = d loss / d recon_rows.  v_space 1:
+ *                            pred = (recon - noise.lerp(video, t)) / (1 - t), target = video - noise (t[b] < 1); v_space 0: pred = recon,
+ *                            target = video (noise and t may be null).  part: at least 1024 floats. */
+int d4_flow_noised_patches(const float* video, const float* noise, const float* t, float* rows, int B, int C, int T, int nh, int nw, int ps, void* stream);
+size_t d4_tok_rows_part_floats(int rows, int dim);
+int d4_layernorm_rows_bwd(const float* x, int ldx, const float* dy, const float* g, float* dx, float* dg, float* part, size_t part_floats, int rows, int dim,
+                          float eps, void* stream);
+int d4_mask_rows_fwd(const float* x, const uint8_t* mask, const float* token, float* y, int rows, int dim, void* stream);
+int d4_mask_rows_bwd(const float* dy, const uint8_t* mask, float* dx, float* dtoken, float* part, size_t part_floats, int rows, int dim, void* stream);
+int d4_recon_loss_fwd_bwd(const float* recon_rows, const float* video, const float* noise, const float* t, int B, int C, int T, int nh, int nw, int ps, int v_space,
+                          float* loss, float* d_rows, float* part, size_t part_floats, void* stream);
 
 #ifdef __cplusplus
 }
