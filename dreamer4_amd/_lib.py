@@ -196,6 +196,8 @@ SYMBOLS = {
     'd4_attn_out_cols': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 2 + [_P] + [_I] * 3 + [_F] + [_I] * 3 + [_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'd4_frame_pool': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _I, _I, _I, _F, _P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'd4_frame_pool_tail': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'd4_lqap_in': (_I, [_P, _I, _P, _I, _P, _P, _P, _P] + [_I] * 5 + [_F, _P]),
+    'd4_lqap_out': (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I] + [_I] * 5 + [_P]),
     'd4_debug_last_form': (C.c_char_p, [C.c_char_p]),
     'd4_debug_forms': (_I, [C.c_char_p, _I, C.POINTER(C.c_char_p)]),
     'd4_train_attn_core_plane_floats': (C.c_size_t, [_I] * 3),

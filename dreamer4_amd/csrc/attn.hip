@@ -306,7 +306,7 @@ __global__ __launch_bounds__(256) void space_attn_kernel(SmallAttnArgs p) {
 // The kernel is a template over the number of 16-row query tiles QT and key tiles KT: <1, 1> is the within-frame self attention (value residual,
 // special-token mask, belief projection, restricted query set), <1, 2> / <2, 1> / <1, 1> the small cross forms (learned-query pools in / out with up
 // to 32 latents or queries, the agent token's cross attention).
-template <int QT, int KT, int NWB = 4>            // NWB waves (= (group, head) units) per block: 2 for the 64-key form, whose V' tiles are 17 KB per wave
+template <int QT, int KT, int NWB = 4, bool QCOMPACT = false>            // NWB waves (= (group, head) units) per block: 2 for the 64-key form, whose V' tiles are 17 KB per wave
 __global__ __launch_bounds__(NWB * 64) void attn_mfma_kernel(SmallAttnArgs p) {
     __shared__ __attribute__((aligned(16))) float Vs_all[NWB][KT * 16 * SM_LDV];
     __shared__ __attribute__((aligned(16))) float kinv_all[NWB][KT * 16];
@@ -318,10 +318,11 @@ __global__ __launch_bounds__(NWB * 64) void attn_mfma_kernel(SmallAttnArgs p) {
     float* op = p.out ? p.out + g * p.o_group_stride + h * 64 : nullptr;
     uint16_t* ob = p.out_b ? p.out_b + g * p.o_group_stride + h * 64 : nullptr;
     const int64_t ois = p.o_item_stride;
-    attn_mfma_unit<QT, KT>(p, g, h, lane, Vs_all[w], kinv_all[w], vinv_all[w], [&](int orank, int t, int tok, float v) {
+    auto store = [&](int orank, int t, int tok, float v) {
         if (op) op[(int64_t)orank * ois + 16 * t + tok] = v;
         if (ob) ob[(int64_t)orank * ois + 16 * t + tok] = bf16_bits(v);
-    });
+    };
+    attn_mfma_unit<QT, KT, decltype(store), AttnKvGlobal, QCOMPACT>(p, g, h, lane, Vs_all[w], kinv_all[w], vinv_all[w], store);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -458,8 +459,10 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
                              al4(p.v, p.v_group_stride, p.v_item_stride) && (!p.vres || al4(p.vres, p.r_group_stride, p.r_item_stride)) &&
                              ((uintptr_t)p.k_gamma % 16) == 0;
         *wrote_b = mfma_ok;
+        D4_REQUIRE(!p.q_compact || (mfma_ok && p.q_hi > 0 && !p.q_last), "small_attn: compact queries need the matrix-pipe form (head dim 64, 16-byte aligned rows) and a query range");
         note_form(FAM_SMALL_ATTN, mfma_ok ? "attn_mfma_kernel<1,1>" : p.dh == 64 ? "space_attn_kernel<64>" : p.dh == 32 ? "space_attn_kernel<32>" : "space_attn_kernel<16>");
-        if (mfma_ok) D4_GLUE_LAUNCH(GL_SPACE_ATTN, sp_bytes, (attn_mfma_kernel<1, 1>), dim3(cdiv(waves, 4)), block, 0, stream, p);
+        if (mfma_ok && p.q_compact) D4_GLUE_LAUNCH(GL_SPACE_ATTN, sp_bytes, (attn_mfma_kernel<1, 1, 4, true>), dim3(cdiv(waves, 4)), block, 0, stream, p);
+        else if (mfma_ok) D4_GLUE_LAUNCH(GL_SPACE_ATTN, sp_bytes, (attn_mfma_kernel<1, 1>), dim3(cdiv(waves, 4)), block, 0, stream, p);
         else if (p.dh == 64) D4_GLUE_LAUNCH(GL_SPACE_ATTN, sp_bytes, space_attn_kernel<64>, dim3(waves), block, 0, stream, p);
         else if (p.dh == 32) hipLaunchKernelGGL(space_attn_kernel<32>, dim3(waves), block, 0, stream, p);
         else hipLaunchKernelGGL(space_attn_kernel<16>, dim3(waves), block, 0, stream, p);
@@ -467,6 +470,7 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
         return 0;
     }
     // no form below implements the restricted query set: refuse it instead of writing every query row
+    D4_REQUIRE(!p.q_compact, "small_attn: compact queries are implemented for self attention over 8..16 tokens only");
     D4_REQUIRE(p.q_lo == 0 && p.q_hi == 0, "small_attn: the query restriction (q_lo=%d, q_hi=%d) is implemented for self attention over 8..16 tokens only (nq=%d, nk=%d)",
                p.q_lo, p.q_hi, p.nq, p.nk);
     // algorithmic bytes: a batch-independent operand (group stride 0) is counted once

@@ -39,10 +39,28 @@ __device__ __forceinline__ void online_softmax_step(f32x4 (&pr)[4], float mt, fl
 }
 
 constexpr int SM_LDV = 68;
+// Where the key / value operands of attn_mfma_unit come from.  A source fills, for key tile kt, this lane's fragments of key row j = 16 kt + (l & 15):
+// k4[s] / v4[s] = features 16 s + 4 (l >> 4) .. + 3 of head h (zeros when !ok).  AttnKvGlobal reads them from p.k / p.v (every stand-alone form);
+// a fused kernel that has just computed the rows on the matrix pipe hands them over in registers (latent_ends.hip).
+struct AttnKvGlobal {
+    __device__ __forceinline__ void operator()(const SmallAttnArgs& p, int g, int kt, int j, bool ok, int hoff, f32x4 (&k4)[4], f32x4 (&v4)[4]) const {
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        const float* kp = p.k + g * p.k_group_stride + (int64_t)j * p.k_item_stride + hoff;
+        const float* vp = p.v + g * p.v_group_stride + (int64_t)j * p.v_item_stride + hoff;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            k4[s] = ok ? *reinterpret_cast<const f32x4*>(kp + 16 * s) : zero;
+            v4[s] = ok ? *reinterpret_cast<const f32x4*>(vp + 16 * s) : zero;
+        }
+    }
+};
+
 // One (group g, head h) on the calling wave.  Vs [KT * 16][SM_LDV], kinv_s / vinv_s [KT * 16]: this wave's LDS scratch.
 // store(orank, t, tok, value): output row `orank` (after the query-set restriction), feature 16 t + tok of head h.
-template <int QT, int KT, class Store>
-__device__ __forceinline__ void attn_mfma_unit(const SmallAttnArgs& p, int g, int h, int lane, float* Vs, float* kinv_s, float* vinv_s, Store store) {
+// QCOMPACT (SmallAttnArgs::q_compact; a form of its own so that every other instantiation keeps its code): q and gate hold the rows [q_lo, q_hi) alone.
+template <int QT, int KT, class Store, class KvSource = AttnKvGlobal, bool QCOMPACT = false>
+__device__ __forceinline__ void attn_mfma_unit(const SmallAttnArgs& p, int g, int h, int lane, float* Vs, float* kinv_s, float* vinv_s, Store store,
+                                               KvSource kv_source = KvSource{}) {
     const int nq = p.nq, nk = p.nk;
     const int tok = lane & 15, kq = lane >> 4;
     const int hoff = h * 64 + 4 * kq;
@@ -54,13 +72,16 @@ __device__ __forceinline__ void attn_mfma_unit(const SmallAttnArgs& p, int g, in
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         const int i = 16 * qt + tok;
-        const float* qp = p.q + g * p.q_group_stride + (int64_t)i * p.q_item_stride + hoff;
+        const int qoff = QCOMPACT ? p.q_lo : 0;                              // (compact q / gate: the restricted rows alone, in rank order)
+        const bool q_ok = QCOMPACT ? (i >= p.q_lo && i < p.q_hi) : i < nq;
+        const float* qp = p.q + g * p.q_group_stride + (int64_t)(i - qoff) * p.q_item_stride + hoff;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) q4[qt][s] = i < nq ? *reinterpret_cast<const f32x4*>(qp + 16 * s) : zero;
+        for (int s = 0; s < 4; ++s) q4[qt][s] = q_ok ? *reinterpret_cast<const f32x4*>(qp + 16 * s) : zero;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int qi = 16 * qt + 4 * kq + r;
-            gate_logit[qt][r] = (p.gate && qi < nq) ? p.gate[g * p.g_group_stride + (int64_t)qi * p.g_item_stride + h] : 0.f;
+            const bool g_ok = QCOMPACT ? (qi >= p.q_lo && qi < p.q_hi) : qi < nq;
+            gate_logit[qt][r] = (p.gate && g_ok) ? p.gate[g * p.g_group_stride + (int64_t)(qi - qoff) * p.g_item_stride + h] : 0.f;
         }
     }
     f32x4 gm[4];
@@ -70,16 +91,11 @@ __device__ __forceinline__ void attn_mfma_unit(const SmallAttnArgs& p, int g, in
     for (int kt = 0; kt < KT; ++kt) {
         const int j = 16 * kt + tok;
         const bool ok = j < nk;
-        const float* kp = p.k + g * p.k_group_stride + (int64_t)j * p.k_item_stride + hoff;
-        const float* vp = p.v + g * p.v_group_stride + (int64_t)j * p.v_item_stride + hoff;
         const float* rp = p.vres ? p.vres + g * p.r_group_stride + (int64_t)j * p.r_item_stride + hoff : nullptr;
         f32x4 v4[4], r4[4];
+        kv_source(p, g, kt, j, ok, hoff, k4[kt], v4);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            k4[kt][s] = ok ? *reinterpret_cast<const f32x4*>(kp + 16 * s) : zero;
-            v4[s] = ok ? *reinterpret_cast<const f32x4*>(vp + 16 * s) : zero;
-            r4[s] = (ok && rp) ? *reinterpret_cast<const f32x4*>(rp + 16 * s) : zero;
-        }
+        for (int s = 0; s < 4; ++s) r4[s] = (ok && rp) ? *reinterpret_cast<const f32x4*>(rp + 16 * s) : zero;
         float wmix = 0.f;
         if (p.vres && ok) wmix = sigmoidf(p.mix[g * p.m_group_stride + (int64_t)j * p.m_item_stride + h]);
         float ksq = 0.f, vsq = 0.f;

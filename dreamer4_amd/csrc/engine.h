@@ -66,7 +66,7 @@ struct d4_engine {
     // captured decode frames: key = (batch, num_steps, step_log2, has_tasks, history bucket) -> executable graph of the K+1 evaluations.
     // The history bucket (d4::time_history_bucket of the frame offset) is part of the key because the time-attention launcher picks its
     // kernel by it: a replayed frame runs exactly the kernels the same frame runs when enqueued eagerly.
-    struct FrameGraph { int B, K, sl, tasks, bucket, lean; hipGraphExec_t exec; };      // lean: the clean evaluation kept the agent row alone (engine_forward: need_pred)
+    struct FrameGraph { int B, K, sl, tasks, bucket, variant; hipGraphExec_t exec; };   // variant: bit 0 the clean evaluation kept the agent row alone (engine_forward: need_pred), bits 1.. the latent-end forms (d4_rollout)
     std::vector<FrameGraph> graphs;
     int graph_max_rows = 4096;
     bool warm = false;
@@ -131,6 +131,12 @@ struct d4_engine {
 
     // ---- prepared weight images (workspace)
     std::vector<float*> proj_w, proj_b;
+    // second image of the LAST layer's fused projection, column groups contiguous: [k | v | mix] then [q | head gates] (rows of proj_w[depth - 1], same
+    // folded values; proj_bc the biases in the same order).  A denoise evaluation projects the first group on every row and the second on the
+    // compact rows only (engine_forward: compact_q); null when the engine never takes that path
+    float *proj_wc = nullptr, *proj_bc = nullptr;
+    float* qc = nullptr;                   // [Fr * (ns + 1)][ldqc]: q | head gates of the compact rows
+    int ldqc = 0;
     std::vector<d4::FfPrep> ffp;           // depth layers + special ff at index depth
     std::vector<float*> pq_w, pkv_w;
     // bf16 engine, wide key projection (round 6): pkq_w[l] = the folded key weights of pools l .. depth-2 followed by pool l's query weights,

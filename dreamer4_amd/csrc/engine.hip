@@ -43,6 +43,12 @@ int engine_layout(d4_engine* e, bool assign) {
         e->proj_w[l] = fl((size_t)N * D);
         e->proj_b[l] = fl(N);
     }
+    e->proj_wc = nullptr; e->proj_bc = nullptr;
+    const bool compact_q_image = !e->encoder && !e->decoder && depth >= 2;      // (a flag, not the pointer: the sizing pass assigns none)
+    if (compact_q_image) {
+        e->proj_wc = fl((size_t)e->Nproj * D);
+        e->proj_bc = fl(e->Nproj);
+    }
     e->ffp.assign(depth + 1, FfPrep{});
     for (int l = 0; l <= depth; ++l) {
         e->ffp[l].w1 = fl((size_t)2 * e->inner_pad * D);
@@ -106,6 +112,8 @@ int engine_layout(d4_engine* e, bool assign) {
     e->xfc = fl(Fr * KR * D);
     e->xpool_c = fl(Fr * KR * D);
     e->att_c = fl(Fr * KR * hd);
+    e->ldqc = (hd + c.attn_heads + 3) / 4 * 4;
+    e->qc = compact_q_image ? fl(Fr * KR * e->ldqc) : nullptr;
     if (e->encoder) {
         const size_t P = e->P, dp = e->dim_patch;
         e->t2p_wf = fl((size_t)dl * D);
@@ -605,6 +613,16 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
         if ((rc = copy_rows(a.mix_b, h, e->proj_b[l] + 3 * hd + h, h, 1, h, s))) return rc;
         if (l == 0 && (rc = fold_attn_rows(w + (size_t)(3 * hd + 2 * h) * D, D, e->vres_w, e->vres_norm, hd, s))) return rc;
         if ((rc = prep_ff(e->layer_ff[l], e->ffp[l], e, s))) return rc;
+        if (l == c.depth - 1 && e->proj_wc) {
+            // the same rows regrouped: [k | v | mix] [q | gates]
+            float* wc = e->proj_wc;
+            if ((rc = fill_f32(e->proj_bc, 0.f, N, s))) return rc;
+            if ((rc = copy_rows(w + (size_t)hd * D, D, wc, D, 2 * hd, D, s))) return rc;
+            if ((rc = copy_rows(w + (size_t)(3 * hd + h) * D, D, wc + (size_t)2 * hd * D, D, h, D, s))) return rc;
+            if ((rc = copy_rows(w, D, wc + (size_t)(2 * hd + h) * D, D, hd, D, s))) return rc;
+            if ((rc = copy_rows(w + (size_t)3 * hd * D, D, wc + (size_t)(3 * hd + h) * D, D, h, D, s))) return rc;
+            if ((rc = copy_rows(a.mix_b, h, e->proj_bc + 2 * hd, h, 1, h, s))) return rc;
+        }
     }
     if (!e->decoder && (rc = prep_ff(e->sff, e->ffp[c.depth], e, s))) return rc;
     for (int p = 0; p < c.depth; ++p) {
@@ -752,6 +770,10 @@ static int ff_block(d4_engine* e, const FfPrep& fp, const float* out_b, const fl
 int g_pool_wide_keys = 1;             // test hook d4_debug_switch("pool_wide_keys")
 int g_rollout_clean_agent_row = 1;    // test hook d4_debug_switch("rollout_clean_agent_row"): 0 = the rollout's clean evaluation computes the latent prediction too
 int g_rollout_batched_heads = 1;      // test hook d4_debug_switch("rollout_batched_heads"): 0 = value and reward heads after every frame
+// The denoise evaluations' latent-token ends (fp32 engine, dynamics mode): test hooks, 0 = the launches they replace, same bits
+int g_lqap_in_fused = 1;              // d4_debug_switch("lqap_in_fused"): latents -> K | V -> learned-query attention in one per-frame kernel (latent_ends.hip)
+int g_lqap_out_fused = 1;             // d4_debug_switch("lqap_out_fused"): learned-query attention -> latent prediction in one per-frame kernel
+int g_last_layer_compact_q = 1;       // d4_debug_switch("last_layer_compact_q"): a denoise evaluation's last layer projects q | head gates on the compact rows only
 unsigned g_launch_count = 0;          // kernel launches so far (common.h: D4_LAUNCH_CHECK; read / reset through d4_debug_switch("launch_count"))
 // rule_M > 0 (the final pool of an evaluation that keeps the agent row alone): the rows the same pool has when the spatial rows are kept too — every
 // product and the mix are dispatched as for that row count (GemmArgs::rule_M), so the rows computed carry the bits they have there
@@ -873,6 +895,19 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     const int n = c.num_latent_tokens, dl = c.dim_latent, ns = c.num_spatial_tokens;
     const int Fr = B * Tq, M = Fr * S;
     const bool denoise_only = !need_agent && !e->encoder && !e->decoder;        // dynamics evaluation whose last layer only feeds the spatial rows
+    const bool fp32_engine = !e->bf16 || e->split;                              // every product of the latent ends on the f32-input kernels
+    // Would the dispatcher run this product of the evaluation on the LDS-DMA family (gemm2.hip)?  The kernels that replace or split such a product carry
+    // that family's bits.  The call is described as engine_gemm hands it to gemm(): its flags, rule_M and, on a split-operand engine, the weight's planes.
+    auto tiled_family = [e](int M_, int N_, int K_, int flags, const float* W, int rule_M = 0) {
+        GemmArgs g{};
+        g.M = M_; g.N = N_; g.K = K_; g.lda = K_; g.ldw = K_; g.ldc = N_; g.flags = flags; g.rms_eps = RMS_EPS; g.rule_M = rule_M; g.W = W;
+        if (e->bf16) {
+            for (const auto& m : e->mirrors)
+                if (W >= m.src && W < m.src + m.n) { g.Wb = m.dst + (W - m.src); break; }
+            if (g.Wb && e->split) { g.wplane = (int64_t)e->bf16_cap; if (!gemm_x3_applicable(g)) { g.Wb = nullptr; g.wplane = 0; } }
+        }
+        return gemm_rule_takes_v2(g);
+    };
     int rc;
     if (e->h2) {                              // fp16x2 mode: every slab is rewritten by this evaluation -> no row exponent of the last one is valid
         e->aexp_M = (size_t)M;
@@ -903,6 +938,11 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     // ---- latents -> spatial tokens (LearnedQueriesAttentionPool, D4:7168; a plain Linear when there is one per latent)
     if (same_len) {
         if ((rc = gemm_simple(latents, dl, e->lin_w, dl, e->space, D, Fr * n, D, dl, 0, e->lin_b, nullptr, 0, s))) return rc;
+    } else if (g_lqap_in_fused && fp32_engine && !g_small_attn_wide && lqap_in_applicable(h, c.attn_dim_head, n, ns, dl) && frame_fused_frames_ok(Fr) &&
+               tiled_family(Fr * n, 2 * hd, dl, GEMM_RMS_ROWSCALE, e->lin_kv_w)) {
+        // one workgroup per frame: K | V of the latents on the matrix pipe, straight into the learned queries' attention (e->lkv is not written)
+        if ((rc = lqap_in(latents, dl, e->lin_kv_w, dl, e->lin_q, e->lin_gate, e->lq_in.k_gamma, e->latt, Fr, h, n, ns, dl, RMS_EPS, s))) return rc;
+        if ((rc = gemm_simple(e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0, s))) return rc;
     } else {
     if ((rc = gemm_simple(latents, dl, e->lin_kv_w, dl, e->lkv, 2 * hd, Fr * n, 2 * hd, dl, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0, s))) return rc;
     {
@@ -945,6 +985,20 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         const AttnW& a = e->layer_attn[l];
         float* P = l == 0 ? e->proj0 : e->proj;
         const int ldp = l == 0 ? e->Nproj0 : e->Nproj;
+        // Last layer of a denoise evaluation (the compact tail below): its attention reads the queries and head gates of the ns spatial rows only, so
+        // q | gates are projected on the compact rows (e->xpool_c, the same values as those rows of x_in: the same row scale) and k | v | mix on every
+        // row — two problems of one launch on the regrouped image.  Taken only where the whole projection and both parts run on the LDS-DMA family by the
+        // dispatcher's own rule (gemm_rule_takes_v2 on the calls as they are made: weight planes of a split-operand engine, rule_M), so the bits are
+        // those of the single launch; a projection the split-operand kernels take (N >= 2048) keeps its one launch.
+        const bool compact_q = g_last_layer_compact_q && fp32_engine && e->proj_wc && denoise_only && l == c.depth - 1 && !e->is_time[l] && c.depth >= 2 && S <= 16 && S >= 8 &&
+                               c.attn_dim_head == 64 && !g_small_attn_wide && tiled_family(M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_w[l]) &&
+                               tiled_family(M, 2 * hd + h, D, GEMM_RMS_ROWSCALE, e->proj_wc) && tiled_family(Mc, hd + h, D, GEMM_RMS_ROWSCALE, e->proj_wc, M);
+        if (compact_q) {
+            GemmArgs ga{x_in, D, e->proj_wc, D, P, ldp, e->proj_bc, nullptr, 0, M, 2 * hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+            GemmArgs gb{e->xpool_c, D, e->proj_wc + (size_t)(2 * hd + h) * D, D, e->qc, e->ldqc, e->proj_bc + 2 * hd + h, nullptr, 0, Mc, hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+            gb.rule_M = M;
+            if ((rc = gemm_two(ga, gb, s))) return rc;
+        } else
         if ((rc = gemm_simple(x_in, D, e->proj_w[l], D, P, ldp, M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_b[l], nullptr, 0, s))) return rc;
         bool fused_out = false;
         if (e->is_time[l]) {
@@ -977,6 +1031,13 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             if (denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8) {
                 sa.q_lo = 1; sa.q_hi = 1 + ns; sa.q_last = 0;
                 sa.out = e->att_c; sa.o_group_stride = (int64_t)nkeep * hd; sa.out_b = nullptr;
+                if (compact_q) {
+                    // k | v | mix at columns 0, hd, 2 hd of P; q | gates of the restricted rows in e->qc
+                    sa.k = P; sa.v = P + hd; sa.mix = P + 2 * hd;
+                    sa.q = e->qc; sa.q_group_stride = (int64_t)nkeep * e->ldqc; sa.q_item_stride = e->ldqc;
+                    sa.gate = e->qc + hd; sa.g_group_stride = (int64_t)nkeep * e->ldqc; sa.g_item_stride = e->ldqc;
+                    sa.q_compact = 1;
+                }
             }
             // per-frame fused form: attention of all heads of a frame, then its output projection + residual, in one kernel
             const bool tail_compact = denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8;
@@ -1084,6 +1145,10 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     }
     if ((rc = gather_space_double_norm(xfc, e->gs, e->latent_norm, e->lq_out.norm_ctx, Fr, nkeep, 0, D, ns, RMS_EPS, s))) return rc;
     if ((rc = gemm_simple(e->gs, D, e->lout_kv_w, D, e->okv, 2 * hd, Fr * ns, 2 * hd, D, 0, nullptr, nullptr, 0, s))) return rc;
+    if (g_lqap_out_fused && fp32_engine && !g_small_attn_wide && lqap_out_applicable(h, c.attn_dim_head, n, ns, dl) && dl % 4 == 0 && frame_fused_frames_ok(Fr) &&
+        tiled_family(Fr * n, dl, hd, 0, e->lout_w))
+        // one workgroup per frame: the learned queries' attention into LDS, the latent projection as its tail (e->oatt is not written)
+        return lqap_out(e->okv, 2 * hd, e->lout_q, e->lout_gate, e->lq_out.k_gamma, e->lout_w, hd, e->pred, dl, Fr, h, n, ns, dl, s);
     {
         SmallAttnArgs sa{};
         sa.dh = c.attn_dim_head;
@@ -1470,6 +1535,8 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
     // stage keeps the agent row only where the engine can (engine_clean_agent_only); lean_keep = token rows per frame of e->xfc after it.
     const bool lean = d4::g_rollout_clean_agent_row != 0;
     const int lean_keep = (lean && d4::engine_clean_agent_only(e)) ? 1 : c.num_spatial_tokens + 1;
+    // what a captured frame's launches depend on besides its shape: the clean-evaluation form and the forms of the latent-token ends (test hooks)
+    const int variant = (lean ? 1 : 0) | (d4::g_lqap_in_fused ? 2 : 0) | (d4::g_lqap_out_fused ? 4 : 0) | (d4::g_last_layer_compact_q ? 8 : 0);
     // Only the sampled action (policy head) and the terminal feed the next frame; values and rewards are outputs nobody reads inside the loop: they
     // are computed once after it, over the whole agent history [B][F][D] — the caller's, else the engine's own (one frame: the frame's rows).
     const float* hist = nullptr;
@@ -1504,7 +1571,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
             }
             hipGraphExec_t exec = nullptr;
             const int bucket = e->Lt > 0 ? d4::time_history_bucket(t0) : 0;
-            for (auto& g : e->graphs) if (g.B == B && g.K == K && g.sl == sl && g.tasks == (tasks != nullptr) && g.bucket == bucket && g.lean == (int)lean) exec = g.exec;
+            for (auto& g : e->graphs) if (g.B == B && g.K == K && g.sl == sl && g.tasks == (tasks != nullptr) && g.bucket == bucket && g.variant == variant) exec = g.exec;
             if (!exec) {
                 if (!e->warm) {
                     // first decode frame of this engine: run it eagerly once (function attributes, lazy module load)
@@ -1532,7 +1599,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                     D4_HIP(ce);
                     D4_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                     (void)hipGraphDestroy(graph);
-                    e->graphs.push_back({B, K, sl, tasks != nullptr, bucket, (int)lean, exec});
+                    e->graphs.push_back({B, K, sl, tasks != nullptr, bucket, variant, exec});
                 }
             }
             if (exec) {
@@ -1661,6 +1728,9 @@ int d4_debug_switch(const char* name, int value) {
     else if (name && !strcmp(name, "rollout_clean_agent_row")) sw = &d4::g_rollout_clean_agent_row;
     else if (name && !strcmp(name, "rollout_batched_heads")) sw = &d4::g_rollout_batched_heads;
     else if (name && !strcmp(name, "attn_out_cols")) sw = &d4::g_attn_out_cols;
+    else if (name && !strcmp(name, "lqap_in_fused")) sw = &d4::g_lqap_in_fused;
+    else if (name && !strcmp(name, "lqap_out_fused")) sw = &d4::g_lqap_out_fused;
+    else if (name && !strcmp(name, "last_layer_compact_q")) sw = &d4::g_last_layer_compact_q;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
     else if (name && !strcmp(name, "pool_mix_deep")) sw = &d4::g_pool_mix_deep;
     else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
@@ -1696,7 +1766,7 @@ int d4_debug_buffer(d4_engine* e, const char* name, float** ptr) {
         {"ckv", e->ckv}, {"catt", e->catt}, {"lkv", e->lkv}, {"latt", e->latt}, {"space", e->space}, {"gs", e->gs},
         {"okv", e->okv}, {"oatt", e->oatt}, {"oproj", e->oproj}, {"pred", e->pred}, {"x_lat", e->x_lat},
         {"cache", e->cache}, {"lin_q", e->lin_q}, {"lin_gate", e->lin_gate}, {"lout_q", e->lout_q},
-        {"l_logits", e->l_logits}, {"l_dlogits", e->l_dlogits}, {"l_adv", e->l_adv}, {"l_returns", e->l_returns}, {"l_mask", e->l_mask},
+        {"qc", e->qc}, {"l_logits", e->l_logits}, {"l_dlogits", e->l_dlogits}, {"l_adv", e->l_adv}, {"l_returns", e->l_returns}, {"l_mask", e->l_mask},
     };
     for (auto& t : tbl) if (!strcmp(t.n, name)) {
         // a bf16 engine keeps some activation buffers ONLY as bf16 images (nothing writes the fp32 buffer): handing out the stale fp32 view would mislead
@@ -1966,6 +2036,17 @@ int d4_small_attn_wide_bf16(const float* q, int64_t q_group_stride, int64_t q_it
     return small_attn_entry(2, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
                             k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
                             nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
+}
+
+int d4_lqap_in(const float* latents, int ldl, const float* w_kv, int ldw, const float* q, const float* gate, const float* k_gamma, float* out, int frames,
+               int heads, int n, int ns, int dl, float eps, void* stream) {
+    D4_REQUIRE(latents && w_kv && q && gate && k_gamma && out, "d4_lqap_in: null argument");
+    return d4::lqap_in(latents, ldl, w_kv, ldw, q, gate, k_gamma, out, frames, heads, n, ns, dl, eps, static_cast<hipStream_t>(stream));
+}
+int d4_lqap_out(const float* kv, int ldkv, const float* q, const float* gate, const float* k_gamma, const float* w_out, int ldw, float* pred, int ldp,
+                int frames, int heads, int n, int ns, int dl, void* stream) {
+    D4_REQUIRE(kv && q && gate && k_gamma && w_out && pred, "d4_lqap_out: null argument");
+    return d4::lqap_out(kv, ldkv, q, gate, k_gamma, w_out, ldw, pred, ldp, frames, heads, n, ns, dl, static_cast<hipStream_t>(stream));
 }
 
 int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,

@@ -945,6 +945,32 @@ int gemm_pair(const GemmArgs& a_in, const GemmArgs& b_in, hipStream_t stream) {
 static std::recursive_mutex g_gemm_mu;
 static std::recursive_mutex& gemm_mutex() { return g_gemm_mu; }
 
+// Would gemm() below run this call — these exact arguments, weight planes and rule_M included — on the LDS-DMA f32 family (gemm2.hip through gemm_v2)?
+// The same tests in the same order as gemm(); a forced configuration answers false (a forced call is not taken by rule).  The engine asks this before
+// it replaces a product by a kernel that carries that family's bits (engine.hip: the latent-token ends, the last layer's split projection).
+bool gemm_rule_takes_v2(const GemmArgs& p) {
+    if (p.M < 1 || g_forced_cfg >= 0) return false;
+    const bool ta = p.flags & GEMM_TRANS_A, tb = p.flags & GEMM_TRANS_B;
+    if (ta || tb) return false;
+    if (p.Wb && p.wplane > 0 && p.wscale) {
+        if (gemm_h2_takes(p)) return false;
+        GemmArgs q = p;
+        q.Wb = nullptr; q.wplane = 0; q.wscale = nullptr; q.aexp = nullptr;
+        return gemm_rule_takes_v2(q);
+    }
+    if (p.Wb && p.wplane > 0) {
+        const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
+        if (wide && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && p.M >= 1024))) return false;
+        if (wide && p.M >= 256 && gemm_x3_applicable(p)) return false;
+        GemmArgs q = p;
+        q.Wb = nullptr; q.wplane = 0;
+        return gemm_rule_takes_v2(q);
+    }
+    if (p.Wb) return false;
+    if (gemm_skinny_applicable(p) || gemm2_ksplit_rule(p)) return false;
+    return use_v2(p);
+}
+
 int gemm(const GemmArgs& p, hipStream_t stream) {
     std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
     D4_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad sizes M=%d N=%d K=%d", p.M, p.N, p.K);

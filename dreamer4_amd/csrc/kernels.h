@@ -48,6 +48,7 @@ struct GemmArgs {
 };
 
 int gemm(const GemmArgs& p, hipStream_t stream);
+bool gemm_rule_takes_v2(const GemmArgs& p);               // gemm.hip: would gemm() run exactly this call on the LDS-DMA f32 family (gemm2.hip) by its rules?
 // bf16 MFMA path (gemm_bf16.hip): A fp32 rounded to bf16 on the way into LDS, W pre-converted, fp32 accumulate / epilogue
 bool gemm_bf16_applicable(const GemmArgs& p);
 int gemm_bf16(const GemmArgs& p, hipStream_t stream);
@@ -148,6 +149,8 @@ struct SmallAttnArgs {
     // space_attn only: restrict the QUERIES to tokens [q_lo, q_hi) plus the last token; outputs are written at item
     // rank (i - q_lo, or q_hi - q_lo for the last token).  q_hi == 0 -> all queries, natural order.
     int q_lo = 0, q_hi = 0, q_last = 1;   // q_last = 0: do not add the last token to the restricted query set
+    int q_compact = 0;                    // 1 (with q_hi > 0, q_last = 0; matrix-pipe form only): q and gate hold the rows [q_lo, q_hi) alone, row i at item i - q_lo;
+                                          // the other queries, whose outputs are dropped anyway, read as zeros
     int dh = 64;                          // head dim (16 / 32 / 64): lanes >= dh of the wavefront idle; rows are packed h * dh + lane
     uint16_t* out_b = nullptr;            // optional bf16 copy of the output (same strides as `out`): the next GEMM's bf16 activation image (bf16 engine)
     int wide = 0;                         // != 0: more than 64 items on a side go to the tiled matrix-pipe core (attn_wide_mfma.hip, up to WIDE_ATTN_MAX per side);
@@ -186,6 +189,19 @@ constexpr int POOL_DEEP_CHUNK = 64;
 int pool_mix_deep(const PoolMixArgs& p, hipStream_t stream);
 extern int g_pool_mix_deep;              // pool_mix_deep.hip: 1 = the engine's pools of <= 64 hiddens take pool_mix_deep too (test hook; default 0)
 void note_pool_deep_form(const char* name);                      // attn.hip: the form record of family "pool_mix_deep"
+
+// ------------------------------------------------------------------------------------ latent-token ends of a trunk evaluation (latent_ends.hip)
+// One workgroup per frame, 8 heads x 64.  lqap_in: latents [frames * n][ldl] -> K | V (w_kv [2 * 512][ldw], RMS row scale) -> attention of the ns
+// learned queries q [ns][512] (gate [ns][8]) -> out [frames * ns][512].  lqap_out: attention of the n learned queries over the frame's ns rows of
+// kv [frames * ns][ldkv] (K | V) -> pred [frames * n][ldp] = pooled [n][512] x w_out [dl][ldw]^T.  Same bits as the GEMM (gemm2.hip family) and
+// small_attn launches they replace; the `applicable` predicates are by shape only.
+bool lqap_in_applicable(int heads, int dh, int n, int ns, int dl);
+int lqap_in(const float* latents, int ldl, const float* w_kv, int ldw, const float* q, const float* gate, const float* k_gamma, float* out, int frames,
+            int heads, int n, int ns, int dl, float eps, hipStream_t s);
+bool lqap_out_applicable(int heads, int dh, int n, int ns, int dl);
+int lqap_out(const float* kv, int ldkv, const float* q, const float* gate, const float* k_gamma, const float* w_out, int ldw, float* pred, int ldp, int frames,
+             int heads, int n, int ns, int dl, hipStream_t s);
+extern int g_lqap_in_fused, g_lqap_out_fused, g_last_layer_compact_q;      // engine.hip: test hooks, default 1 (d4_debug_switch)
 
 // ------------------------------------------------------------------------------------ per-frame fused block tails (frame_fused.hip)
 // W [N][K] -> Wt [N / 16][K / 4][16][4]: the weight image the per-frame kernels stream (a 16-row tile is one contiguous run)

@@ -9,7 +9,7 @@
 namespace d4 {
 
 enum GlueClass : int { GL_SPACE_ATTN = 0, GL_TIME_ATTN, GL_TIME_KV_APPEND, GL_POOL_MIX, GL_SMALL_ATTN, GL_ASSEMBLE, GL_SPLITK_REDUCE, GL_ATTN_WIDE,
-                       GL_FRAME_ATTN_OUT, GL_FRAME_POOL_TAIL, GL_N };
+                       GL_FRAME_ATTN_OUT, GL_FRAME_POOL_TAIL, GL_LATENT_ENDS, GL_N };
 
 // true: this launch is timed — launch with hipExtLaunchKernelGGL(..., *a, *b, 0, ...); `bytes` = algorithmic HBM bytes of the launch
 bool glue_prof_begin(int cls, double bytes, hipEvent_t* a, hipEvent_t* b, double flops = 0.);      // flops: matrix work a fused class carries (per-frame kernels)

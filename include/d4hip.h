@@ -643,6 +643,15 @@ int d4_frame_pool(const float* q, int ldq, const float* x, int ldx, const float*
                   int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream);
 int d4_frame_pool_tail(const float* u, const float* wv_t, const float* wo_t, int frames, int S, int D, int pool_heads, const float* resid, int ldr,
                        float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream);
+/* The latent-token ends of a dynamics evaluation as one per-frame kernel each (csrc/latent_ends.hip; 8 heads x 64, n <= 32, ns <= 16, dl <= 256).
+ * d4_lqap_in: latents [frames * n][ldl] -> K | V = rms-scaled latents x w_kv [2 * 512][ldw]^T (dl % 32 == 0) -> attention of the ns learned queries
+ * q [ns][512] with head gates gate [ns][8] -> out [frames * ns][512]: the bits of d4_gemm(GEMM_RMS_ROWSCALE) on the LDS-DMA family, then d4_small_attn.
+ * d4_lqap_out: attention of the n learned queries q [n][512] (gate [n][8]) over the ns rows kv [frames * ns][ldkv] (K | V) of each frame ->
+ * pred [frames * n][ldp] = pooled x w_out [dl][ldw]^T: the bits of d4_small_attn, then d4_gemm on the LDS-DMA family. */
+int d4_lqap_in(const float* latents, int ldl, const float* w_kv, int ldw, const float* q, const float* gate, const float* k_gamma, float* out, int frames,
+               int heads, int n, int ns, int dl, float eps, void* stream);
+int d4_lqap_out(const float* kv, int ldkv, const float* q, const float* gate, const float* k_gamma, const float* w_out, int ldw, float* pred, int ldp,
+                int frames, int heads, int n, int ns, int dl, void* stream);
 
 int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps,
                         void* stream);
