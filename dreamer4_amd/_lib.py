@@ -82,6 +82,19 @@ class AssembleDesc(C.Structure):
     ]
 
 
+class PolicyLossDesc(C.Structure):
+    """d4_policy_loss_desc: the learner's PolicyLossArgs (include/d4hip.h)."""
+    _fields_ = [
+        ('logits', C.c_void_p), ('ld', C.c_int32), ('actions', C.c_void_p), ('old_log_probs', C.c_void_p), ('old_logits', C.c_void_p), ('ldo', C.c_int32),
+        ('advantages', C.c_void_p), ('mask', C.c_void_p), ('action_sizes', C.c_void_p), ('rows', C.c_int32), ('na', C.c_int32), ('total', C.c_int32),
+        ('cparams', C.c_void_p), ('ldc', C.c_int32), ('actions_cont', C.c_void_p), ('old_log_probs_cont', C.c_void_p), ('old_cparams', C.c_void_p),
+        ('nc', C.c_int32), ('beta_param', C.c_int32), ('objective', C.c_int32), ('normalize', C.c_int32), ('use_gate', C.c_int32), ('reverse_kl', C.c_int32),
+        ('eps', C.c_float), ('clip', C.c_float), ('ent_w', C.c_float), ('gate_temp', C.c_float), ('pmpo_alpha', C.c_float), ('kl_w', C.c_float),
+        ('loss', C.c_void_p), ('dlogits', C.c_void_p), ('dcparams', C.c_void_p), ('row_pl', C.c_void_p), ('row_ent', C.c_void_p), ('row_aux', C.c_void_p),
+        ('scratch', C.c_void_p),
+    ]
+
+
 # d4_gemm_run families / d4_gemm_run_pair targets
 GEMM_TILE, GEMM_V2, GEMM_V2_KSPLIT, GEMM_X3, GEMM_X3SK, GEMM_H2, GEMM_SKINNY, GEMM_BF16, GEMM_BF16A = range(9)
 PAIR_SKINNY, PAIR_BF16A, PAIR_V2 = range(3)
@@ -241,6 +254,8 @@ SYMBOLS = {
     'd4_hl_gauss_scalar': (_I, [_P, _I, _P, _P, _I, _I, _P]),
     'd4_ppo_policy_loss': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     'd4_gae': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P]),
+    'd4_gae_adv': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P]),
+    'd4_policy_loss': (_I, [C.POINTER(PolicyLossDesc), _P]),
     'd4_categorical_sample_logp': (_I, [_P, _I, _P, _I, _P, _I, _I, _F, _P, _P, _P]),
     'd4_hl_gauss_ce': (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
     'd4_flow_noised_patches': (_I, [_P] * 4 + [_I] * 6 + [_P]),

@@ -372,6 +372,29 @@ __global__ void finalize_losses_kernel(const float* scal, float* losses, int obj
     losses[1] = scal[7] / count;
 }
 
+// The policy branch's loss as one sequence (learn() and the stateless entry d4_policy_loss both run it, so the two cannot drift): the masked
+// advantage statistics scal[0..2] (sum adv * mask, count, sum of squared differences; each all-reduced where a callback is given), the fused
+// forward + backward kernel, and the row sums scal[4..6].  scal is zeroed by the caller, who also finalises (learn() adds the value branch's
+// sum first).
+static int policy_loss_run(const PolicyLossArgs& p, float* scal, int (*allreduce_sum)(float*, int, void*), void* allreduce_user, hipStream_t s) {
+    int rc;
+    const int64_t R = p.R;
+    hipLaunchKernelGGL(reduce1_kernel<RED_PROD>, dim3(1), dim3(1024), 0, s, p.adv_raw, p.mask, scal, R, scal + 0);
+    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, p.mask, nullptr, scal, R, scal + 1);
+    D4_LAUNCH_CHECK();
+    if (allreduce_sum && (rc = allreduce_sum(scal, 2, allreduce_user))) { set_error("allreduce callback failed (%d)", rc); return 5; }
+    hipLaunchKernelGGL(reduce1_kernel<RED_SQDIFF_MASKED>, dim3(1), dim3(1024), 0, s, p.adv_raw, p.mask, scal, R, scal + 2);
+    D4_LAUNCH_CHECK();
+    if (allreduce_sum && (rc = allreduce_sum(scal + 2, 1, allreduce_user))) { set_error("allreduce callback failed (%d)", rc); return 5; }
+    hipLaunchKernelGGL(policy_loss_kernel, dim3(cdiv(p.R, 128)), dim3(128), 0, s, p);
+    D4_LAUNCH_CHECK();
+    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, p.row_pl, nullptr, scal, R, scal + 4);
+    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, p.row_ent, nullptr, scal, R, scal + 5);
+    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, p.row_aux, nullptr, scal, R, scal + 6);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------ MLP backward pieces
 __global__ void silu_bwd_kernel(const float* dy, const float* z, float* dz, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -579,14 +602,6 @@ int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s) {
     D4_LAUNCH_CHECK();
     if (io->returns) D4_HIP(hipMemcpyAsync(io->returns, e->l_returns, sizeof(float) * R, hipMemcpyDeviceToDevice, s));
 
-    hipLaunchKernelGGL(reduce1_kernel<RED_PROD>, dim3(1), dim3(1024), 0, s, row_a, mask_keep, scal, (int64_t)R, scal + 0);
-    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, mask_keep, nullptr, scal, (int64_t)R, scal + 1);
-    D4_LAUNCH_CHECK();
-    if (io->allreduce_sum && (rc = io->allreduce_sum(scal, 2, io->allreduce_user))) { set_error("allreduce callback failed (%d)", rc); return 5; }
-    hipLaunchKernelGGL(reduce1_kernel<RED_SQDIFF_MASKED>, dim3(1), dim3(1024), 0, s, row_a, mask_keep, scal, (int64_t)R, scal + 2);
-    D4_LAUNCH_CHECK();
-    if (io->allreduce_sum && (rc = io->allreduce_sum(scal + 2, 1, io->allreduce_user))) { set_error("allreduce callback failed (%d)", rc); return 5; }
-
     const int normalize = io->normalize_advantages < 0 ? (io->objective != 2) : io->normalize_advantages;
 
     // ---- policy head forward (saved), logits of prediction head 0
@@ -621,8 +636,8 @@ int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s) {
         p.pmpo_alpha = c.pmpo_pos_to_neg_weight;
         p.kl_w = io->objective == 2 ? c.pmpo_kl_div_loss_weight : 0.f;
         D4_REQUIRE(!(p.kl_w > 0.f) || ((na == 0 || io->old_action_logits) && (nc == 0 || io->old_cont_params)), "pmpo with a KL weight needs old_action_unembeds  [D4:6160-6170]");
-        hipLaunchKernelGGL(policy_loss_kernel, dim3(cdiv(R, 128)), dim3(128), 0, s, p);
-        D4_LAUNCH_CHECK();
+        // advantage statistics, the fused loss kernel and its row sums
+        if ((rc = policy_loss_run(p, scal, io->allreduce_sum, io->allreduce_user, s))) return rc;
     }
     // ---- value head forward (saved) + HL-Gauss cross entropy
     const int vld = (c.value_num_bins + 3) / 4 * 4;
@@ -637,9 +652,6 @@ int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s) {
                                e->value_support, R, c.value_num_bins, sqrtf(2.f) * sigma, c.hl_gauss_eps, c.value_min, c.value_max, e->l_dvbins, row_vl);
         D4_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, row_pl, nullptr, scal, (int64_t)R, scal + 4);
-    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, row_ent, nullptr, scal, (int64_t)R, scal + 5);
-    hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, row_aux, nullptr, scal, (int64_t)R, scal + 6);
     hipLaunchKernelGGL(reduce1_kernel<RED_SUM>, dim3(1), dim3(1024), 0, s, row_vl, nullptr, scal, (int64_t)R, scal + 7);
     D4_LAUNCH_CHECK();
     if (io->allreduce_sum && (rc = io->allreduce_sum(scal + 4, 4, io->allreduce_user))) { set_error("allreduce callback failed (%d)", rc); return 5; }
@@ -732,6 +744,17 @@ int d4_gae(const float* rewards, const float* values, const int64_t* lens, const
     return 0;
 }
 
+// d4_gae with the two further outputs the learner consumes: adv = returns - values (values read as 0 past `len`) and the learnable-step mask.
+int d4_gae_adv(const float* rewards, const float* values, const int64_t* lens, const uint8_t* is_truncated, const uint8_t* terminals, float gamma,
+               float lam, int batch, int time, float* returns, float* adv, float* mask, void* stream) {
+    D4_REQUIRE(rewards && values && returns && adv && mask, "d4_gae_adv: null argument");
+    D4_REQUIRE(batch >= 1 && time >= 1, "d4_gae_adv: batch >= 1 and time >= 1");
+    hipLaunchKernelGGL(d4::gae_kernel, dim3(d4::cdiv(batch, 128)), dim3(128), 0, static_cast<hipStream_t>(stream), rewards, values, lens,
+                       is_truncated, terminals, gamma, lam, batch, time, returns, adv, mask);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+
 // Stateless form of the value branch's loss (D4:6254-6295: HL-Gauss / two-hot targets of the returns, cross entropy against the value bins,
 // mean over the learnable steps), forward + backward in one call:  loss[0] = sum_r mask[r] * CE_r / max(sum mask, 1),  dlogits = d loss / d logits.
 // support: [bins + 1] bin edges (HL-Gauss) or [bins] bin values (two-hot), device.  mask: [rows] or null (all rows).  scratch >= 2 * rows + 64 floats.
@@ -757,10 +780,54 @@ int d4_hl_gauss_ce(const float* logits, int ld, const float* targets, const floa
     return 0;
 }
 
-// Stateless form of the policy branch's loss for discrete actions (D4:6077-6242: joint log-prob of the stored actions under MultiCategorical
-// logits, PPO clipped surrogate (objective 0, D4:6204-6212) or SPO (1, D4:6188-6198) against the behaviour log-probs, entropy bonus, masked mean
-// over the learnable steps), forward + backward in one call — the fused kernel d4_learn runs, with the advantages taken as given (normalise them
-// before):  loss[0] = sum_r mask[r] (pl_r - entropy_weight * H_r) / max(sum mask, 1),  dlogits [rows][ld] = d loss / d logits.
+// Stateless form of the whole policy branch's loss (D4:5985-6242; test / tooling use): fills PolicyLossArgs from the descriptor
+// and runs policy_loss_run, the sequence d4_learn runs, then finalize_losses_kernel.  Everything is refused before the first launch.
+int d4_policy_loss(const d4_policy_loss_desc* d, void* stream) {
+    D4_REQUIRE(d, "d4_policy_loss: null argument");
+    D4_REQUIRE(d->advantages && d->loss && d->row_pl && d->row_ent && d->row_aux && d->scratch, "d4_policy_loss: null argument");
+    D4_REQUIRE(d->rows >= 1 && d->na >= 0 && d->nc >= 0 && d->na + d->nc >= 1, "d4_policy_loss: rows >= 1 and at least one action");
+    D4_REQUIRE(d->objective >= 0 && d->objective <= 2, "d4_policy_loss: objective 0 (ppo), 1 (spo) or 2 (pmpo)");
+    D4_REQUIRE(d->beta_param == 0 || d->beta_param == 1, "d4_policy_loss: beta_param 0 (softplus) or 1 (exp)");
+    if (d->na > 0) {
+        D4_REQUIRE(d->logits && d->actions && d->old_log_probs && d->action_sizes && d->dlogits, "d4_policy_loss: null argument (discrete part)");
+        D4_REQUIRE(d->total >= d->na && d->ld >= d->total, "d4_policy_loss: ld < total");
+    } else {
+        D4_REQUIRE(d->total == 0 && (d->ld == 0 || d->dlogits), "d4_policy_loss: without discrete actions total is 0 and ld columns of dlogits are zeroed");
+    }
+    if (d->nc > 0) {
+        D4_REQUIRE(d->cparams && d->actions_cont && d->old_log_probs_cont && d->dcparams, "d4_policy_loss: null argument (continuous part)");
+        D4_REQUIRE(d->ldc >= 2 * d->nc, "d4_policy_loss: ldc < 2 * nc");
+    } else {
+        D4_REQUIRE(d->ldc == 0 || d->dcparams, "d4_policy_loss: without continuous actions ldc columns of dcparams are zeroed");
+    }
+    if (d->objective == 2 && d->kl_w > 0.f)
+        D4_REQUIRE((d->na == 0 || (d->old_logits && d->ldo >= d->total)) && (d->nc == 0 || d->old_cparams),
+                   "d4_policy_loss: pmpo with a KL weight needs the old logits / old parameters  [D4:6160-6170]");
+    D4_REQUIRE(!d->use_gate || d->gate_temp > 0.f, "d4_policy_loss: gate temperature must be positive");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* scal = d->scratch;                  // [64]: statistics and sums as in d4::learn; [32..33] the finalised pair
+    float* ones = d->scratch + 64;             // [rows]
+    const float* mask = d->mask;
+    D4_HIP(hipMemsetAsync(scal, 0, 64 * sizeof(float), s));
+    if (!mask) { if (int rc = d4::fill_f32(ones, 1.f, d->rows, s)) return rc; mask = ones; }
+    d4::PolicyLossArgs p{};
+    p.logits = d->logits; p.ld = d->ld; p.actions = d->actions; p.old_lp = d->old_log_probs; p.old_logits = d->old_logits; p.ldo = d->ldo;
+    p.adv_raw = d->advantages; p.mask = mask; p.scal = scal; p.action_sizes = d->action_sizes; p.dlogits = d->dlogits;
+    p.row_pl = d->row_pl; p.row_ent = d->row_ent; p.row_aux = d->row_aux;
+    p.cparams = d->cparams; p.ldc = d->ldc; p.actions_cont = d->actions_cont; p.old_lp_cont = d->old_log_probs_cont; p.old_cparams = d->old_cparams;
+    p.dcparams = d->dcparams; p.beta_param = d->beta_param; p.nc = d->nc;
+    p.R = d->rows; p.na = d->na; p.A = d->total; p.objective = d->objective; p.normalize = d->normalize; p.use_gate = d->use_gate;
+    p.reverse_kl = d->reverse_kl; p.eps = d->eps; p.clip = d->clip; p.ent_w = d->ent_w; p.gate_temp = d->gate_temp; p.pmpo_alpha = d->pmpo_alpha;
+    p.kl_w = d->objective == 2 ? d->kl_w : 0.f;
+    if (int rc = d4::policy_loss_run(p, scal, nullptr, nullptr, s)) return rc;
+    hipLaunchKernelGGL(d4::finalize_losses_kernel, dim3(1), dim3(1), 0, s, scal, scal + 32, d->objective, d->ent_w, p.kl_w);
+    D4_HIP(hipMemcpyAsync(d->loss, scal + 32, sizeof(float), hipMemcpyDeviceToDevice, s));
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+
+// The discrete PPO / SPO form of d4_policy_loss with the advantages taken as given (no gate, no normalisation):
+//   loss[0] = sum_r mask[r] (pl_r - entropy_weight * H_r) / max(sum mask, 1),  dlogits [rows][ld] = d loss / d logits.
 // action_sizes: device int32 [na], total = their sum <= ld.  mask: [rows] or null.  scratch >= 5 * rows + 64 floats.
 int d4_ppo_policy_loss(const float* logits, int ld, const int64_t* actions, const float* old_log_probs, const float* advantages, const float* mask,
                        const int32_t* action_sizes, int rows, int na, int total, int objective, float eps_clip, float entropy_weight, float* loss,
@@ -768,25 +835,13 @@ int d4_ppo_policy_loss(const float* logits, int ld, const int64_t* actions, cons
     D4_REQUIRE(logits && actions && old_log_probs && advantages && action_sizes && loss && dlogits && scratch && rows >= 1 && na >= 1 && total >= 1 && ld >= total,
                "d4_ppo_policy_loss: bad arguments");
     D4_REQUIRE(objective == 0 || objective == 1, "d4_ppo_policy_loss: objective 0 (ppo) or 1 (spo)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* scal = scratch;                     // [64]: [1] count, [4] sum pl, [5] sum -entropy
-    float* ones = scratch + 64;                // [rows]
-    float* row_pl = ones + rows, *row_ent = row_pl + rows, *row_aux = row_ent + rows;
-    D4_HIP(hipMemsetAsync(scal, 0, 64 * sizeof(float), s));
-    if (!mask) { if (int rc = d4::fill_f32(ones, 1.f, rows, s)) return rc; mask = ones; }
-    hipLaunchKernelGGL(d4::reduce1_kernel<d4::RED_SUM>, dim3(1), dim3(1024), 0, s, mask, (const float*)nullptr, scal, (int64_t)rows, scal + 1);
-    d4::PolicyLossArgs p{};
-    p.logits = logits; p.ld = ld; p.actions = actions; p.old_lp = old_log_probs; p.adv_raw = advantages; p.mask = mask; p.scal = scal;
-    p.action_sizes = action_sizes; p.dlogits = dlogits; p.row_pl = row_pl; p.row_ent = row_ent; p.row_aux = row_aux;
-    p.R = rows; p.na = na; p.A = total; p.objective = objective; p.normalize = 0; p.use_gate = 0; p.clip = eps_clip; p.ent_w = entropy_weight;
-    p.eps = 1e-6f; p.gate_temp = 1.f;
-    hipLaunchKernelGGL(d4::policy_loss_kernel, dim3(d4::cdiv(rows, 128)), dim3(128), 0, s, p);
-    hipLaunchKernelGGL(d4::reduce1_kernel<d4::RED_SUM>, dim3(1), dim3(1024), 0, s, row_pl, (const float*)nullptr, scal, (int64_t)rows, scal + 4);
-    hipLaunchKernelGGL(d4::reduce1_kernel<d4::RED_SUM>, dim3(1), dim3(1024), 0, s, row_ent, (const float*)nullptr, scal, (int64_t)rows, scal + 5);
-    hipLaunchKernelGGL(d4::finalize_losses_kernel, dim3(1), dim3(1), 0, s, scal, scratch + 32, objective, entropy_weight, 0.f);
-    D4_HIP(hipMemcpyAsync(loss, scratch + 32, sizeof(float), hipMemcpyDeviceToDevice, s));
-    D4_LAUNCH_CHECK();
-    return 0;
+    d4_policy_loss_desc d{};
+    d.logits = logits; d.ld = ld; d.actions = actions; d.old_log_probs = old_log_probs; d.advantages = advantages; d.mask = mask;
+    d.action_sizes = action_sizes; d.rows = rows; d.na = na; d.total = total; d.objective = objective; d.clip = eps_clip; d.ent_w = entropy_weight;
+    d.eps = 1e-6f; d.gate_temp = 1.f;
+    d.loss = loss; d.dlogits = dlogits; d.scratch = scratch;               // [64 + rows] of the scratch, then the three row terms
+    d.row_pl = scratch + 64 + rows; d.row_ent = d.row_pl + rows; d.row_aux = d.row_ent + rows;
+    return d4_policy_loss(&d, stream);
 }
 
 // Operator-level test entry points of the reductions and the RMSNorm backward: the launchers the learner and the blocks call.

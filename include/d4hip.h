@@ -760,7 +760,7 @@ int d4_categorical_sample_logp(const float* logits, int ld, const float* uniform
  * scratch >= 2 * rows + 64 floats. */
 int d4_hl_gauss_ce(const float* logits, int ld, const float* targets, const float* mask, const float* support, int rows, int bins, float vmin,
                    float vmax, float sigma, float eps, int two_hot, float* loss, float* dlogits, float* scratch, void* stream);
-/* The policy branch's loss for discrete actions, stateless (dreamer4.py:6077-6242: log-prob of the stored actions under the MultiCategorical
+/* The policy branch's loss for discrete actions, stateless (a wrapper of d4_policy_loss below; dreamer4.py:6077-6242: log-prob of the stored actions under the MultiCategorical
  * logits, PPO clipped surrogate (objective 0, dreamer4.py:6204-6212) or SPO (1, dreamer4.py:6188-6198) against the behaviour log-probs
  * [rows][na], entropy bonus, masked mean): loss[0] and dlogits [rows][ld] in one call — the fused kernel d4_learn runs, the advantages taken as
  * given (normalise them before, dreamer4.py:5985-5999).  action_sizes: device int32 [na], `total` their sum.  scratch >= 5 * rows + 64 floats. */
@@ -770,6 +770,49 @@ int d4_ppo_policy_loss(const float* logits, int ld, const int64_t* actions, cons
 int d4_gae(const float* rewards, const float* values, const int64_t* lens, const uint8_t* is_truncated,
            const uint8_t* terminals, float gamma, float lam, int batch, int time, float* returns,
            void* stream);
+/* d4_gae with the two further outputs the learner consumes: adv [batch][time] = returns - values (values read as 0 past `len`)
+ * and mask [batch][time] = 1 on the learnable steps t < len - truncated, 0 elsewhere.  lens null: every trajectory has `time` steps;
+ * is_truncated null: every trajectory is truncated; terminals null: none is terminal.  Nothing past `len` is read. */
+int d4_gae_adv(const float* rewards, const float* values, const int64_t* lens, const uint8_t* is_truncated, const uint8_t* terminals, float gamma,
+               float lam, int batch, int time, float* returns, float* adv, float* mask, void* stream);
+/* The whole policy branch's loss, stateless (dreamer4.py:5985-6242; test / tooling use): the descriptor mirrors the learner's
+ * PolicyLossArgs (csrc/learn.hip) field by field, and the call runs what d4_learn runs: the masked advantage statistics, the fused forward +
+ * backward kernel, the row sums and the final division by max(sum mask, 1).
+ *   discrete part (na > 0): logits [rows][ld], actions int64 [rows][na], old_log_probs [rows][na], action_sizes device int32 [na] with sum
+ *     `total` <= ld, old_logits [rows][ldo] (pmpo KL; else may be null); dlogits [rows][ld], columns total .. ld written as zero.
+ *   continuous part (nc > 0): cparams [rows][ldc] raw Beta parameters (2 per action), actions_cont [rows][nc] in (0, 1), old_log_probs_cont
+ *     [rows][nc], old_cparams [rows][nc][2] (pmpo KL; else may be null), beta_param as d4_config.continuous_beta_param; dcparams [rows][ldc],
+ *     columns 2 nc .. ldc written as zero.
+ *   advantages [rows] raw; normalize != 0: z-scored over the rows with mask != 0, the variance clamped at eps.  mask [rows] or null (all rows).
+ *   objective 0 ppo, 1 spo, 2 pmpo; kl_w is read under pmpo only.
+ *   loss[0]; row_pl / row_ent / row_aux [rows]: the masked per-row surrogate, negative entropy and KL terms.  scratch >= rows + 64 floats.
+ * Refused before any launch: a null argument of a part in use, ld < total, ldc < 2 nc, kl_w > 0 under pmpo without the old logits / parameters,
+ * an objective outside 0 .. 2. */
+typedef struct d4_policy_loss_desc {
+    const float* logits; int32_t ld;
+    const int64_t* actions;
+    const float* old_log_probs;
+    const float* old_logits; int32_t ldo;
+    const float* advantages;
+    const float* mask;
+    const int32_t* action_sizes;
+    int32_t rows, na, total;
+    const float* cparams; int32_t ldc;
+    const float* actions_cont;
+    const float* old_log_probs_cont;
+    const float* old_cparams;
+    int32_t nc, beta_param;
+    int32_t objective, normalize, use_gate, reverse_kl;
+    float eps, clip, ent_w, gate_temp, pmpo_alpha, kl_w;
+    float* loss;
+    float* dlogits;
+    float* dcparams;
+    float* row_pl;
+    float* row_ent;
+    float* row_aux;
+    float* scratch;
+} d4_policy_loss_desc;
+int d4_policy_loss(const d4_policy_loss_desc* d, void* stream);
 /* Pixel-side operators of the VideoTokenizer training forward (dreamer4.py:4239-4603; csrc/tok_train.hip).  Patch rows are
  * [(b t nh nw)][(p1 p2 c)] of a video (b c t (nh p1) (nw p2)); the patch row C * ps * ps and every `dim` must be multiples of 4, row pointers 16-byte
  * aligned.  No allocation, no host synchronisation; column sums and the loss sum go through per-block partials in the caller's `part` and one

@@ -367,3 +367,101 @@ def test_learn_at_baseline_size_vs_oracle(terminal_bias):
         rel_p = (d(torch_step(g_pp)) - d(w_o)).norm().item() / (d(w_o) - d(w0)).norm().item()
         assert rel <= 20 * rel_p + 1e-3, (head, rel, rel_p)
     assert n_checked >= 10
+
+
+# ---- off-policy: the behaviour policy that filled the Experience is not the policy being trained (every test above learns from the weights that
+# acted: ratio == 1, KL == 0, nothing clipped, so the KL gradients, the clipped branch and SPO's quadratic term vanish identically there)
+CONT_HEADS = HEADS + ('action_embedder.continuous_action_unembed',)
+
+
+def off_policy_case(m, B, T, seed, scale, scale_c=0.):
+    """The oracle's rollout under PERTURBED head weights (the unembeddings moved by `scale` / `scale_c` of their rms) -> (cfg, W of the model itself, the
+    rollout as the oracle's dict and as an Experience, the share of learnable steps whose ratio under W lies outside the clip band, the mean KL)."""
+    cfg, W = oracle_config(m), oracle_weights(m)
+    gen = torch.Generator().manual_seed(seed)
+    Wb = dict(W)
+    for k, sc in (('action_embedder.discrete_action_unembed', scale), ('action_embedder.continuous_action_unembed', scale_c)):
+        if k in W and W[k].numel():
+            Wb[k] = W[k] + sc * W[k].pow(2).mean().sqrt() * torch.randn(W[k].shape, generator=gen)
+    kw = {} if cfg.num_continuous_actions == 0 else dict(return_terminals=False)
+    ref = restate.generate(cfg, Wb, T, batch_size=B, noise=make_noise(cfg, T, B, seed), **kw)
+    nc = cfg.num_continuous_actions
+    e = Experience(latents=ref['latents'], agent_embed=ref['agent_embed'], rewards=ref['rewards'], values=ref['values'],
+                   log_probs=Actions(ref['log_probs'], ref['log_probs_cont'] if nc else None), actions=Actions(ref['actions'], ref['actions_cont'] if nc else None),
+                   lens=ref['lens'], terminals=ref['terminals'], is_truncated=ref['is_truncated'],
+                   old_action_unembeds=Actions(ref['old_action_unembeds'], ref['old_cont_params'] if nc else None), step_size=ref['step_size'])
+    with torch.no_grad():
+        Tn = ref['agent_embed'].shape[1]
+        pe = restate.policy_head(cfg, W, ref['agent_embed'])
+        logits = restate.policy_logits(cfg, W, pe)
+        lp = restate.discrete_log_probs(cfg, logits, ref['actions'][:, -Tn:]).sum(-1) - ref['log_probs'].sum(-1)
+        kl, o = 0., 0
+        for n in cfg.num_discrete_actions:
+            a, b = logits[..., o:o + n].log_softmax(-1), ref['old_action_unembeds'][..., o:o + n].log_softmax(-1)
+            kl, o = kl + (a.exp() * (a - b)).sum(-1), o + n
+        if nc:
+            cp = restate.policy_cont_params(cfg, W, pe)
+            lp = lp + (restate.beta_log_prob(cp, ref['actions_cont'][:, -Tn:], cfg.continuous_beta_param) - ref['log_probs_cont']).sum(-1)
+            kl = kl + restate.beta_kl(cp, ref['old_cont_params'], cfg.continuous_beta_param).sum(-1)
+        _, _, _, mask = restate.returns_and_advantage(cfg, ref, normalize=False)
+        outside = ((lp.exp() - 1.).abs() > cfg.ppo_eps_clip)[mask].float().mean().item()
+    return cfg, W, ref, e, outside, kl[mask].mean().item()
+
+
+def check_off_policy_learn(m, cfg, W, ref, e, obj, seed):
+    """learn_from_experience against restate.learn_losses on the same dict, the tolerance of test_learn_vs_oracle_random_config_sweep: the oracle once more
+    on inputs moved by float32 rounding, 20 x what that does (+ 1e-5 of the tensor's scale)."""
+    heads = tuple(k for k in CONT_HEADS)
+    Wg = {k: (v.clone().requires_grad_() if k.startswith(heads) and v.numel() > 0 else v) for k, v in W.items()}
+    pl_o, vl_o = restate.learn_losses(cfg, Wg, ref, obj)
+    pl_o.backward(); vl_o.backward()
+    gen = torch.Generator().manual_seed(seed)
+    jig = lambda x, r: x * (1 + r * (2 * torch.rand(x.shape, generator=gen) - 1))
+    ref2 = dict(ref, values=jig(ref['values'], 2e-6), rewards=jig(ref['rewards'], 2e-6), agent_embed=jig(ref['agent_embed'], 2e-6),
+                log_probs=ref['log_probs'] + 1e-6 * ref['old_action_unembeds'].abs().max() * (2 * torch.rand(ref['log_probs'].shape, generator=gen) - 1))
+    if cfg.num_continuous_actions:
+        ref2['log_probs_cont'] = ref['log_probs_cont'] + 1e-6 * ref['log_probs_cont'].abs().max() * (2 * torch.rand(ref['log_probs_cont'].shape, generator=gen) - 1)
+    Wp = {k: (v.clone().requires_grad_() if k.startswith(heads) and v.numel() > 0 else v) for k, v in W.items()}
+    pl_p, vl_p = restate.learn_losses(cfg, Wp, ref2, obj)
+    pl_p.backward(); vl_p.backward()
+    m.zero_grad()
+    pl, vl = m.learn_from_experience(e, objective=obj)
+    pl.backward(); vl.backward()
+    close(pl, pl_o, atol=2e-5 + 20 * abs(pl_p.item() - pl_o.item())); close(vl, vl_o, atol=2e-5 + 20 * abs(vl_p.item() - vl_o.item()))
+    n = 0
+    for k, p in m.named_parameters():
+        if k.startswith(heads) and p.numel() > 0:
+            sens = (Wp[k].grad - Wg[k].grad).abs().max().item()
+            close(p.grad, Wg[k].grad, atol=20 * sens + 1e-5 * Wg[k].grad.abs().max().item() + 1e-9, rtol=1e-4)
+            n += 1
+    assert n >= 10
+    return pl_o.item()
+
+
+@pytest.mark.parametrize('obj,reverse_kl', (('ppo', True), ('spo', True), ('pmpo', True), ('pmpo', False)))
+def test_off_policy_learn_vs_oracle(obj, reverse_kl):
+    """small_model size, B = 5, T = 6, two action types: the nonzero clip, quadratic and KL gradients (both KL directions) through the unembedding and the
+    policy MLP backward."""
+    from util import randomize_weights
+    m = randomize_weights(small_model(num_discrete_actions=(3, 2), num_tasks=0, pmpo_reverse_kl=reverse_kl, pmpo_kl_div_loss_weight=0.3), terminal_bias=-2.)
+    with torch.no_grad():       # logits of O(5), as in the sweep above
+        dict(m.named_parameters())['action_embedder.discrete_action_unembed'].mul_(0.02)
+    cfg, W, ref, e, outside, kl = off_policy_case(m, 5, 6, 61, 1.5)
+    assert 0.2 <= outside <= 0.8 and kl >= 1e-2, (outside, kl)
+    check_off_policy_learn(m.cuda(), cfg, W, ref, e, obj, 3)
+
+
+@pytest.mark.parametrize('obj,reverse_kl', (('ppo', True), ('pmpo', True), ('pmpo', False)))
+def test_off_policy_learn_vs_oracle_mixed_model(obj, reverse_kl):
+    """The same with a Beta head next to the discrete one: old_cont_params and the continuous log-probs come from the perturbed behaviour weights too."""
+    from dreamer4_amd import DynamicsWorldModel
+    from util import randomize_weights
+    torch.manual_seed(1)
+    m = randomize_weights(DynamicsWorldModel(dim=64, dim_latent=8, num_latent_tokens=6, depth=4, time_block_every=2, attn_heads=2, num_discrete_actions=(3, 2), num_tasks=0,
+                                             num_continuous_actions=2, pmpo_reverse_kl=reverse_kl, pmpo_kl_div_loss_weight=0.3), seed=3, terminal_bias=-2.)
+    with torch.no_grad():
+        m.action_embedder.discrete_action_unembed.mul_(0.02)
+        m.action_embedder.continuous_action_unembed.mul_(30.)
+    cfg, W, ref, e, outside, kl = off_policy_case(m, 5, 6, 62, 0.5, 0.2)
+    assert 0.2 <= outside <= 0.8 and kl >= 1e-2, (outside, kl)
+    check_off_policy_learn(m.cuda(), cfg, W, ref, e, obj, 4)
