@@ -203,6 +203,7 @@ SYMBOLS = {
     'd4_time_attn_decode': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P] + [_I] * 8 + [_P, _F, _I, _I, _P]),
     'd4_gemm_family_configs': (_I, [_I]),
     'd4_gemm_run': (_I, [C.POINTER(GemmDesc), _I, _I, _P]),
+    'd4_gemm_run_rowmap': (_I, [C.POINTER(GemmDesc), _I, _I, _I, _I, _I, _I, _P]),
     'd4_gemm_run_pair': (_I, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _I, _I, _P]),
     'd4_tile16_weights': (_I, [_P, _I, _P, _I, _I, _P]),
     'd4_frame_attn_out': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 2 + [_P] + [_I] * 3 + [_F] + [_I] * 3 + [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),

@@ -227,6 +227,7 @@ __global__ void assemble_kernel(AssembleArgs p) {
             const int rank = (s >= 1 && s <= cns) ? s - 1 : ((p.has_agent && s == p.S - 1) ? cns : -1);
             if (rank >= 0) p.compact[(f * (cns + p.has_agent) + rank) * D + d] = v;
         }
+        if (p.dense && (s <= p.ns || s > p.ns + p.nr)) p.dense[(f * (p.S - p.nr) + (s <= p.ns ? s : s - p.nr)) * D + d] = v;
     }
 }
 // the same, four features per thread (16-byte loads / stores, one set of index divisions per four elements): D % 8 == 0, 16-byte aligned tables
@@ -281,13 +282,14 @@ __global__ __launch_bounds__(256) void assemble4_kernel(AssembleArgs p) {
             const int rank = (s >= 1 && s <= cns) ? s - 1 : ((p.has_agent && s == p.S - 1) ? cns : -1);
             if (rank >= 0) *reinterpret_cast<f32x4*>(p.compact + (f * (cns + p.has_agent) + rank) * p.D + d) = v;
         }
+        if (p.dense && (s <= p.ns || s > p.ns + p.nr)) *reinterpret_cast<f32x4*>(p.dense + (f * (p.S - p.nr) + (s <= p.ns ? s : s - p.nr)) * p.D + d) = v;
     }
 }
 int assemble_tokens(const AssembleArgs& p, hipStream_t s) {
     const int64_t n = (int64_t)p.B * p.Tq * p.S * p.D;
     if (n == 0) return 0;
     auto al = [](const void* q) { return ((uintptr_t)q % 16) == 0; };
-    const bool vec = (p.D % 8) == 0 && al(p.tokens) && al(p.compact) && al(p.signal_embed) && al(p.step_embed) && al(p.space) && al(p.registers) &&
+    const bool vec = (p.D % 8) == 0 && al(p.tokens) && al(p.compact) && al(p.dense) && al(p.signal_embed) && al(p.step_embed) && al(p.space) && al(p.registers) &&
                      al(p.action_embed) && al(p.cont_embed) && al(p.action_learned) && al(p.agent_embed) && al(p.task_embed);
     if (vec) D4_GLUE_LAUNCH(GL_ASSEMBLE, 4.0 * (double)n + 4.0 * p.B * p.Tq * p.ns * p.D, assemble4_kernel, grid1d(n / 4), dim3(256), 0, s, p);
     else D4_GLUE_LAUNCH(GL_ASSEMBLE, 4.0 * (double)n + 4.0 * p.B * p.Tq * p.ns * p.D, assemble_kernel, grid1d(n), dim3(256), 0, s, p);

@@ -152,6 +152,23 @@ struct d4_engine {
     float *lin_kv_w, *lin_q, *lin_gate, *lout_kv_w, *lout_q, *lout_gate, *qtmp;
     float *lout_w;                         // [dl][hd] = to_latent_pred.2.weight @ to_latent_pred.1.attn.to_out.weight
     int32_t *action_offsets, *action_sizes;
+    // ---- the register rows of slab 0 are the parameter `registers`, the same in every frame and evaluation (fp32 engine, dynamics mode):
+    // their share of the two products that read slab 0 row by row is computed at prepare and prefilled; an evaluation projects the other rows only.
+    // Layout index ly = 0: the denoise layout (S - 1 rows per frame), 1: the clean layout (S rows).  Null pointers: the engine never takes that path.
+    float* slab0r = nullptr;               // [Fr][S - nr][D]: the rows of slab 0 without the register block (assemble_tokens writes it with slab 0)
+    float* c0_proj = nullptr;              // [nr][Nproj0]: the register rows of layer 0's fused projection
+    float* proj0r[2] = {nullptr, nullptr}; // [maxFrames * (S - 1 + ly)][Nproj0]: layer 0's projection in the reduced form; only the row-mapped launch writes
+                                           // it, so the register rows prefilled at prepare stay valid (the full form keeps e->proj0)
+    bool l0_ready = false;                 // prepare ran the constant block on the persistent split-operand kernel and prefilled proj0r
+    // keys of slab 0 for the in-loop pools p = 0 .. depth - 2: region p of layout ly starts at kvr[ly] + p * kvr_stride[ly] and holds
+    // [maxFrames * (S - 1 + ly) rows: slab block 0, used from its END downwards][(2 depth - 2) * Mmax rows: slab blocks 1 ..]; a call of M rows reads
+    // its keys [L][M][hp] at (end of block 0) - M * hp, so the prefilled register rows sit at a position counted from the end of block 0 that does
+    // not depend on the call's frame count, and the blocks 1 .. of no call overlap block 0 of another
+    float* ck = nullptr;                   // [depth - 1][nr][hp]: the register rows' keys per in-loop pool
+    float* kvr[2] = {nullptr, nullptr};
+    size_t kvr_stride[2] = {0, 0};
+    int64_t pkv_stride = 0;                // pkv_w[p + 1] - pkv_w[p] (elements), constant: the batched launch's weight stride
+    bool ck_ready = false;                 // prepare ran the constant key blocks on the LDS-DMA family and prefilled kvr
 
     // ---- activations (workspace)
     float *cslabs, *xfc, *xpool_c, *att_c, *pool_u;                   // row-compacted hiddens (spatial + agent rows) and final tokens

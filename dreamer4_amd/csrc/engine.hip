@@ -141,6 +141,31 @@ int engine_layout(d4_engine* e, bool assign) {
     e->pool_kv = fl((size_t)e->nslab * M * 2 * hp);
     e->pool_att = fl(M * hp);
     e->pool_u = fl(M * (size_t)e->php * D);
+    // constant register rows (engine.h): the dense image of slab 0's other rows, the constant blocks, and the buffers only the reduced forms write
+    e->slab0r = e->c0_proj = e->ck = nullptr;
+    e->proj0r[0] = e->proj0r[1] = e->kvr[0] = e->kvr[1] = nullptr;
+    e->kvr_stride[0] = e->kvr_stride[1] = 0; e->pkv_stride = 0;
+    const int nr = c.num_register_tokens;
+    const bool const_rows = !e->encoder && !e->decoder && (!e->bf16 || e->split) && nr > 0;
+    const bool const_l0 = const_rows && e->split;                                        // layer 0's projection: the split-operand family only
+    const bool const_keys = const_rows && depth >= 2 && c.pool_heads == 4 && D <= 1024;   // the pools' mix path (keys only, [L][M][hp])
+    if (const_l0 || const_keys) e->slab0r = fl(Fr * (size_t)(S - nr) * D);
+    if (const_l0) {
+        e->c0_proj = fl((size_t)nr * e->Nproj0);
+        for (int ly = 0; ly < 2; ++ly) e->proj0r[ly] = fl(Fr * (size_t)(S - 1 + ly) * e->Nproj0);
+    }
+    if (const_keys) {
+        e->ck = fl((size_t)(depth - 1) * nr * hp);
+        for (int ly = 0; ly < 2; ++ly) {
+            e->kvr_stride[ly] = (size_t)(2 * depth - 1) * Fr * (size_t)(S - 1 + ly) * hp;
+            e->kvr[ly] = fl((size_t)(depth - 1) * e->kvr_stride[ly]);
+        }
+        // the pools' folded key weights were carved at equal distances above (the same two sizes per pool): the batched launch's weight stride
+        if (assign) {
+            e->pkv_stride = e->pkv_w[1] - e->pkv_w[0];
+            for (int p = 1; p + 1 < depth; ++p) if (e->pkv_w[p + 1] - e->pkv_w[p] != e->pkv_stride) e->pkv_stride = 0;
+        }
+    }
     if (e->h2) {
         e->aexp_slab = reinterpret_cast<int*>(alloc_bytes((size_t)e->nslab * M * sizeof(int)));
         e->aexp_tmp_rows = (size_t)e->nslab * M;
@@ -744,6 +769,55 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
         }
     }
 
+    // ---- the register rows' share of the products that read slab 0 row by row (engine.h), once per set of weights.  Each block is made by
+    // the kernel family the full product takes in an evaluation — pinned with rule_M, the dispatcher asked first (no family rule, no block: the engine
+    // keeps the full launches) — so the prefilled rows carry the bits the full launch writes; then broadcast into every frame of the reduced-form buffers.
+    e->l0_ready = e->ck_ready = false;
+    if (e->c0_proj || e->ck) {
+        const int nr = c.num_register_tokens, lo = 1 + ns, pin = 4096;
+        t_bf16 = e->bf16 ? e : nullptr;
+        auto planes = [e](GemmArgs g) {                      // the call as engine_gemm hands it to gemm()
+            if (e->bf16)
+                for (const auto& m : e->mirrors)
+                    if (g.W >= m.src && g.W < m.src + m.n) { g.Wb = m.dst + (g.W - m.src); break; }
+            if (g.Wb && e->split) { g.wplane = (int64_t)e->bf16_cap; if (!gemm_x3_applicable(g)) { g.Wb = nullptr; g.wplane = 0; } }
+            return g;
+        };
+        rc = 0;
+        if (e->c0_proj) {
+            GemmArgs g{e->registers, D, e->proj_w[0], D, e->c0_proj, e->Nproj0, e->proj_b[0], nullptr, 0, nr, e->Nproj0, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+            g.rule_M = pin;
+            if (gemm_rule_takes_x3sk(planes(g))) {
+                rc = engine_gemm(g, s);
+                for (int ly = 0; ly < 2 && !rc; ++ly) {
+                    const int Sl = e->S - 1 + ly;
+                    rc = copy_rows(e->c0_proj, 0, e->proj0r[ly] + (size_t)lo * e->Nproj0, Sl * e->Nproj0, e->Fr, nr * e->Nproj0, s);
+                }
+                e->l0_ready = !rc;
+            }
+        }
+        if (!rc && e->ck && e->pkv_stride > 0) {
+            bool ok = true;
+            for (int p = 0; p < c.depth - 1; ++p) {
+                GemmArgs g{e->registers, D, e->pkv_w[p], D, e->ck + (size_t)p * nr * hp, hp, nullptr, nullptr, 0, nr, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+                g.rule_M = pin;
+                ok = ok && gemm_rule_takes_v2(planes(g));
+            }
+            for (int p = 0; ok && p < c.depth - 1 && !rc; ++p) {
+                GemmArgs g{e->registers, D, e->pkv_w[p], D, e->ck + (size_t)p * nr * hp, hp, nullptr, nullptr, 0, nr, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+                g.rule_M = pin;
+                rc = engine_gemm(g, s);
+                for (int ly = 0; ly < 2 && !rc; ++ly) {
+                    const int Sl = e->S - 1 + ly;
+                    rc = copy_rows(e->ck + (size_t)p * nr * hp, 0, e->kvr[ly] + (size_t)p * e->kvr_stride[ly] + (size_t)lo * hp, Sl * hp, e->Fr, nr * hp, s);
+                }
+            }
+            e->ck_ready = ok && !rc;
+        }
+        t_bf16 = nullptr;
+        if (rc) return rc;
+    }
+
     int32_t offs[D4_MAX_ACTION_TYPES] = {0}, sizes[D4_MAX_ACTION_TYPES] = {0};
     int o = 0;
     for (int a = 0; a < e->na; ++a) { offs[a] = o; sizes[a] = c.num_discrete_actions[a]; o += sizes[a]; }
@@ -774,11 +848,16 @@ int g_rollout_batched_heads = 1;      // test hook d4_debug_switch("rollout_batc
 int g_lqap_in_fused = 1;              // d4_debug_switch("lqap_in_fused"): latents -> K | V -> learned-query attention in one per-frame kernel (latent_ends.hip)
 int g_lqap_out_fused = 1;             // d4_debug_switch("lqap_out_fused"): learned-query attention -> latent prediction in one per-frame kernel
 int g_last_layer_compact_q = 1;       // d4_debug_switch("last_layer_compact_q"): a denoise evaluation's last layer projects q | head gates on the compact rows only
+// The register rows of slab 0 are constants of the weights (fp32 engine, dynamics mode): test hooks, 0 = the full launches, same bits
+int g_layer0_const_rows = 1;          // d4_debug_switch("layer0_const_rows"): layer 0's fused projection runs on the rows that change; the register rows were prefilled at prepare
+int g_pool_const_keys = 1;            // d4_debug_switch("pool_const_keys"): the in-loop pools' keys of slab 0 likewise, the changing rows for all pools in one batched launch
 unsigned g_launch_count = 0;          // kernel launches so far (common.h: D4_LAUNCH_CHECK; read / reset through d4_debug_switch("launch_count"))
 // rule_M > 0 (the final pool of an evaluation that keeps the agent row alone): the rows the same pool has when the spatial rows are kept too — every
 // product and the mix are dispatched as for that row count (GemmArgs::rule_M), so the rows computed carry the bits they have there
 static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int M, hipStream_t s, const float* hiddens = nullptr,
-                      float* y_compact = nullptr, int S = 0, int has_agent = 1, int rule_M = 0) {
+                      float* y_compact = nullptr, int S = 0, int has_agent = 1, int rule_M = 0, float* keys0 = nullptr) {
+    // keys0 (an in-loop pool of an evaluation that takes the constant register rows): the pool's keys [L][M][hp] with slab 0's block already in place
+    // (prefilled register rows + the evaluation's batched launch) — the key problem covers slabs 1 .. L - 1, pinned to the family of all L
     if (!hiddens) hiddens = e->slabs;
     const d4_config& c = e->c;
     const int D = e->D, hp = e->hp;
@@ -808,6 +887,10 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
         } else {
         GemmArgs gk{hiddens, D, e->pkv_w[p], D, e->pool_kv, hp, nullptr, nullptr, 0, L * M, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
         gk.rule_M = L * rule_M;
+        if (keys0) {
+            gk.A = hiddens + (size_t)M * D; gk.C = keys0 + (size_t)M * hp; gk.M = (L - 1) * M; gk.rule_M = L * M;
+            pm.k = keys0;
+        }
         if ((rc = gemm_two(gq, gk, s))) return rc;
         if (t_bf16) pm.k_b = t_bf16->shadow_of(e->pool_kv);               // bf16 keys (the only copy of them in this mode)
         }
@@ -908,6 +991,32 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         }
         return gemm_rule_takes_v2(g);
     };
+    // The register rows of slab 0 (rows [1 + ns, 1 + ns + nr) of every frame) are the parameter `registers`: their share of layer 0's projection and of
+    // the in-loop pools' keys was computed at prepare.  Each reduced form is taken only where the full product AND its reduced parts run on the family
+    // the constant block was made by, by the dispatcher's own rule on the calls as they are made (rule_M = the full row count).
+    const int nr = c.num_register_tokens, Sc = S - nr, reg_lo = 1 + ns, ly = has_agent;
+    auto x3sk_family = [e](int M_, int N_, int K_, int flags, const float* W, int rule_M = 0) {
+        GemmArgs g{};
+        g.M = M_; g.N = N_; g.K = K_; g.lda = K_; g.ldw = K_; g.ldc = N_; g.flags = flags; g.rms_eps = RMS_EPS; g.rule_M = rule_M; g.W = W;
+        if (!e->split) return false;
+        for (const auto& m : e->mirrors)
+            if (W >= m.src && W < m.src + m.n) { g.Wb = m.dst + (W - m.src); break; }
+        if (!g.Wb) return false;
+        g.wplane = (int64_t)e->bf16_cap;
+        if (!gemm_x3_applicable(g)) return false;
+        return gemm_rule_takes_x3sk(g);
+    };
+    const bool dynamics = !e->encoder && !e->decoder;
+    const bool l0_const = g_layer0_const_rows && dynamics && e->l0_ready && Sc >= 1 &&
+                          x3sk_family(M, e->Nproj0, D, GEMM_RMS_ROWSCALE, e->proj_w[0]) && x3sk_family(Fr * Sc, e->Nproj0, D, GEMM_RMS_ROWSCALE, e->proj_w[0], M);
+    bool ck_const = g_pool_const_keys && dynamics && e->ck_ready && Sc >= 1 && c.depth >= 2;
+    for (int p = 0; ck_const && p < c.depth - 1; ++p) {
+        const int L = 2 * p + 3;
+        ck_const = tiled_family(L * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p]) && tiled_family((L - 1) * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p], L * M) &&
+                   tiled_family(Fr * Sc, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p], 3 * M);
+    }
+    float* P0 = l0_const ? e->proj0r[ly] : e->proj0;          // layer 0's projection of this evaluation (the same layout either way)
+    auto keys0 = [&](int p) { return ck_const ? e->kvr[ly] + (size_t)p * e->kvr_stride[ly] + (size_t)e->Fr * S * e->hp - (size_t)M * e->hp : nullptr; };
     int rc;
     if (e->h2) {                              // fp16x2 mode: every slab is rewritten by this evaluation -> no row exponent of the last one is valid
         e->aexp_M = (size_t)M;
@@ -972,18 +1081,27 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         a.action_offsets = e->action_offsets;
         a.B = B; a.Tq = Tq; a.S = S; a.D = D; a.ns = ns; a.nr = c.num_register_tokens; a.na = e->na; a.step_log2 = step_log2;
         a.compact = e->cslabs; a.has_agent = has_agent; a.compact_spatial = agent_only ? 0 : 1;
+        a.dense = (l0_const || ck_const) ? e->slab0r : nullptr;
         D4_REQUIRE(tasks == nullptr || c.num_tasks > 0, "tasks given but num_tasks == 0");
         if ((rc = assemble_tokens(a, s))) return rc;
+    }
+    if (ck_const) {
+        // slab 0's keys for every in-loop pool, the rows that change: one batched launch (member p: pool p's folded key weights, region p of kvr)
+        GemmArgs gb{e->slab0r, D, e->pkv_w[0], D, keys0(0), e->hp, nullptr, nullptr, 0, Fr * Sc, e->hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+        gb.batch = c.depth - 1; gb.strideA = 0; gb.strideW = e->pkv_stride; gb.strideC = (int64_t)e->kvr_stride[ly];
+        gb.rule_M = 3 * M;
+        gb.rm_Sc = (uint16_t)Sc; gb.rm_lo = (uint16_t)reg_lo; gb.rm_nr = (uint16_t)nr;
+        if ((rc = engine_gemm(gb, s))) return rc;
     }
     }
     if (t_bf16) if (uint16_t* sb = t_bf16->shadow_of(slab0)) { if ((rc = cvt_rows_bf16(slab0, D, sb, D, M, D, s))) return rc; }
 
     // ---- trunk (AxialSpaceTimeTransformer.forward, D4:3040-3223)
     const float* x_in = slab0;
-    const float* vres = e->proj0 + 3 * hd + 2 * h;
+    const float* vres = P0 + 3 * hd + 2 * h;
     for (int l = 0; l < c.depth; ++l) {
         const AttnW& a = e->layer_attn[l];
-        float* P = l == 0 ? e->proj0 : e->proj;
+        float* P = l == 0 ? P0 : e->proj;
         const int ldp = l == 0 ? e->Nproj0 : e->Nproj;
         // Last layer of a denoise evaluation (the compact tail below): its attention reads the queries and head gates of the ns spatial rows only, so
         // q | gates are projected on the compact rows (e->xpool_c, the same values as those rows of x_in: the same row scale) and k | v | mix on every
@@ -998,6 +1116,12 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             GemmArgs gb{e->xpool_c, D, e->proj_wc + (size_t)(2 * hd + h) * D, D, e->qc, e->ldqc, e->proj_bc + 2 * hd + h, nullptr, 0, Mc, hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             gb.rule_M = M;
             if ((rc = gemm_two(ga, gb, s))) return rc;
+        } else if (l == 0 && l0_const) {
+            // the rows that change, from their dense image, into their places around the prefilled register rows
+            GemmArgs g0{e->slab0r, D, e->proj_w[0], D, P, ldp, e->proj_b[0], nullptr, 0, Fr * Sc, ldp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+            g0.rule_M = M;
+            g0.rm_Sc = (uint16_t)Sc; g0.rm_lo = (uint16_t)reg_lo; g0.rm_nr = (uint16_t)nr;
+            if ((rc = engine_gemm(g0, s))) return rc;
         } else
         if ((rc = gemm_simple(x_in, D, e->proj_w[l], D, P, ldp, M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_b[l], nullptr, 0, s))) return rc;
         bool fused_out = false;
@@ -1065,7 +1189,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         if ((rc = ff_block(e, e->ffp[l], e->layer_ff[l].out_b, h1, D, h2, D, M, s, cslab(2 * l + 2), S, has_agent))) return rc;
         if (l != c.depth - 1) {
             float* xc = (denoise_only && l == c.depth - 2 && !e->is_time[c.depth - 1] && S <= 16 && S >= 8) ? e->xpool_c : nullptr;
-            if ((rc = pool_block(e, l, h2, e->xpool, 2 * l + 3, M, s, nullptr, xc, S, has_agent))) return rc;
+            if ((rc = pool_block(e, l, h2, e->xpool, 2 * l + 3, M, s, nullptr, xc, S, has_agent, 0, keys0(l)))) return rc;
             x_in = e->xpool;
         }
     }
@@ -1536,7 +1660,8 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
     const bool lean = d4::g_rollout_clean_agent_row != 0;
     const int lean_keep = (lean && d4::engine_clean_agent_only(e)) ? 1 : c.num_spatial_tokens + 1;
     // what a captured frame's launches depend on besides its shape: the clean-evaluation form and the forms of the latent-token ends (test hooks)
-    const int variant = (lean ? 1 : 0) | (d4::g_lqap_in_fused ? 2 : 0) | (d4::g_lqap_out_fused ? 4 : 0) | (d4::g_last_layer_compact_q ? 8 : 0);
+    const int variant = (lean ? 1 : 0) | (d4::g_lqap_in_fused ? 2 : 0) | (d4::g_lqap_out_fused ? 4 : 0) | (d4::g_last_layer_compact_q ? 8 : 0) |
+                        (d4::g_layer0_const_rows ? 16 : 0) | (d4::g_pool_const_keys ? 32 : 0);
     // Only the sampled action (policy head) and the terminal feed the next frame; values and rewards are outputs nobody reads inside the loop: they
     // are computed once after it, over the whole agent history [B][F][D] — the caller's, else the engine's own (one frame: the frame's rows).
     const float* hist = nullptr;
@@ -1731,6 +1856,8 @@ int d4_debug_switch(const char* name, int value) {
     else if (name && !strcmp(name, "lqap_in_fused")) sw = &d4::g_lqap_in_fused;
     else if (name && !strcmp(name, "lqap_out_fused")) sw = &d4::g_lqap_out_fused;
     else if (name && !strcmp(name, "last_layer_compact_q")) sw = &d4::g_last_layer_compact_q;
+    else if (name && !strcmp(name, "layer0_const_rows")) sw = &d4::g_layer0_const_rows;
+    else if (name && !strcmp(name, "pool_const_keys")) sw = &d4::g_pool_const_keys;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
     else if (name && !strcmp(name, "pool_mix_deep")) sw = &d4::g_pool_mix_deep;
     else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
@@ -2110,9 +2237,20 @@ int d4_gemm_family_configs(int family) {
     }
     return -1;
 }
+static int gemm_run_args(const d4::GemmArgs& g, int family, int config, void* stream);
 int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream) {
     if (int rc = gemm_desc_check("d4_gemm_run", d)) return rc;
-    const d4::GemmArgs g = gemm_args_of(*d);
+    return gemm_run_args(gemm_args_of(*d), family, config, stream);
+}
+// ... with the output row map (GemmArgs::rm_*): the families that implement it run it, every other launcher refuses
+int d4_gemm_run_rowmap(const d4_gemm_desc* d, int family, int config, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream) {
+    if (int rc = gemm_desc_check("d4_gemm_run_rowmap", d)) return rc;
+    D4_REQUIRE(rm_Sc >= 1 && rm_nr >= 0 && rm_lo >= 0 && rm_lo <= rm_Sc && rm_S == rm_Sc + rm_nr && rm_S <= 65535, "d4_gemm_run_rowmap: bad row map (Sc=%d S=%d lo=%d nr=%d)", rm_Sc, rm_S, rm_lo, rm_nr);
+    d4::GemmArgs g = gemm_args_of(*d);
+    g.rm_Sc = (uint16_t)rm_Sc; g.rm_lo = (uint16_t)rm_lo; g.rm_nr = (uint16_t)rm_nr;
+    return gemm_run_args(g, family, config, stream);
+}
+static int gemm_run_args(const d4::GemmArgs& g, int family, int config, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool al16 = ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && (g.lda % 4) == 0 && (g.ldw % 4) == 0;
 #define D4_RUN_REFUSE(cond, why) D4_REQUIRE(cond, "d4_gemm_run: call not supported (family %d, configuration %d, M=%d N=%d K=%d flags=%d: " why ")", family, config, g.M, g.N, g.K, g.flags)

@@ -911,6 +911,8 @@ bool gemm_h2_takes(const GemmArgs& p) {
 int gemm_pair(const GemmArgs& a_in, const GemmArgs& b_in, hipStream_t stream) {
     std::lock_guard<std::recursive_mutex> lock(gemm_mutex());
     GemmArgs a = a_in, b = b_in;
+    if (int rc = gemm_rowmap_refused(a, "gemm_pair")) return rc;
+    if (int rc = gemm_rowmap_refused(b, "gemm_pair")) return rc;
     const bool fp32_rule = (!a.Wb || (a.wplane > 0 && a.N < 2048)) && (!b.Wb || (b.wplane > 0 && b.N < 2048)) &&     // neither goes to a bf16 / split-operand kernel
                            !gemm_h2_takes(a) && !gemm_h2_takes(b);
     if (fp32_rule && g_forced_cfg < 0 && a.M > 0 && b.M > 0 && a.K == b.K && use_v2(a) && use_v2(b) && !gemm_skinny_applicable(a) &&
@@ -945,6 +947,25 @@ int gemm_pair(const GemmArgs& a_in, const GemmArgs& b_in, hipStream_t stream) {
 static std::recursive_mutex g_gemm_mu;
 static std::recursive_mutex& gemm_mutex() { return g_gemm_mu; }
 
+// The output row map (GemmArgs::rm_*): well formed, and on a call whose epilogue the two mapped kernels implement (bias and row scale only).
+bool gemm_rowmap_ok(const GemmArgs& p) {
+    if (p.rm_Sc <= 0) return true;
+    return p.rm_lo <= p.rm_Sc && p.C && !p.R && !p.C2 && !p.Cb && !p.C2b &&
+           !(p.flags & ~GEMM_RMS_ROWSCALE);
+}
+// A launcher that does not implement the map must not ignore it.
+int gemm_rowmap_refused(const GemmArgs& p, const char* who) {
+    D4_REQUIRE(p.rm_Sc <= 0, "%s: this kernel family does not implement the output row map (M=%d N=%d K=%d flags=%d)", who, p.M, p.N, p.K, p.flags);
+    return 0;
+}
+
+// Would gemm() below run this call on the persistent split-operand kernel (gemm_x3sk.hip)?  The same tests in the same order as gemm().
+bool gemm_rule_takes_x3sk(const GemmArgs& p) {
+    if (p.M < 1 || g_forced_cfg >= 0 || (p.flags & (GEMM_TRANS_A | GEMM_TRANS_B)) || !p.Wb || p.wplane <= 0 || p.wscale) return false;
+    const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
+    return wide && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && (p.rule_M > 0 ? p.rule_M : p.M) >= 1024));
+}
+
 // Would gemm() below run this call — these exact arguments, weight planes and rule_M included — on the LDS-DMA f32 family (gemm2.hip through gemm_v2)?
 // The same tests in the same order as gemm(); a forced configuration answers false (a forced call is not taken by rule).  The engine asks this before
 // it replaces a product by a kernel that carries that family's bits (engine.hip: the latent-token ends, the last layer's split projection).
@@ -960,8 +981,9 @@ bool gemm_rule_takes_v2(const GemmArgs& p) {
     }
     if (p.Wb && p.wplane > 0) {
         const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
-        if (wide && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && p.M >= 1024))) return false;
-        if (wide && p.M >= 256 && gemm_x3_applicable(p)) return false;
+        const int rm = p.rule_M > 0 ? p.rule_M : p.M;
+        if (wide && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && rm >= 1024))) return false;
+        if (wide && rm >= 256 && gemm_x3_applicable(p)) return false;
         GemmArgs q = p;
         q.Wb = nullptr; q.wplane = 0;
         return gemm_rule_takes_v2(q);
@@ -981,10 +1003,11 @@ int gemm(const GemmArgs& p, hipStream_t stream) {
     D4_REQUIRE(!((p.flags & GEMM_RMS_ROWSCALE) && ta), "gemm: rms rowscale needs a non-transposed A");
     D4_REQUIRE(!((p.flags & GEMM_SWIGLU) && (p.N % 64) != 0), "gemm: swiglu needs N %% 64 == 0 (packed pairs)");
     D4_REQUIRE(!((p.flags & GEMM_SWIGLU) && (ta || tb)), "gemm: swiglu epilogue is forward-only");
+    D4_REQUIRE(gemm_rowmap_ok(p), "gemm: bad output row map (Sc=%d lo=%d nr=%d) or an epilogue it does not cover (flags=%d)", p.rm_Sc, p.rm_lo, p.rm_nr, p.flags);
     // fp16x2 engine mode (two fp16 planes of W + row scales, gemm_h2.hip): the rule gemm_h2_takes names the calls; every other call drops the
     // planes and runs on the f32-input kernels
     if (p.Wb && p.wplane > 0 && p.wscale) {
-        if (gemm_h2_takes(p)) return gemm_v4(p, stream);
+        if (gemm_h2_takes(p)) { if (int rc = gemm_rowmap_refused(p, "gemm_h2")) return rc; return gemm_v4(p, stream); }
         GemmArgs q = p;
         q.Wb = nullptr; q.wplane = 0; q.wscale = nullptr; q.aexp = nullptr;
         return gemm(q, stream);
@@ -999,12 +1022,15 @@ int gemm(const GemmArgs& p, hipStream_t stream) {
         // half full as 128 x 64 half tiles — bit-identical to the plain kernel; same-box A/B pairs, profiles/r03l_ab_late_changes.txt: 188.8 vs
         // 191.8-192.4 (half-tile calls only) vs 199.3-200.0 ms (never) per step on a mid-speed box, level on the fastest one).
         const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
-        if (wide && g_forced_cfg < 0 && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && p.M >= 1024))) return launch_v3sk(p, stream);
-        if (wide && p.M >= 256 && gemm_x3_applicable(p)) return gemm_v3(p, stream);
+        // (rule_M: a caller that runs a subset of a product's rows keeps the family of the whole product)
+        const int rm = p.rule_M > 0 ? p.rule_M : p.M;
+        if (wide && g_forced_cfg < 0 && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && rm >= 1024))) return launch_v3sk(p, stream);
+        if (wide && rm >= 256 && gemm_x3_applicable(p)) return gemm_v3(p, stream);
         GemmArgs q = p;
         q.Wb = nullptr; q.wplane = 0;
         return gemm(q, stream);
     }
+    if (p.Wb) if (int rc = gemm_rowmap_refused(p, "gemm_bf16")) return rc;
     if (p.Wb && p.Ab && gemm_bf16a_applicable(p)) return gemm_bf16a(p, stream);     // bf16 engine, the activation has a bf16 image: both operands by LDS-DMA
     if (p.Wb) return gemm_bf16(p, stream);
     // test hook: 100 + c forces configuration c of the second family, 0 .. N_TILE_CFG-1 a configuration of this one
@@ -1013,6 +1039,7 @@ int gemm(const GemmArgs& p, hipStream_t stream) {
     // few rows x long K (the heads' hidden layers at rollout batch): the contraction cut four ways inside the workgroup — a rule on the shape
     if ((g_forced_cfg < 0 && gemm2_ksplit_rule(p)) || (g_forced_cfg == 199 && gemm2_ksplit_applicable(p))) return launch_v2ks(p, stream);      // (199: test hook, any shape it can run)
     if ((g_forced_cfg < 0 || g_forced_cfg >= 300) && use_v2(p)) return gemm_v2(p, stream);      // (300 + c forces a tile of the split-operand family only)
+    if (int rc = gemm_rowmap_refused(p, "gemm (first fp32 family)")) return rc;
     if (!ta && !tb) return launch_t<false, false>(p, stream);
     if (!ta && tb) return launch_t<false, true>(p, stream);
     if (ta && tb) return launch_t<true, true>(p, stream);

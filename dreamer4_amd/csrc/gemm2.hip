@@ -40,7 +40,9 @@ __device__ __forceinline__ int chunk_swizzle(int row) {
     else return (0x78 >> (((row >> 2) & 3) * 2)) & 3;          // {0, 2, 3, 1} packed two bits each: 0b01'11'10'00
 }
 
-template <int WGM, int WGN, int TM, int TN, int NS, int BK, bool RMS>
+// RMAP: the output rows go through GemmArgs' row map (rm_*: dense frames of rm_Sc rows into frames of rm_Sc + rm_nr rows around a gap); an instantiation of its
+// own (gemm2_rowmap_kernel) — every other kernel passes false and keeps its code.
+template <int WGM, int WGN, int TM, int TN, int NS, int BK, bool RMS, bool RMAP = false>
 __device__ __forceinline__ void gemm2_body(GemmArgs& p, int bid, const int bz) {
     static_assert(BK == 16 || BK == 32, "k-tile");
     constexpr int CH = BK / 4;                      // 16-byte chunks per tile row
@@ -281,7 +283,12 @@ __device__ __forceinline__ void gemm2_body(GemmArgs& p, int bid, const int bz) {
                     for (int e = 0; e < 4; ++e) if (full || gn + e < p.N) v[e] += rp[e];
                 }
             }
-            float* cp = p.C + (int64_t)gm * p.ldc + gn;
+            int64_t crow = gm;
+            if constexpr (RMAP) {
+                const int fr = gm / p.rm_Sc, t = gm - fr * p.rm_Sc;
+                crow = (int64_t)fr * (p.rm_Sc + p.rm_nr) + t + (t >= p.rm_lo ? p.rm_nr : 0);
+            }
+            float* cp = p.C + crow * p.ldc + gn;
             if (p.flags & GEMM_ACCUMULATE) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (full || gn + e < p.N) v[e] += cp[e];
@@ -306,6 +313,12 @@ __device__ __forceinline__ void gemm2_body(GemmArgs& p, int bid, const int bz) {
 template <int WGM, int WGN, int TM, int TN, int NS, int BK, bool RMS>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm2_kernel(GemmArgs p) {
     gemm2_body<WGM, WGN, TM, TN, NS, BK, RMS>(p, blockIdx.x, blockIdx.y);
+}
+
+// the single / batched launch with the row-mapped store (GemmArgs::rm_Sc > 0; plain epilogue only: launch2 checks)
+template <int WGM, int WGN, int TM, int TN, int NS, int BK, bool RMS>
+__global__ __launch_bounds__(WGM* WGN * 64) void gemm2_rowmap_kernel(GemmArgs p) {
+    gemm2_body<WGM, WGN, TM, TN, NS, BK, RMS, true>(p, blockIdx.x, blockIdx.y);
 }
 
 // Two independent GEMMs in ONE grid (blocks [0, nblk_a) work on `a`, the rest on `b`): launch ramp and tail are paid once.  Used for the
@@ -469,6 +482,7 @@ bool gemm2_ksplit_rule(const GemmArgs& p) {
 }
 
 int gemm2_ksplit_launch(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(p, "gemm2_ksplit")) return rc;
     D4_REQUIRE(gemm2_ksplit_applicable(p), "gemm2_ksplit: call not supported (M=%d N=%d K=%d flags=%d)", p.M, p.N, p.K, p.flags);
     const size_t lds = (size_t)KS_GROUPS * KS_RING_F * sizeof(float);
     static DeviceOnce attr_set;
@@ -520,12 +534,14 @@ template <int WGM, int WGN, int TM, int TN, int NS, int BK>
 static int launch2(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
     constexpr int BM = WGM * TM * 16, BN = WGN * TN * 16;
     const size_t lds = (size_t)(NS * (BM + BN) * BK + BM) * sizeof(float);
-    const bool rms = (p.flags & GEMM_RMS_ROWSCALE) != 0;
-    auto k = rms ? gemm2_kernel<WGM, WGN, TM, TN, NS, BK, true> : gemm2_kernel<WGM, WGN, TM, TN, NS, BK, false>;
-    static DeviceOnce attr_set[2];
-    if (attr_set[rms].need()) {
+    const bool rms = (p.flags & GEMM_RMS_ROWSCALE) != 0, rmap = p.rm_Sc > 0;
+    D4_REQUIRE(gemm_rowmap_ok(p), "gemm2: bad output row map (Sc=%d lo=%d nr=%d) or an epilogue it does not cover (flags=%d)", p.rm_Sc, p.rm_lo, p.rm_nr, p.flags);
+    auto k = rmap ? (rms ? gemm2_rowmap_kernel<WGM, WGN, TM, TN, NS, BK, true> : gemm2_rowmap_kernel<WGM, WGN, TM, TN, NS, BK, false>)
+                  : (rms ? gemm2_kernel<WGM, WGN, TM, TN, NS, BK, true> : gemm2_kernel<WGM, WGN, TM, TN, NS, BK, false>);
+    static DeviceOnce attr_set[4];
+    if (attr_set[2 * rmap + rms].need()) {
         D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[rms].done();
+        attr_set[2 * rmap + rms].done();
     }
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), p.batch > 0 ? p.batch : 1), block(WGM * WGN * 64);
     if (ea) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)lds, stream, ea, eb, 0, p);
@@ -562,6 +578,8 @@ bool gemm2_pair_applicable(const GemmArgs& a, const GemmArgs& b) {
 }
 
 int gemm2_pair_launch(int c, const GemmArgs& a, const GemmArgs& b, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(a, "gemm2 pair")) return rc;
+    if (int rc = gemm_rowmap_refused(b, "gemm2 pair")) return rc;
     D4_REQUIRE(gemm2_pair_applicable(a, b) && gemm2_config_valid(c, a) && gemm2_config_valid(c, b), "gemm2 pair: configuration %d is not valid for these calls", c);
     switch (c) {
         case V2_64x64: return launch2_pair<2, 2, 2, 2, 3, 32>(a, b, stream, ea, eb);

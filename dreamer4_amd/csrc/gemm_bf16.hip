@@ -363,6 +363,7 @@ bool gemm_bf16_config_valid(int c, const GemmArgs& p) { return gemm_bf16_applica
 
 // tile choice by rule
 int gemm_bf16(const GemmArgs& p, hipStream_t stream) {
+    if (int rc = gemm_rowmap_refused(p, "gemm_bf16")) return rc;
     D4_REQUIRE(gemm_bf16_applicable(p), "gemm_bf16: call not supported (M=%d N=%d K=%d flags=%d)", p.M, p.N, p.K, p.flags);
     const bool swiglu = (p.flags & GEMM_SWIGLU) != 0;
     const int nb = p.batch > 0 ? p.batch : 1;

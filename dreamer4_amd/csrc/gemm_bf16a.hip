@@ -409,6 +409,7 @@ static int launch_va(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEv
 }
 
 int gemm_bf16a_launch(int c, const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(p, "gemm_bf16a")) return rc;
     D4_REQUIRE(gemm_bf16a_config_valid(c, p), "gemm_bf16a: configuration %d is not valid for this call", c);
     switch (c) {
         case VA_128x128: return launch_va<4, 2, 2, 4, 3>(p, stream, ea, eb);
@@ -465,6 +466,8 @@ bool gemm_bf16a_pair_applicable(const GemmArgs& a, const GemmArgs& b) {
     return c == VA_128x64 || c == VA_64x64;
 }
 int gemm_bf16a_pair_launch(const GemmArgs& a, const GemmArgs& b, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(a, "pair launch")) return rc;
+    if (int rc = gemm_rowmap_refused(b, "pair launch")) return rc;
     D4_REQUIRE(gemm_bf16a_pair_applicable(a, b), "gemm_bf16a_pair: call not supported");
     const GemmArgs& big = (double)a.M * a.N >= (double)b.M * b.N ? a : b;
     if (gemm_bf16a_rule(big) == VA_128x64) return launch_va_pair<4, 2, 2, 2, 3>(a, b, stream, ea, eb);

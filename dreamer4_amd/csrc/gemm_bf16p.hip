@@ -474,6 +474,7 @@ __global__ __launch_bounds__(512) void gemm_bf16p_kernel(GemmArgs p) {
 #undef D4P_SLOT
 
 int gemm_bf16p_launch(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(p, "gemm_bf16p")) return rc;
     constexpr int BM = 256, BN = 256;
     const size_t lds = (size_t)8 * 64 * (256 + 16) + BM * sizeof(float);          // max(ring 8 x 16 KB, epilogue staging) + row scales
     const bool rms = (p.flags & GEMM_RMS_ROWSCALE) != 0;

@@ -488,6 +488,7 @@ static int launch_h2(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEv
 }
 
 int gemm_h2_launch(int c, const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(p, "gemm_h2")) return rc;
     D4_REQUIRE(gemm_h2_config_valid(c, p), "gemm_h2: configuration %d is not valid for this call", c);
     switch (c) {
         case H2_64x64: return launch_h2<64, 64, 2, 2, 3, 1, 3>(p, stream, ea, eb);

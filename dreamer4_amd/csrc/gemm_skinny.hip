@@ -188,6 +188,8 @@ bool gemm_skinny_pair_applicable(const GemmArgs& a, const GemmArgs& b) {
 }
 
 int gemm_skinny_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t stream) {
+    if (int rc = gemm_rowmap_refused(a, "pair launch")) return rc;
+    if (int rc = gemm_rowmap_refused(b, "pair launch")) return rc;
     int nw; bool u6;
     skinny_shape(a.K, nw, u6);
     const int nba = cdiv(a.N, SKN), nbb = cdiv(b.N, SKN);
@@ -203,6 +205,7 @@ int gemm_skinny_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t stream) {
 }
 
 int gemm_skinny(const GemmArgs& p, hipStream_t stream) {
+    if (int rc = gemm_rowmap_refused(p, "gemm_skinny")) return rc;
     const bool swiglu = (p.flags & GEMM_SWIGLU) != 0;
     int nw; bool u6;
     skinny_shape(p.K, nw, u6);

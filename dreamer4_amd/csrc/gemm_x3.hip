@@ -381,6 +381,7 @@ static int launch_x3(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEv
 }
 
 int gemm_x3_launch(int c, const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    if (int rc = gemm_rowmap_refused(p, "gemm_x3")) return rc;
     D4_REQUIRE(gemm_x3_config_valid(c, p), "gemm_x3: configuration %d is not valid for this call", c);
     switch (c) {
         case X3_64x64: return launch_x3<64, 64, 2, 2, 3, 1, 3>(p, stream, ea, eb);

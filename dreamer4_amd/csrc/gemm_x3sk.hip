@@ -51,7 +51,9 @@ __device__ __forceinline__ void split3(float a, __bf16& h1, __bf16& h2, __bf16& 
 
 // One work item on the calling workgroup: rows bm0 .. bm0 + 127, columns bn0 .. bn0 + 64 TNV - 1, all of K.
 // TNV = 2: a 128 x 128 tile (wave tile 32 x 64); TNV = 1: a half tile of 128 x 64 (wave tile 32 x 32).
-template <int TNV>
+// RMAP: the output rows go through GemmArgs' row map (rm_*: dense frames of rm_Sc rows into frames of rm_Sc + rm_nr rows around a gap) — a second instantiation
+// of the epilogue's store address only; the plain form keeps its code.
+template <int TNV, bool RMAP>
 __device__ __forceinline__ void sk_item(const SkArgs& s, const int bm0, const int bn0, __bf16* As, __bf16* Bs, float* rowscale_s) {
     const GemmArgs& p = s.p;
     const int kt0 = 0, kt1 = p.K / SK_BK;
@@ -265,6 +267,11 @@ __device__ __forceinline__ void sk_item(const SkArgs& s, const int bm0, const in
                 if (p.bias) v += p.bias[gn];
                 if (p.flags & GEMM_SILU) v = siluf(v);
                 if (p.R) v += p.R[(int64_t)gm * p.ldr + gn];
+                if constexpr (RMAP) {
+                    const int fr = gm / p.rm_Sc, t = gm - fr * p.rm_Sc;
+                    p.C[((int64_t)fr * (p.rm_Sc + p.rm_nr) + t + (t >= p.rm_lo ? p.rm_nr : 0)) * p.ldc + gn] = v;
+                    continue;
+                }
                 if (p.flags & GEMM_ACCUMULATE) v += p.C[(int64_t)gm * p.ldc + gn];
                 p.C[(int64_t)gm * p.ldc + gn] = v;
                 if (p.C2) {
@@ -279,7 +286,8 @@ __device__ __forceinline__ void sk_item(const SkArgs& s, const int bm0, const in
     __syncthreads();                                   // rowscale_s / the LDS tiles are rewritten by the next item
 }
 
-__global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_kernel(SkArgs s) {
+template <bool RMAP>
+__device__ __forceinline__ void sk_walk(const SkArgs s) {
     const GemmArgs& p = s.p;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     __bf16* As = reinterpret_cast<__bf16*>(smem_raw);                 // [2][3][BM][LD]
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_kernel(SkArgs s) {
         // whole rounds, then the remaining tiles as 2 R half tiles: item h = (remaining tile h / 2, column half h & 1) on workgroup h % P
         for (int i = 0; i < s.F; ++i) {
             tile_of(b + i * s.P, tm, tn);
-            sk_item<2>(s, tm * SK_BM, tn * SK_BN, As, Bs, rowscale_s);
+            sk_item<2, RMAP>(s, tm * SK_BM, tn * SK_BN, As, Bs, rowscale_s);
         }
         // remaining tile j's two halves go to workgroups j and R8 + j (R8 = R rounded up to 8): both sit on XCD j % 8, the XCD whose L2 the banded
         // walk gave tile F P + j's neighbours to (with h / 2 on workgroup h the halves landed on other XCDs: +18 MB of fabric reads per launch)
@@ -315,23 +323,27 @@ __global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_kernel(SkArgs s) {
             if (j >= 0 && j < s.R && (b < s.R || b >= R8)) {
                 tile_of(s.F * s.P + j, tm, tn);
                 const int bn0 = tn * SK_BN + half * 64;
-                if (bn0 < p.N) sk_item<1>(s, tm * SK_BM, bn0, As, Bs, rowscale_s);
+                if (bn0 < p.N) sk_item<1, RMAP>(s, tm * SK_BM, bn0, As, Bs, rowscale_s);
             }
             return;
         }
         for (int h = b; h < 2 * s.R; h += s.P) {
             tile_of(s.F * s.P + h / 2, tm, tn);
             const int bn0 = tn * SK_BN + (h & 1) * 64;
-            if (bn0 < p.N) sk_item<1>(s, tm * SK_BM, bn0, As, Bs, rowscale_s);
+            if (bn0 < p.N) sk_item<1, RMAP>(s, tm * SK_BM, bn0, As, Bs, rowscale_s);
         }
         return;
     }
     // whole tiles only: F rounds, then the last partial round's R tiles on the first R workgroups
     for (int i = 0; i < s.F + (b < s.R ? 1 : 0); ++i) {
         tile_of(b + i * s.P, tm, tn);
-        sk_item<2>(s, tm * SK_BM, tn * SK_BN, As, Bs, rowscale_s);
+        sk_item<2, RMAP>(s, tm * SK_BM, tn * SK_BN, As, Bs, rowscale_s);
     }
 }
+
+__global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_kernel(SkArgs s) { sk_walk<false>(s); }
+// the same walk with the row-mapped store (GemmArgs::rm_Sc > 0; plain epilogue only: the launcher checks)
+__global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_rowmap_kernel(SkArgs s) { sk_walk<true>(s); }
 
 static std::atomic<int> g_sk_cus[64];            // per device id (a process may drive several devices); 0 = not queried yet
 
@@ -381,14 +393,17 @@ int gemm_x3sk_launch(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEv
     a.half = gemm_x3sk_half_plan(p, &a.F, &a.R, &a.P) ? 1 : 0;
     const int T = a.F * a.P + a.R;
     if (T < a.P && !a.half) a.P = T;                   // a small call: one tile per workgroup, nothing persistent
-    static DeviceOnce attr_set;
-    if (attr_set.need()) {
-        D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3sk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS));
-        attr_set.done();
+    D4_REQUIRE(gemm_rowmap_ok(p), "gemm_x3sk: bad output row map (Sc=%d lo=%d nr=%d) or an epilogue it does not cover (flags=%d)", p.rm_Sc, p.rm_lo, p.rm_nr, p.flags);
+    const bool rmap = p.rm_Sc > 0;
+    auto k = rmap ? gemm_x3sk_rowmap_kernel : gemm_x3sk_kernel;
+    static DeviceOnce attr_set[2];
+    if (attr_set[rmap].need()) {
+        D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS));
+        attr_set[rmap].done();
     }
     const dim3 grid(a.P), block(SK_NT);
-    if (ea) hipExtLaunchKernelGGL(gemm_x3sk_kernel, grid, block, (uint32_t)SK_LDS, stream, ea, eb, 0, a);
-    else hipLaunchKernelGGL(gemm_x3sk_kernel, grid, block, SK_LDS, stream, a);
+    if (ea) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)SK_LDS, stream, ea, eb, 0, a);
+    else hipLaunchKernelGGL(k, grid, block, SK_LDS, stream, a);
     D4_LAUNCH_CHECK();
     return 0;
 }

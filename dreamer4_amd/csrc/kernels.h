@@ -35,8 +35,11 @@ struct GemmArgs {
                                        // bf16-activation kernel (gemm_bf16a.hip) and never touches the fp32 A
     uint16_t* Cb = nullptr;            // optional bf16 copy of the output ([M][ldc]; SiLU-GLU: [M][N/2] at ldc), for the next GEMM's Ab
     uint16_t* C2b = nullptr;           // ... and of the row-compacted second output ([rows][ldc2])
+    // output row map, first half (see rm_nr below); the four 16-bit fields sit in the struct's two alignment gaps, so GemmArgs — a kernel argument of every
+    // GEMM kernel — keeps its size and field offsets
     int group_m = 0;                   // > 0 (gemm_bf16a.hip): tiles are walked in groups of `group_m` row panels, column-major inside a group, so the
                                        // ~32 tiles an XCD runs at a time share few operand panels (its 4 MB L2 then holds them); 0: row-major
+    uint16_t rm_Sc = 0, rm_lo = 0;     // (row map: dense rows per frame; first dense row that lies behind the gap)
     int64_t wplane = 0;                // > 0: Wb holds THREE bf16 planes (W = W1 + W2 + W3, plane stride in elements) and the call runs as
                                        // an fp32 GEMM on the bf16 matrix cores (split operands, six products: gemm_x3.hip)
     const float* wscale = nullptr;     // set (with wplane > 0): Wb holds TWO fp16 planes of W scaled row by row (hi, lo 2^11) and wscale[n] = the exact
@@ -45,7 +48,16 @@ struct GemmArgs {
     const int* aexp = nullptr;         // optional (gemm_h2.hip): scale exponent of every A row ([batch][M]) from a producer that knows it; null: the kernel finds it
     int rule_M = 0;                    // > 0: the row count the dispatcher's FAMILY rules see instead of M (few-row kernel, k-split form) — a caller that runs
                                        // a subset of a product's rows keeps the family, and so the bits, of the whole product (engine.hip: the rollout's clean evaluation)
+    // output row map (rm_Sc > 0): A holds frames of rm_Sc dense rows, C frames of rm_Sc + rm_nr rows with a gap of rm_nr rows starting at row rm_lo of a
+    // frame — dense row r goes to row (r / rm_Sc) * (rm_Sc + rm_nr) + (r % rm_Sc) + ((r % rm_Sc) >= rm_lo ? rm_nr : 0); the gap rows are not written.  Plain
+    // epilogue only (bias, row scale; no R / C2 / accumulate / SiLU-GLU / bf16 copy).  Honoured by gemm_x3sk.hip and gemm2.hip (single and batched launch);
+    // every other launcher refuses such a call (gemm_rowmap_refused)
+    uint16_t rm_nr = 0, rm_spare = 0;
 };
+static_assert(sizeof(GemmArgs) == 232, "GemmArgs is a kernel argument: the row map lives in its alignment gaps");
+bool gemm_rowmap_ok(const GemmArgs& p);                   // gemm.hip: no map, or a well-formed one on a call whose epilogue the mapped kernels implement
+int gemm_rowmap_refused(const GemmArgs& p, const char* who);   // gemm.hip: 0 when p carries no row map, else the error "who: ... does not implement the output row map"
+bool gemm_rule_takes_x3sk(const GemmArgs& p);             // gemm.hip: would gemm() run exactly this call on the persistent split-operand kernel by its rules?
 
 int gemm(const GemmArgs& p, hipStream_t stream);
 bool gemm_rule_takes_v2(const GemmArgs& p);               // gemm.hip: would gemm() run exactly this call on the LDS-DMA f32 family (gemm2.hip) by its rules?
@@ -202,6 +214,7 @@ bool lqap_out_applicable(int heads, int dh, int n, int ns, int dl);
 int lqap_out(const float* kv, int ldkv, const float* q, const float* gate, const float* k_gamma, const float* w_out, int ldw, float* pred, int ldp, int frames,
              int heads, int n, int ns, int dl, hipStream_t s);
 extern int g_lqap_in_fused, g_lqap_out_fused, g_last_layer_compact_q;      // engine.hip: test hooks, default 1 (d4_debug_switch)
+extern int g_layer0_const_rows, g_pool_const_keys;                         // engine.hip: the constant register rows, test hooks, default 1
 
 // ------------------------------------------------------------------------------------ per-frame fused block tails (frame_fused.hip)
 // W [N][K] -> Wt [N / 16][K / 4][16][4]: the weight image the per-frame kernels stream (a 16-row tile is one contiguous run)
@@ -298,6 +311,7 @@ struct AssembleArgs {
     float* compact;                // optional [B*Tq][ns (+ 1)][D]: spatial (+ agent) rows only
     int has_agent;                 // 0: the frame is packed without its trailing agent token (S = tokens actually present)
     int compact_spatial = 1;       // 0: the compact copy keeps the agent row alone ([B*Tq][1][D]; the rollout's clean evaluation)
+    float* dense = nullptr;        // optional [B*Tq][S - nr][D]: the frame's rows without the register block (rows [1 + ns, 1 + ns + nr)), in frame order
 };
 int assemble_tokens(const AssembleArgs& p, hipStream_t s);
 

@@ -296,6 +296,9 @@ int d4_frame_fused_set(int mode);
  * "rollout_batched_heads" (d4_rollout): 1 (default) the value and reward heads run once after the frame loop over all batch * F agent rows
  * (values / rewards: fp32 rounding apart from the per-frame path at F > 1, bit-identical with the same launches at F == 1; everything else
  * bit-identical); 0 after every frame.
+ * "layer0_const_rows" / "pool_const_keys" (fp32 dynamics engine): 1 (default) the register rows of a frame, which are a parameter, keep their share
+ * of layer 0's fused projection / of the in-loop pools' keys of slab 0 from d4_engine_prepare, and an evaluation projects the other rows only
+ * (bit-identical); 0 the full launches.
  * "launch_count" (not a switch): returns the number of kernel launches the library has enqueued since the counter was last set, and sets it to
  * `value` (launches inside a replayed hipGraph are not seen). */
 int d4_debug_switch(const char* name, int value);
@@ -614,6 +617,10 @@ int d4_gemm_family_configs(int family);
 /* Runs `d` on exactly the family / configuration named.  A call the family's `*_applicable` / `*_config_valid` refuses fails with an error that
  * starts "d4_gemm_run: call not supported" and names the reason; nothing falls through to another family. */
 int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream);
+/* The same with an output row map (csrc/kernels.h: GemmArgs::rm_*): A holds frames of rm_Sc dense rows, C frames of rm_S = rm_Sc + rm_nr rows; dense row r
+ * goes to row (r / rm_Sc) * rm_S + (r % rm_Sc) + ((r % rm_Sc) >= rm_lo ? rm_nr : 0) and the gap rows are not written.  D4_GEMM_X3SK and D4_GEMM_V2 (single
+ * and batched) implement it for the plain epilogue (bias, row scale); every other family, and any other epilogue, fails with an error. */
+int d4_gemm_run_rowmap(const d4_gemm_desc* d, int family, int config, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream);
 #define D4_PAIR_SKINNY 0        /* gemm_skinny_pair */
 #define D4_PAIR_BF16A 1         /* gemm_bf16a_pair_launch */
 #define D4_PAIR_V2 2            /* gemm2_pair_launch(config) */
