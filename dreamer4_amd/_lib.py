@@ -113,6 +113,18 @@ class LearnIO(C.Structure):
         ('allreduce_sum', ALLREDUCE_FN), ('allreduce_user', C.c_void_p),
         ('losses', C.c_void_p), ('returns', C.c_void_p),
         ('d_agent_embed_policy', C.c_void_p), ('d_agent_embed_value', C.c_void_p),
+        ('ema_returns', C.c_void_p), ('reward_ema_decay', C.c_double), ('q_lo', C.c_float), ('q_hi', C.c_float),
+        ('clip_values', C.c_int32), ('value_clip', C.c_float),
+    ]
+
+
+class ValueLossDesc(C.Structure):
+    """d4_value_loss_desc (include/d4hip.h)."""
+    _fields_ = [
+        ('logits', C.c_void_p), ('ld', C.c_int32), ('returns', C.c_void_p), ('old_values', C.c_void_p), ('mask', C.c_void_p), ('support', C.c_void_p),
+        ('rows', C.c_int32), ('bins', C.c_int32), ('vmin', C.c_float), ('vmax', C.c_float), ('sigma', C.c_float), ('eps', C.c_float),
+        ('two_hot', C.c_int32), ('clip_values', C.c_int32), ('value_clip', C.c_float),
+        ('loss', C.c_void_p), ('row_loss', C.c_void_p), ('dlogits', C.c_void_p), ('scratch', C.c_void_p),
     ]
 
 
@@ -257,6 +269,8 @@ SYMBOLS = {
     'd4_gae': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P]),
     'd4_gae_adv': (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P]),
     'd4_policy_loss': (_I, [C.POINTER(PolicyLossDesc), _P]),
+    'd4_return_stats': (_I, [_P, _P, _P, _L, _P, C.c_double, _F, _F, _P, _P, _P]),
+    'd4_value_loss': (_I, [C.POINTER(ValueLossDesc), _P]),
     'd4_categorical_sample_logp': (_I, [_P, _I, _P, _I, _P, _I, _I, _F, _P, _P, _P]),
     'd4_hl_gauss_ce': (_I, [_P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
     'd4_flow_noised_patches': (_I, [_P] * 4 + [_I] * 6 + [_P]),

@@ -192,6 +192,7 @@ struct d4_engine {
     float *l_tmp[4];
     float *l_cparams, *l_dcparams, *l_cu_g;
     float *l_logits, *l_dlogits, *l_vbins, *l_dvbins, *l_returns, *l_adv, *l_scal, *l_mask, *l_rows, *l_dpe;
+    float* l_oldv;           // [LR] old values, 0 past `len` (return statistics, value clipping)
 };
 
 namespace d4 {

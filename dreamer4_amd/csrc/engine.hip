@@ -268,6 +268,7 @@ int engine_layout(d4_engine* e, bool assign) {
         e->l_rows = fl(4 * R);
         e->l_dpe = fl(R * 4 * (size_t)D);
         e->l_scal = fl(64);
+        e->l_oldv = fl(R);
     }
     e->ws_need = off + 256;
     return 0;

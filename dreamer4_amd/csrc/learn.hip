@@ -53,6 +53,14 @@ __global__ void gae_kernel(const float* rewards, const float* values, const int6
     }
 }
 
+// old values with 0 past `len`, as gae_kernel reads them (D4:5950): the input of the return statistics and of the value clipping
+__global__ void masked_old_values_kernel(const float* values, const int64_t* lens, int B, int T, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * T) return;
+    const int b = i / T, t = i - b * T;
+    out[i] = (!lens || t < (int)lens[b]) ? values[i] : 0.f;
+}
+
 // ------------------------------------------------------------------------------------ deterministic reductions
 // out[slot] = sum_i f(a[i], b[i]) with one 1024-thread block (fixed tree order).
 enum { RED_PROD = 0, RED_SQDIFF_MASKED = 1, RED_SUM = 2 };
@@ -361,6 +369,219 @@ __global__ __launch_bounds__(256) void value_loss_kernel(const float* vbins, int
     if (lane == 0) row_loss[r] = loss * mk;
 }
 
+// ------------------------------------------------------------------------------------ value loss with PPO value clipping, fwd + bwd
+// D4:6283-6291 on top of value_loss_kernel (same targets, same CE, one wave per row):
+//   values  = sum_c softmax(v)_c * centre_c            (HL-Gauss: centres of the bin edges; TWO_HOT: the bin values)
+//   clipped = old + clamp(values - old, -clip, clip);  q = encoder(clipped), the encoder and range clamp of the returns
+//   loss    = max(CE, -sum_c p_c log max(q_c, 1e-20))
+// Gradient: where the clipped branch wins, d loss / d clipped goes through q (HL-Gauss: the erf differences and the normaliser; two-hot: the two
+// weights) and, where neither the +-clip clamp nor the range clamp is active (autograd's clamp: inclusive ends), on through values into the
+// logits: d values / d v_j = softmax_j (centre_j - values).  A q_c below 1e-20 passes nothing (clamp(min)).  A tie of the two losses halves both.
+template <bool TWO_HOT>
+__global__ __launch_bounds__(256) void value_loss_clip_kernel(const float* vbins, int ld, const float* returns, const float* old_values, const float* mask,
+                                                              const float* scal, const float* support, int R, int bins,
+                                                              float sigma_sqrt2, float hl_eps, float vmin, float vmax, float clip,
+                                                              float* dv, float* row_loss) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const int lane = threadIdx.x & 63;
+    const float count = fmaxf(scal[1], 1.f);
+    const float mk = mask[r];
+    const float* v = vbins + (int64_t)r * ld;
+    const float rlo = TWO_HOT ? support[0] : vmin, rhi = TWO_HOT ? support[bins - 1] : vmax;
+    // encoder of a scalar x already clamped into the range: two-hot indices and left weight, or the HL-Gauss normaliser
+    auto two_hot_of = [&](float x, int& li, int& ri, float& wl) {
+        int lo = 0, hi = bins;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (support[mid] < x) lo = mid + 1; else hi = mid; }
+        li = lo - 1 > 0 ? lo - 1 : 0;
+        ri = li + 1 < bins - 1 ? li + 1 : bins - 1;
+        wl = (support[ri] - x) / (support[ri] - support[li]);
+    };
+    const float ret = fminf(fmaxf(returns[r], rlo), rhi);
+    int li = 0, ri = 0;
+    float wl = 0.f;
+    if (TWO_HOT) two_hot_of(ret, li, ri, wl);
+    const float z = TWO_HOT ? 1.f : erff((support[bins] - ret) / sigma_sqrt2) - erff((support[0] - ret) / sigma_sqrt2);
+    const float zc = fmaxf(z, hl_eps);
+    auto target = [&](int c) -> float {
+        if (TWO_HOT) return c == ri ? 1.f - wl : (c == li ? wl : 0.f);
+        return (erff((support[c + 1] - ret) / sigma_sqrt2) - erff((support[c] - ret) / sigma_sqrt2)) / zc;
+    };
+    auto centre = [&](int c) -> float { return TWO_HOT ? support[c] : (support[c] + support[c + 1]) / 2.f; };
+    float mx = -FLT_MAX;
+    for (int c = lane; c < bins; c += 64) mx = fmaxf(mx, v[c]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int c = lane; c < bins; c += 64) se += expf(v[c] - mx);
+    const float lse = mx + logf(wave_sum(se));
+    float loss1 = 0.f, psum = 0.f, values = 0.f;
+    for (int c = lane; c < bins; c += 64) {
+        const float pr = target(c);
+        loss1 -= pr * (v[c] - lse);
+        psum += pr;
+        values += expf(v[c] - lse) * centre(c);
+    }
+    loss1 = wave_sum(loss1);
+    psum = wave_sum(psum);
+    values = wave_sum(values);
+    // the clipped prediction and its encoding
+    const float old = old_values[r];
+    const float diff = values - old;
+    const float clipped = old + fminf(fmaxf(diff, -clip), clip);
+    const bool through = diff >= -clip && diff <= clip && clipped >= rlo && clipped <= rhi;       // d x / d values = 1
+    const float x = fminf(fmaxf(clipped, rlo), rhi);
+    int li2 = 0, ri2 = 0;
+    float wl2 = 0.f;
+    if (TWO_HOT) two_hot_of(x, li2, ri2, wl2);
+    const float z2 = TWO_HOT ? 1.f : erff((support[bins] - x) / sigma_sqrt2) - erff((support[0] - x) / sigma_sqrt2);
+    const float zc2 = fmaxf(z2, hl_eps);
+    // d erf((s - x) / a) / dx = -k exp(-((s - x) / a)^2),  k = 2 / (a sqrt(pi))
+    const float k = 1.1283791670955126f / sigma_sqrt2;
+    auto gauss = [&](int c) -> float { const float u = (support[c] - x) / sigma_sqrt2; return expf(-u * u); };
+    const float dz2 = (TWO_HOT || z2 < hl_eps) ? 0.f : -k * (gauss(bins) - gauss(0));
+    float loss2 = 0.f, dl2 = 0.f;                                                                 // loss2 and d loss2 / d x
+    for (int c = lane; c < bins; c += 64) {
+        const float pr = target(c);
+        float q, dq;
+        if (TWO_HOT) {
+            const float inv = 1.f / (support[ri2] - support[li2]);
+            q = c == ri2 ? 1.f - wl2 : (c == li2 ? wl2 : 0.f);
+            dq = c == ri2 ? inv : (c == li2 ? -inv : 0.f);
+        } else {
+            const float num = erff((support[c + 1] - x) / sigma_sqrt2) - erff((support[c] - x) / sigma_sqrt2);
+            q = num / zc2;
+            dq = -k * (gauss(c + 1) - gauss(c)) / zc2 - num * dz2 / (zc2 * zc2);
+        }
+        loss2 -= pr * logf(fmaxf(q, 1e-20f));
+        if (q >= 1e-20f) dl2 -= pr * dq / q;
+    }
+    loss2 = wave_sum(loss2);
+    dl2 = wave_sum(dl2);
+    const float w2 = loss2 > loss1 ? 1.f : (loss2 == loss1 ? 0.5f : 0.f), w1 = 1.f - w2;
+    const float g2 = through ? w2 * dl2 : 0.f;                                                    // d loss / d values
+    const float scale = mk / count;
+    for (int c = lane; c < bins; c += 64) {
+        const float pr = target(c);
+        const float pc = expf(v[c] - lse);
+        dv[(int64_t)r * ld + c] = (w1 * (pc * psum - pr) + g2 * pc * (centre(c) - values)) * scale;
+    }
+    for (int c = bins + lane; c < ld; c += 64) dv[(int64_t)r * ld + c] = 0.f;
+    if (lane == 0) row_loss[r] = fmaxf(loss1, loss2) * mk;
+}
+
+// ------------------------------------------------------------------------------------ return statistics (keep_reward_ema_stats)
+// D4:5985-6015 in ONE workgroup, nothing read back by the host.  The quantiles are exact order statistics of the kept returns: each float is
+// mapped to an unsigned key of the same order (sign bit flipped for positives, all bits for negatives) and the element of rank k is found
+// digit by digit, 8 bits per pass: a 256-bin histogram (LDS integer atomics) of the keys that share the digits found so far, a scan, the bin that
+// holds rank k.  The four ranks (floor and ceil of both positions) go through the four passes together, one histogram each: 1024 threads = 4 x
+// 256 bins for the scan.  Counts are integers and the float sums have a fixed tree order: equal inputs give equal bits.
+__device__ __forceinline__ uint32_t order_key(float x) {
+    const uint32_t u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float order_key_inv(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ float block_sum_1024(float s, float* sh) {
+    __syncthreads();
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__global__ __launch_bounds__(1024) void return_stats_kernel(const float* returns, const float* old_values, const float* mask, int64_t n, float* ema,
+                                                            float ema_w, float q_lo, float q_hi, float* adv, float* stats) {
+    __shared__ uint32_t hist[4][256];
+    __shared__ uint32_t scan[2][1024];
+    __shared__ float shf[1024];
+    __shared__ uint32_t s_prefix[4], s_rank[4];
+    __shared__ uint32_t s_count;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    uint32_t cnt = 0;
+    for (int64_t i = tid; i < n; i += 1024) cnt += (!mask || mask[i] != 0.f) ? 1u : 0u;
+    atomicAdd(&s_count, cnt);
+    __syncthreads();
+    const uint32_t N = s_count;
+    float mean_e = ema[0], var_e = ema[1];
+    if (N > 0) {
+        // positions q (N - 1) in double: a float position loses the fraction beyond 2^24 / N
+        const double pos_lo = (double)q_lo * (double)(N - 1), pos_hi = (double)q_hi * (double)(N - 1);
+        const double fl_lo = floor(pos_lo), fl_hi = floor(pos_hi);
+        if (tid == 0) {
+            s_rank[0] = (uint32_t)fl_lo; s_rank[1] = (uint32_t)ceil(pos_lo); s_rank[2] = (uint32_t)fl_hi; s_rank[3] = (uint32_t)ceil(pos_hi);
+            for (int j = 0; j < 4; ++j) s_prefix[j] = 0;
+        }
+        for (int pass = 0; pass < 4; ++pass) {
+            const int shift = 24 - 8 * pass;
+            const uint32_t pmask = pass == 0 ? 0u : 0xffffffffu << (shift + 8);
+            (&hist[0][0])[tid] = 0;
+            __syncthreads();
+            const uint32_t p0 = s_prefix[0], p1 = s_prefix[1], p2 = s_prefix[2], p3 = s_prefix[3];
+            for (int64_t i = tid; i < n; i += 1024) {
+                if (mask && mask[i] == 0.f) continue;
+                const uint32_t key = order_key(returns[i]), hi = key & pmask, d = (key >> shift) & 255u;
+                if (hi == p0) atomicAdd(&hist[0][d], 1u);
+                if (hi == p1) atomicAdd(&hist[1][d], 1u);
+                if (hi == p2) atomicAdd(&hist[2][d], 1u);
+                if (hi == p3) atomicAdd(&hist[3][d], 1u);
+            }
+            __syncthreads();
+            // inclusive scan of each histogram: thread = (rank j, bin b)
+            const int b = tid & 255, j = tid >> 8;
+            const uint32_t own = (&hist[0][0])[tid];
+            int cur = 0;
+            scan[0][tid] = own;
+            __syncthreads();
+            for (int w = 1; w < 256; w <<= 1) {
+                const uint32_t t = scan[cur][tid] + (b >= w ? scan[cur][tid - w] : 0u);
+                scan[cur ^ 1][tid] = t;
+                cur ^= 1;
+                __syncthreads();
+            }
+            const uint32_t incl = scan[cur][tid], excl = incl - own, kj = s_rank[j];
+            __syncthreads();
+            if (kj >= excl && kj < incl) { s_rank[j] = kj - excl; s_prefix[j] |= (uint32_t)b << shift; }
+            __syncthreads();
+        }
+        const float x0 = order_key_inv(s_prefix[0]), x1 = order_key_inv(s_prefix[1]), x2 = order_key_inv(s_prefix[2]), x3 = order_key_inv(s_prefix[3]);
+        // torch.lerp(a, b, w): a + w (b - a) below one half, b - (b - a)(1 - w) from there
+        const float w_lo = (float)(pos_lo - fl_lo), w_hi = (float)(pos_hi - fl_hi);
+        const float lo = w_lo < 0.5f ? x0 + w_lo * (x1 - x0) : x1 - (x1 - x0) * (1.f - w_lo);
+        const float hi = w_hi < 0.5f ? x2 + w_hi * (x3 - x2) : x3 - (x3 - x2) * (1.f - w_hi);
+        float s = 0.f;
+        for (int64_t i = tid; i < n; i += 1024)
+            if (!mask || mask[i] != 0.f) s += fminf(fmaxf(returns[i], lo), hi);
+        const float mean = block_sum_1024(s, shf) / (float)N;
+        s = 0.f;
+        for (int64_t i = tid; i < n; i += 1024)
+            if (!mask || mask[i] != 0.f) { const float d = fminf(fmaxf(returns[i], lo), hi) - mean; s += d * d; }
+        const float var = block_sum_1024(s, shf) / (float)N;
+        mean_e = mean_e + ema_w * (mean - mean_e);                       // lerp_ (weight below one half)
+        var_e = var_e + ema_w * (var - var_e);
+        __syncthreads();                                                 // every thread has read ema[] before it is written
+        if (tid == 0) { ema[0] = mean_e; ema[1] = var_e; stats[0] = lo; stats[1] = hi; stats[2] = mean; stats[3] = var; }
+    } else if (tid == 0) {
+        stats[0] = stats[1] = stats[2] = stats[3] = 0.f;
+    }
+    const float sd = sqrtf(fmaxf(var_e, 1e-5f));
+    for (int64_t i = tid; i < n; i += 1024) adv[i] = (returns[i] - mean_e) / sd - (old_values[i] - mean_e) / sd;
+}
+
+int return_stats(const float* returns, const float* old_values, const float* mask, int64_t n, float* ema, double reward_ema_decay, float q_lo, float q_hi,
+                 float* adv, float* stats, hipStream_t s) {
+    float w = (float)(1. - reward_ema_decay);
+    // torch's lerp takes its other branch from one half on; the kernel has the lower one only (a decay above one half, as any EMA has)
+    D4_REQUIRE(w < 0.5f, "return statistics: reward_ema_decay must exceed 0.5");
+    hipLaunchKernelGGL(return_stats_kernel, dim3(1), dim3(1024), 0, s, returns, old_values, mask, n, ema, w, q_lo, q_hi, adv, stats);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void masked_mean_final_kernel(const float* scal, float* out) { out[0] = scal[7] / fmaxf(scal[1], 1.f); }
 
 __global__ void finalize_losses_kernel(const float* scal, float* losses, int objective, float ent_w, float kl_w) {
@@ -592,6 +813,12 @@ int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s) {
     const int D = e->D, A = e->A, Apad = (A + 3) / 4 * 4 + (A == 0 ? 4 : 0), na = e->na, nc = e->nc, Cpad = (2 * nc + 3) / 4 * 4 + (nc == 0 ? 4 : 0);
     int rc;
     float* scal = e->l_scal;
+    const bool need_vold = io->ema_returns || io->clip_values;
+    D4_REQUIRE(!(io->ema_returns && io->allreduce_sum), "learn: keep_reward_ema_stats is single-process only (the return quantiles are not reduced over ranks)  [D4:5999]");
+    D4_REQUIRE(!io->ema_returns || (io->q_lo >= 0.f && io->q_lo <= io->q_hi && io->q_hi <= 1.f && io->reward_ema_decay > 0.5 && io->reward_ema_decay <= 1.),
+               "learn: 0 <= q_lo <= q_hi <= 1 and 0.5 < reward_ema_decay <= 1");
+    D4_REQUIRE(!io->clip_values || io->value_clip >= 0.f, "learn: value_clip >= 0");
+    D4_REQUIRE(!need_vold || e->l_oldv, "learn: no workspace for the old values");
     D4_HIP(hipMemsetAsync(scal, 0, 64 * sizeof(float), s));
 
     // ---- returns, advantages, masks
@@ -600,7 +827,14 @@ int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s) {
     hipLaunchKernelGGL(gae_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s, io->rewards, io->old_values, io->lens, io->is_truncated,
                        io->terminals, c.gae_discount_factor, c.gae_lambda, B, T, e->l_returns, row_a, mask_keep);
     D4_LAUNCH_CHECK();
+    if (need_vold) {      // the old values as the reference's later steps see them: 0 past `len` (D4:5950); launched with an option on only
+        hipLaunchKernelGGL(masked_old_values_kernel, dim3(cdiv(R, 256)), dim3(256), 0, s, io->old_values, io->lens, B, T, e->l_oldv);
+        D4_LAUNCH_CHECK();
+    }
     if (io->returns) D4_HIP(hipMemcpyAsync(io->returns, e->l_returns, sizeof(float) * R, hipMemcpyDeviceToDevice, s));
+    // keep_reward_ema_stats: the EMA pair is updated on the stream and the advantage is formed from the normalised returns and old values
+    // (D4:5985-6015); scal[40..43] = lo, hi, mean, var
+    if (io->ema_returns && (rc = return_stats(e->l_returns, e->l_oldv, mask_keep, R, io->ema_returns, io->reward_ema_decay, io->q_lo, io->q_hi, row_a, scal + 40, s))) return rc;
 
     const int normalize = io->normalize_advantages < 0 ? (io->objective != 2) : io->normalize_advantages;
 
@@ -644,7 +878,14 @@ int learn(d4_engine* e, const d4_learn_io* io, hipStream_t s) {
     if ((rc = mlp_forward(e, e->value, io->agent_embed, D, R, e->l_vbins, vld, save_v, s))) return rc;
     {
         const float sigma = c.hl_gauss_sigma_to_bin_ratio * (c.value_max - c.value_min) / (float)c.value_num_bins;
-        if (c.reward_encoder_type == 1)
+        if (io->clip_values) {
+            if (c.reward_encoder_type == 1)
+                hipLaunchKernelGGL(value_loss_clip_kernel<true>, dim3(cdiv(R, 4)), dim3(256), 0, s, e->l_vbins, vld, e->l_returns, e->l_oldv, mask_keep, scal,
+                                   e->value_support, R, c.value_num_bins, sqrtf(2.f) * sigma, c.hl_gauss_eps, c.value_min, c.value_max, io->value_clip, e->l_dvbins, row_vl);
+            else
+                hipLaunchKernelGGL(value_loss_clip_kernel<false>, dim3(cdiv(R, 4)), dim3(256), 0, s, e->l_vbins, vld, e->l_returns, e->l_oldv, mask_keep, scal,
+                                   e->value_support, R, c.value_num_bins, sqrtf(2.f) * sigma, c.hl_gauss_eps, c.value_min, c.value_max, io->value_clip, e->l_dvbins, row_vl);
+        } else if (c.reward_encoder_type == 1)
             hipLaunchKernelGGL(value_loss_kernel<true>, dim3(cdiv(R, 4)), dim3(256), 0, s, e->l_vbins, vld, e->l_returns, mask_keep, scal,
                                e->value_support, R, c.value_num_bins, sqrtf(2.f) * sigma, c.hl_gauss_eps, c.value_min, c.value_max, e->l_dvbins, row_vl);
         else
@@ -776,6 +1017,51 @@ int d4_hl_gauss_ce(const float* logits, int ld, const float* targets, const floa
                            sqrtf(2.f) * sigma, eps, vmin, vmax, dlogits, row_loss);
     hipLaunchKernelGGL(d4::reduce1_kernel<d4::RED_SUM>, dim3(1), dim3(1024), 0, s, row_loss, (const float*)nullptr, scal, (int64_t)rows, scal + 7);
     hipLaunchKernelGGL(d4::masked_mean_final_kernel, dim3(1), dim3(1), 0, s, scal, loss);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+
+// Stateless form of the return statistics (D4:5985-6015): the kernel d4_learn launches when io->ema_returns is given.
+int d4_return_stats(const float* returns, const float* old_values, const float* mask, int64_t n, float* ema, double reward_ema_decay, float q_lo,
+                    float q_hi, float* adv, float* stats, void* stream) {
+    D4_REQUIRE(returns && old_values && ema && adv && stats, "d4_return_stats: null argument");
+    D4_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "d4_return_stats: 1 <= n < 2^31");
+    D4_REQUIRE(q_lo >= 0.f && q_lo <= q_hi && q_hi <= 1.f, "d4_return_stats: 0 <= q_lo <= q_hi <= 1");
+    D4_REQUIRE(reward_ema_decay > 0.5 && reward_ema_decay <= 1., "d4_return_stats: 0.5 < reward_ema_decay <= 1");
+    return d4::return_stats(returns, old_values, mask, n, ema, reward_ema_decay, q_lo, q_hi, adv, stats, static_cast<hipStream_t>(stream));
+}
+
+// Stateless form of the value branch's loss with the clipping option (D4:6254-6295).  clip_values = 0 launches what d4_hl_gauss_ce
+// launches, on the caller's row_loss.
+int d4_value_loss(const d4_value_loss_desc* d, void* stream) {
+    D4_REQUIRE(d, "d4_value_loss: null argument");
+    D4_REQUIRE(d->logits && d->returns && d->support && d->loss && d->row_loss && d->dlogits && d->scratch, "d4_value_loss: null argument");
+    D4_REQUIRE(d->rows >= 1 && d->bins >= 1 && d->ld >= d->bins, "d4_value_loss: rows >= 1, bins >= 1, ld >= bins");
+    D4_REQUIRE(!d->clip_values || (d->old_values && d->value_clip >= 0.f && (!d->two_hot || d->bins >= 2)), "d4_value_loss: clipping needs old_values, value_clip >= 0 and, two-hot, two bins");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rows = d->rows, bins = d->bins;
+    float* scal = d->scratch;                  // [64]: [1] count, [7] summed row losses
+    float* ones = d->scratch + 64;             // [rows]
+    const float* mask = d->mask;
+    const float a = sqrtf(2.f) * d->sigma;
+    D4_HIP(hipMemsetAsync(scal, 0, 64 * sizeof(float), s));
+    if (!mask) { if (int rc = d4::fill_f32(ones, 1.f, rows, s)) return rc; mask = ones; }
+    hipLaunchKernelGGL(d4::reduce1_kernel<d4::RED_SUM>, dim3(1), dim3(1024), 0, s, mask, (const float*)nullptr, scal, (int64_t)rows, scal + 1);
+    if (d->clip_values) {
+        if (d->two_hot)
+            hipLaunchKernelGGL(d4::value_loss_clip_kernel<true>, dim3(d4::cdiv(rows, 4)), dim3(256), 0, s, d->logits, d->ld, d->returns, d->old_values, mask, scal, d->support,
+                               rows, bins, a, d->eps, d->vmin, d->vmax, d->value_clip, d->dlogits, d->row_loss);
+        else
+            hipLaunchKernelGGL(d4::value_loss_clip_kernel<false>, dim3(d4::cdiv(rows, 4)), dim3(256), 0, s, d->logits, d->ld, d->returns, d->old_values, mask, scal, d->support,
+                               rows, bins, a, d->eps, d->vmin, d->vmax, d->value_clip, d->dlogits, d->row_loss);
+    } else if (d->two_hot)
+        hipLaunchKernelGGL(d4::value_loss_kernel<true>, dim3(d4::cdiv(rows, 4)), dim3(256), 0, s, d->logits, d->ld, d->returns, mask, scal, d->support, rows, bins,
+                           a, d->eps, d->vmin, d->vmax, d->dlogits, d->row_loss);
+    else
+        hipLaunchKernelGGL(d4::value_loss_kernel<false>, dim3(d4::cdiv(rows, 4)), dim3(256), 0, s, d->logits, d->ld, d->returns, mask, scal, d->support, rows, bins,
+                           a, d->eps, d->vmin, d->vmax, d->dlogits, d->row_loss);
+    hipLaunchKernelGGL(d4::reduce1_kernel<d4::RED_SUM>, dim3(1), dim3(1024), 0, s, d->row_loss, (const float*)nullptr, scal, (int64_t)rows, scal + 7);
+    hipLaunchKernelGGL(d4::masked_mean_final_kernel, dim3(1), dim3(1), 0, s, scal, d->loss);
     D4_LAUNCH_CHECK();
     return 0;
 }

@@ -100,6 +100,10 @@ def run_learner(model, experience: Experience, objective='ppo', use_delight_gati
     if objective not in _OBJECTIVES:
         raise ValueError(f'unknown objective {objective}')
     dev = model.device
+    keep_ema = bool(getattr(model, 'keep_reward_ema_stats', False))
+    if keep_ema and (parallel.world_size(process_group) > 1 or parallel.force_collectives()):
+        # the reference's own "todo - handle distributed" (dreamer4.py:5999): quantiles of the global batch are not built
+        raise NotImplementedError('keep_reward_ema_stats=True is single-process only: the return quantiles are not reduced over a process group')
     exp = experience.to(dev)
     assert all(v is not None for v in (exp.log_probs, exp.actions, exp.values, exp.rewards, exp.step_size)), \
         'the generations need to contain the log probs, values, and rewards for policy optimization'
@@ -175,6 +179,15 @@ def run_learner(model, experience: Experience, objective='ppo', use_delight_gati
         d_pol, d_val = torch.zeros_like(agent), torch.zeros_like(agent)
         io.d_agent_embed_policy, io.d_agent_embed_value = P(d_pol), P(d_val)
 
+    ema = None
+    if keep_ema:
+        # the two scalar buffers as one device pair for the kernel; written back in place after the call, on the same stream
+        ema = torch.stack([model.ema_returns_mean.detach().float().reshape(()), model.ema_returns_var.detach().float().reshape(())]).to(dev).contiguous()
+        io.ema_returns, io.reward_ema_decay = P(ema), float(model.reward_ema_decay)
+        io.q_lo, io.q_hi = model.reward_quantile_filter
+    if getattr(model, 'clip_values', False):
+        io.clip_values, io.value_clip = 1, float(model.value_clip)
+
     cb, failure = None, []
     if stats == 'global' and (parallel.world_size(process_group) > 1 or parallel.force_collectives()):
         ws, base = model._ws, model._ws.data_ptr()
@@ -198,6 +211,10 @@ def run_learner(model, experience: Experience, objective='ppo', use_delight_gati
     if failure:
         raise failure[0]
     _lib.check(rc)
+    if ema is not None:
+        with torch.no_grad():
+            model.ema_returns_mean.copy_(ema[0])
+            model.ema_returns_var.copy_(ema[1])
     if want_embed_grads:
         return losses, returns, (d_pol, d_val)
     return losses, returns

@@ -123,7 +123,7 @@ _UNSUPPORTED_DEFAULTS = dict(
     pred_orig_latent=True, use_time_rnn=False, add_reward_embed_to_agent_token=False,
     add_state_pred_head=False, agent_predicts_state=False, continuous_norm_stats=None, continuous_dist_type='beta',
     continuous_dist_kwargs={}, continuous_target_action_range=None,
-    num_latent_genes=0, keep_reward_ema_stats=False, clip_values=False, time_attention_use_pope=False,
+    num_latent_genes=0, time_attention_use_pope=False,
     latent_ar=False, identity_latents_to_spatial=False, has_aug_conditioning=False, ssl_lapo=False,
     ssl_tem=False, actor_spr=False, agent_policy_gradient_frac=1., agent_value_gradient_frac=1.,
     policy_head_mlp_activation='silu', value_head_mlp_activation='silu', state_terminal_pred_mlp_activation='silu',
@@ -170,6 +170,11 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         delight_temperature=1.,
         normalize_advantages=None,
         policy_entropy_weight=.01,
+        keep_reward_ema_stats=False,
+        reward_ema_decay=0.998,
+        reward_quantile_filter=(0.05, 0.95),
+        value_clip=0.4,
+        clip_values=False,
         head_mlp_recipe='pre_rms',
         continuous_beta_param='softplus_p1',
         matmul_dtype='fp32',
@@ -327,6 +332,17 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
         self.pmpo_kl_div_loss_weight = pmpo_kl_div_loss_weight
         self.use_delight_gating, self.delight_temperature = use_delight_gating, delight_temperature
         self.normalize_advantages, self.policy_entropy_weight = normalize_advantages, policy_entropy_weight
+        # Dreamer-style return normalisation and PPO value clipping of the learner (dreamer4.py:5985-6015, 6283-6291); read at
+        # call time, as the reference reads them
+        self.keep_reward_ema_stats, self.reward_ema_decay = bool(keep_reward_ema_stats), float(reward_ema_decay)
+        self.reward_quantile_filter = tuple(float(q) for q in reward_quantile_filter)
+        if len(self.reward_quantile_filter) != 2 or not 0. <= self.reward_quantile_filter[0] <= self.reward_quantile_filter[1] <= 1.:
+            raise ValueError('reward_quantile_filter must be a pair 0 <= lo <= hi <= 1')
+        if not 0.5 < self.reward_ema_decay <= 1.:
+            raise ValueError('reward_ema_decay must lie in (0.5, 1]')
+        self.clip_values, self.value_clip = bool(clip_values), float(value_clip)
+        if self.value_clip < 0.:
+            raise ValueError('value_clip must not be negative')
         self.pool_heads, self.pool_dim_head = 4, 64              # AttentionPool defaults, dreamer4.py:2147-2148
         # [flow | spatial | registers | action (only with an action space, dreamer4.py:7124-7130) | agent]
         self.tokens_per_frame = 1 + num_spatial_tokens + num_register_tokens + (1 if (len(nda) > 0 or self.num_continuous_actions > 0) else 0) + 1
@@ -443,8 +459,8 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             _register(self, f'{name}.support', support, buffer=True, persistent=False)
             _register(self, f'{name}.centers', (support[:-1] + support[1:]) / 2, buffer=True, persistent=False)
         _register(self, 'zero', torch.tensor(0.), buffer=True, persistent=False)
-        # buffers of the reference's state_dict that the imagination path never reads (dreamer4.py:5245-5246, 5260-5263): registered
-        # so that a reference checkpoint loads with strict=True
+        # buffers of the reference's state_dict (dreamer4.py:5245-5246, 5260-5263), registered so that a reference checkpoint loads with
+        # strict=True.  The EMA pair is the state of keep_reward_ema_stats: the learner updates both in place (learner.py)
         for name, val in (('ema_returns_mean', 0.), ('ema_returns_var', 1.)):
             _register(self, name, torch.tensor(val), buffer=True)
         for name, val in self._loss_weight_init.items():

@@ -225,6 +225,18 @@ typedef struct d4_learn_io {
      * that produced agent_embed (dreamer4_amd/trunk_ops.py).  NULL (the default path): not computed. */
     float* d_agent_embed_policy;
     float* d_agent_embed_value;
+    /* ---- appended; all zero = off, the launches and bits of before ----
+     * keep_reward_ema_stats (D4:5985-6015): device [2] = ema_returns_mean, ema_returns_var, updated in place on the stream (no host
+     * synchronisation); NULL = off.  The masked returns are clamped to their q_lo / q_hi quantiles (torch.quantile, linear), their mean and
+     * biased variance go into the pair by lerp with weight 1 - reward_ema_decay, and the advantage becomes
+     * (returns - mean) / std - (old_values - mean) / std with std = sqrt(max(var, 1e-5)).  No learnable step: the pair is left as it is.
+     * Single process only: refused together with allreduce_sum. */
+    float* ema_returns;
+    double reward_ema_decay;
+    float q_lo, q_hi;
+    /* clip_values (D4:6283-6291): value loss = max(CE(values), -sum p log max(encode(old + clamp(values - old, +-value_clip)), 1e-20)) per row */
+    int32_t clip_values;
+    float value_clip;
 } d4_learn_io;
 
 int d4_learn(d4_engine* e, const d4_learn_io* io, void* stream);
@@ -820,6 +832,36 @@ typedef struct d4_policy_loss_desc {
     float* scratch;
 } d4_policy_loss_desc;
 int d4_policy_loss(const d4_policy_loss_desc* d, void* stream);
+/* Return statistics of keep_reward_ema_stats, stateless (dreamer4.py:5985-6015): one workgroup, no host synchronisation.
+ *   x = returns[i] with mask[i] != 0 (mask null: all n); lo, hi = their q_lo / q_hi quantiles (linear interpolation, exact order statistics by a
+ *   four-pass radix selection, any n); mean, var = mean and biased variance of clamp(x, lo, hi);
+ *   ema[0] <- lerp(ema[0], mean, 1 - reward_ema_decay), ema[1] likewise with var (in place; untouched when no element is kept);
+ *   adv[i] = (returns[i] - ema[0]) / std - (old_values[i] - ema[0]) / std for all n, std = sqrt(max(ema[1], 1e-5)), from the UPDATED pair;
+ *   stats[4] = lo, hi, mean, var (zeros when no element is kept). */
+int d4_return_stats(const float* returns, const float* old_values, const float* mask, int64_t n, float* ema, double reward_ema_decay, float q_lo,
+                    float q_hi, float* adv, float* stats, void* stream);
+/* The value branch's loss with PPO value clipping, stateless (dreamer4.py:6254-6295).  The fields are d4_hl_gauss_ce's arguments, plus
+ * old_values [rows], clip_values and value_clip, plus row_loss [rows] (the masked per-row losses).  clip_values = 0: d4_hl_gauss_ce's launches and
+ * bits (old_values may be null).  clip_values != 0: per row  values = sum softmax(logits) * centres (bin centres of the edges / the two-hot bin
+ * values), clipped = old + clamp(values - old, +-value_clip), q = the targets' encoder applied to clipped (same range clamp),
+ * loss = max(CE, -sum p log max(q, 1e-20)) and dlogits its gradient (through q and values where the clipped branch wins and no clamp is active).
+ * scratch >= rows + 64 floats. */
+typedef struct d4_value_loss_desc {
+    const float* logits; int32_t ld;
+    const float* returns;
+    const float* old_values;
+    const float* mask;
+    const float* support;
+    int32_t rows, bins;
+    float vmin, vmax, sigma, eps;
+    int32_t two_hot, clip_values;
+    float value_clip;
+    float* loss;
+    float* row_loss;
+    float* dlogits;
+    float* scratch;
+} d4_value_loss_desc;
+int d4_value_loss(const d4_value_loss_desc* d, void* stream);
 /* Pixel-side operators of the VideoTokenizer training forward (dreamer4.py:4239-4603; csrc/tok_train.hip).  Patch rows are
  * [(b t nh nw)][(p1 p2 c)] of a video (b c t (nh p1) (nw p2)); the patch row C * ps * ps and every `dim` must be multiples of 4, row pointers 16-byte
  * aligned.  No allocation, no host synchronisation; column sums and the loss sum go through per-block partials in the caller's `part` and one
