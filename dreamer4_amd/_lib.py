@@ -217,6 +217,9 @@ SYMBOLS = {
     'd4_gemm_run': (_I, [C.POINTER(GemmDesc), _I, _I, _P]),
     'd4_gemm_run_rowmap': (_I, [C.POINTER(GemmDesc), _I, _I, _I, _I, _I, _I, _P]),
     'd4_gemm_run_pair': (_I, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _I, _I, _P]),
+    'd4_gemm_fill_capacity': (_I, [C.POINTER(GemmDesc)]),
+    'd4_gemm_run_fill': (_I, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _I, _P]),
+    'd4_gemm_run_fill_rowmap': (_I, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _I, _I, _I, _I, _I, _P]),
     'd4_tile16_weights': (_I, [_P, _I, _P, _I, _I, _P]),
     'd4_frame_attn_out': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 2 + [_P] + [_I] * 3 + [_F] + [_I] * 3 + [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     'd4_attn_out_cols': (_I, [_P, _L, _L] * 4 + [_P] + [_P, _L, _L] * 2 + [_P] + [_I] * 3 + [_F] + [_I] * 3 + [_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),

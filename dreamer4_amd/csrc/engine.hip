@@ -830,11 +830,28 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------- forward
+// A feedforward's input projection as ff_block makes it and as engine_gemm hands it to gemm() on a split-operand engine (the weight's three planes)
+static GemmArgs ff_in_call(d4_engine* e, const FfPrep& fp, const float* x, int ldx, int rows) {
+    GemmArgs g1{x, ldx, fp.w1, e->D, e->ffh, e->inner_pad, fp.b1, nullptr, 0, rows, 2 * e->inner_pad, e->D,
+                GEMM_RMS_ROWSCALE | GEMM_SWIGLU, RMS_EPS, 2.0 * rows * (2.0 * e->inner) * e->D};
+    if (e->bf16 && e->split) {
+        for (const auto& m : e->mirrors)
+            if (g1.W >= m.src && g1.W < m.src + m.n) { g1.Wb = m.dst + (g1.W - m.src); break; }
+        if (g1.Wb) { g1.wplane = (int64_t)e->bf16_cap; if (!gemm_x3_applicable(g1)) { g1.Wb = nullptr; g1.wplane = 0; } }
+    }
+    return g1;
+}
+
+// fill (ff_fill_pool_keys; engine_forward_impl has checked the rules): the input projection runs as the filled form of the persistent kernel and carries
+// the first rows of the next pool's key problem on the workgroups its last round leaves idle
 static int ff_block(d4_engine* e, const FfPrep& fp, const float* out_b, const float* x, int ldx, float* y, int ldy,
-                    int rows, hipStream_t s, float* y_compact = nullptr, int S = 0, int has_agent = 1) {
+                    int rows, hipStream_t s, float* y_compact = nullptr, int S = 0, int has_agent = 1, const GemmArgs* fill = nullptr) {
     int rc;
     GemmArgs g1{x, ldx, fp.w1, e->D, e->ffh, e->inner_pad, fp.b1, nullptr, 0, rows, 2 * e->inner_pad, e->D,
                 GEMM_RMS_ROWSCALE | GEMM_SWIGLU, RMS_EPS, 2.0 * rows * (2.0 * e->inner) * e->D};
+    if (fill) {
+        if ((rc = gemm_x3sk_fill(ff_in_call(e, fp, x, ldx, rows), *fill, gemm_x3sk_fill_tiles(*fill), s))) return rc;
+    } else
     if ((rc = engine_gemm(g1, s))) return rc;
     GemmArgs g2{e->ffh, e->inner_pad, fp.w2, e->inner_pad, y, ldy, out_b, x, ldx, rows, e->D, e->inner_pad, 0, RMS_EPS,
                 2.0 * rows * (double)e->D * e->inner};
@@ -852,13 +869,26 @@ int g_last_layer_compact_q = 1;       // d4_debug_switch("last_layer_compact_q")
 // The register rows of slab 0 are constants of the weights (fp32 engine, dynamics mode): test hooks, 0 = the full launches, same bits
 int g_layer0_const_rows = 1;          // d4_debug_switch("layer0_const_rows"): layer 0's fused projection runs on the rows that change; the register rows were prefilled at prepare
 int g_pool_const_keys = 1;            // d4_debug_switch("pool_const_keys"): the in-loop pools' keys of slab 0 likewise, the changing rows for all pools in one batched launch
+// The pools' old keys ride in the preceding feedforward's input projection (split-operand fp32 engine, dynamics mode): test hook, 0 = the separate launches, same bits
+int g_ff_fill_pool_keys = 1;          // d4_debug_switch("ff_fill_pool_keys")
 unsigned g_launch_count = 0;          // kernel launches so far (common.h: D4_LAUNCH_CHECK; read / reset through d4_debug_switch("launch_count"))
+// The key problem of pool p's mix path over L hiddens of M rows, as pool_block issues it (rule_M, keys0: see there)
+static GemmArgs pool_key_call(d4_engine* e, int p, const float* hiddens, int L, int M, int rule_M, float* keys0) {
+    const int D = e->D, hp = e->hp;
+    GemmArgs gk{hiddens, D, e->pkv_w[p], D, e->pool_kv, hp, nullptr, nullptr, 0, L * M, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+    gk.rule_M = L * rule_M;
+    if (keys0) { gk.A = hiddens + (size_t)M * D; gk.C = keys0 + (size_t)M * hp; gk.M = (L - 1) * M; gk.rule_M = L * M; }
+    return gk;
+}
+
 // rule_M > 0 (the final pool of an evaluation that keeps the agent row alone): the rows the same pool has when the spatial rows are kept too — every
 // product and the mix are dispatched as for that row count (GemmArgs::rule_M), so the rows computed carry the bits they have there
 static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int M, hipStream_t s, const float* hiddens = nullptr,
-                      float* y_compact = nullptr, int S = 0, int has_agent = 1, int rule_M = 0, float* keys0 = nullptr) {
+                      float* y_compact = nullptr, int S = 0, int has_agent = 1, int rule_M = 0, float* keys0 = nullptr, int keys_done = 0) {
     // keys0 (an in-loop pool of an evaluation that takes the constant register rows): the pool's keys [L][M][hp] with slab 0's block already in place
     // (prefilled register rows + the evaluation's batched launch) — the key problem covers slabs 1 .. L - 1, pinned to the family of all L
+    // keys_done (ff_fill_pool_keys): the first rows of the key problem were written by the preceding feedforward's filled launch; the problem starts
+    // behind them, pinned to the family of all L likewise
     if (!hiddens) hiddens = e->slabs;
     const d4_config& c = e->c;
     const int D = e->D, hp = e->hp;
@@ -886,12 +916,9 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
             pm.k = nullptr; pm.k_b = e->kall_b + (size_t)p * hp; pm.ldk = ld;
             pm.q = nullptr; pm.q_b = e->kall_b + (size_t)(L - 1) * M * ld + (size_t)(c.depth - 1) * hp; pm.ldq = ld;
         } else {
-        GemmArgs gk{hiddens, D, e->pkv_w[p], D, e->pool_kv, hp, nullptr, nullptr, 0, L * M, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
-        gk.rule_M = L * rule_M;
-        if (keys0) {
-            gk.A = hiddens + (size_t)M * D; gk.C = keys0 + (size_t)M * hp; gk.M = (L - 1) * M; gk.rule_M = L * M;
-            pm.k = keys0;
-        }
+        GemmArgs gk = pool_key_call(e, p, hiddens, L, M, rule_M, keys0);
+        if (keys0) pm.k = keys0;
+        if (keys_done > 0) { gk.A += (size_t)keys_done * D; gk.C += (size_t)keys_done * hp; gk.M -= keys_done; gk.rule_M = L * M; }
         if ((rc = gemm_two(gq, gk, s))) return rc;
         if (t_bf16) pm.k_b = t_bf16->shadow_of(e->pool_kv);               // bf16 keys (the only copy of them in this mode)
         }
@@ -1187,10 +1214,32 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         float* h1 = slab(2 * l + 1);
         float* h2 = slab(2 * l + 2);
         if (!fused_out && (rc = gemm_c2(e->att, hd, a.to_out, hd, h1, D, M, D, hd, 0, nullptr, x_in, D, cslab(2 * l + 1), S, t_keep_hi - t_keep_lo, has_agent, s))) return rc;
-        if ((rc = ff_block(e, e->ffp[l], e->layer_ff[l].out_b, h1, D, h2, D, M, s, cslab(2 * l + 2), S, has_agent))) return rc;
+        // The pool behind this feedforward projects every hidden so far to keys, and all but the newest slab exist before the feedforward starts: their
+        // first rows ride on the workgroups the input projection's last round leaves idle (gemm_x3sk.hip: the filled form).  Taken only where
+        // the dispatcher runs the input projection on the persistent kernel by its own rule, that launch has a partial round, the pool takes the mix
+        // path with separate keys, and the full key problem and the shortened one both stay on the LDS-DMA family (whose bits the fill tiles carry).
+        GemmArgs kfill{};
+        int keys_done = 0;
+        if (g_ff_fill_pool_keys && dynamics && e->split && l < c.depth - 1 && c.pool_heads == 4 && D <= 1024 && !e->kall_b) {
+            const int L = 2 * l + 3;
+            const GemmArgs g1 = ff_in_call(e, e->ffp[l], h1, D, M);
+            const int cap = g1.Wb && gemm_rule_takes_x3sk(g1) ? gemm_x3sk_fill_capacity(g1) : 0;
+            const GemmArgs gk = pool_key_call(e, l, e->slabs, L, M, 0, keys0(l));
+            const int ready = (gk.M - M) / 128;                              // whole 128-row blocks of the slabs <= 2 l + 1 (the problem ends with slab 2 l + 2)
+            const int per_block = (e->hp + 63) / 64;                          // 128 x 64 tiles per 128-row block
+            const int blocks = cap / per_block < ready ? cap / per_block : ready;
+            if (blocks > 0 && tiled_family(L * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[l]) &&
+                tiled_family(gk.M - 128 * blocks, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[l], L * M)) {
+                keys_done = 128 * blocks;
+                kfill = gk;
+                kfill.M = keys_done; kfill.rule_M = 0;
+                D4_REQUIRE(gemm_x3sk_fill_applicable(kfill), "ff_fill_pool_keys: the key problem of pool %d is no fill problem", l);
+            }
+        }
+        if ((rc = ff_block(e, e->ffp[l], e->layer_ff[l].out_b, h1, D, h2, D, M, s, cslab(2 * l + 2), S, has_agent, keys_done ? &kfill : nullptr))) return rc;
         if (l != c.depth - 1) {
             float* xc = (denoise_only && l == c.depth - 2 && !e->is_time[c.depth - 1] && S <= 16 && S >= 8) ? e->xpool_c : nullptr;
-            if ((rc = pool_block(e, l, h2, e->xpool, 2 * l + 3, M, s, nullptr, xc, S, has_agent, 0, keys0(l)))) return rc;
+            if ((rc = pool_block(e, l, h2, e->xpool, 2 * l + 3, M, s, nullptr, xc, S, has_agent, 0, keys0(l), keys_done))) return rc;
             x_in = e->xpool;
         }
     }
@@ -1662,7 +1711,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
     const int lean_keep = (lean && d4::engine_clean_agent_only(e)) ? 1 : c.num_spatial_tokens + 1;
     // what a captured frame's launches depend on besides its shape: the clean-evaluation form and the forms of the latent-token ends (test hooks)
     const int variant = (lean ? 1 : 0) | (d4::g_lqap_in_fused ? 2 : 0) | (d4::g_lqap_out_fused ? 4 : 0) | (d4::g_last_layer_compact_q ? 8 : 0) |
-                        (d4::g_layer0_const_rows ? 16 : 0) | (d4::g_pool_const_keys ? 32 : 0);
+                        (d4::g_layer0_const_rows ? 16 : 0) | (d4::g_pool_const_keys ? 32 : 0) | (d4::g_ff_fill_pool_keys ? 64 : 0);
     // Only the sampled action (policy head) and the terminal feed the next frame; values and rewards are outputs nobody reads inside the loop: they
     // are computed once after it, over the whole agent history [B][F][D] — the caller's, else the engine's own (one frame: the frame's rows).
     const float* hist = nullptr;
@@ -1850,6 +1899,11 @@ int d4_debug_switch(const char* name, int value) {
         d4::g_launch_count = (unsigned)value;
         return old;
     }
+    if (name && !strcmp(name, "ff_fill_launches")) {    // launches of the filled persistent kernel that carried fill tiles, counted as launch_count is
+        const int old = (int)(d4::g_fill_launches & 0x7fffffffu);
+        d4::g_fill_launches = (unsigned)value;
+        return old;
+    }
     if (name && !strcmp(name, "time_attn_fused_append")) sw = &d4::g_time_attn_fused_append;
     else if (name && !strcmp(name, "rollout_clean_agent_row")) sw = &d4::g_rollout_clean_agent_row;
     else if (name && !strcmp(name, "rollout_batched_heads")) sw = &d4::g_rollout_batched_heads;
@@ -1859,6 +1913,7 @@ int d4_debug_switch(const char* name, int value) {
     else if (name && !strcmp(name, "last_layer_compact_q")) sw = &d4::g_last_layer_compact_q;
     else if (name && !strcmp(name, "layer0_const_rows")) sw = &d4::g_layer0_const_rows;
     else if (name && !strcmp(name, "pool_const_keys")) sw = &d4::g_pool_const_keys;
+    else if (name && !strcmp(name, "ff_fill_pool_keys")) sw = &d4::g_ff_fill_pool_keys;
     else if (name && !strcmp(name, "pool_wide_keys")) sw = &d4::g_pool_wide_keys;
     else if (name && !strcmp(name, "pool_mix_deep")) sw = &d4::g_pool_mix_deep;
     else if (name && !strcmp(name, "time_attn_tiled")) sw = &d4::g_time_attn_tiled;
@@ -2295,6 +2350,30 @@ static int gemm_run_args(const d4::GemmArgs& g, int family, int config, void* st
     }
     D4_REQUIRE(false, "d4_gemm_run: unknown family %d", family);
 #undef D4_RUN_REFUSE
+}
+// The filled form of the persistent split-operand kernel (gemm_x3sk.hip): `main` in whole tiles with the first `fill_tiles` 128 x 64 tiles of `fill` on the
+// workgroups its last round leaves idle; the launcher's refusals come back as errors
+int d4_gemm_fill_capacity(const d4_gemm_desc* main) {
+    if (!main || main->M < 1 || main->N < 1 || main->K < 1) return 0;
+    return d4::gemm_x3sk_fill_capacity(gemm_args_of(*main));
+}
+int d4_gemm_run_fill(const d4_gemm_desc* main, const d4_gemm_desc* fill, int fill_tiles, void* stream) {
+    if (int rc = gemm_desc_check("d4_gemm_run_fill", main)) return rc;
+    D4_REQUIRE(fill_tiles == 0 || fill, "d4_gemm_run_fill: fill tiles without a fill descriptor");
+    if (fill_tiles != 0) if (int rc = gemm_desc_check("d4_gemm_run_fill", fill)) return rc;
+    const d4::GemmArgs g = gemm_args_of(*main);
+    D4_REQUIRE(((uintptr_t)g.A % 16) == 0 && (g.lda % 4) == 0 && !g.wscale, "d4_gemm_run_fill: main operands must be 16-byte aligned split-operand planes");
+    return d4::gemm_x3sk_fill(g, fill ? gemm_args_of(*fill) : d4::GemmArgs{}, fill_tiles, static_cast<hipStream_t>(stream));
+}
+// ... with an output row map on the FILL problem (as d4_gemm_run_rowmap): the filled form does not implement it, so this is an error — the entry exists
+// so that the refusal can be observed
+int d4_gemm_run_fill_rowmap(const d4_gemm_desc* main, const d4_gemm_desc* fill, int fill_tiles, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream) {
+    if (int rc = gemm_desc_check("d4_gemm_run_fill_rowmap", main)) return rc;
+    if (int rc = gemm_desc_check("d4_gemm_run_fill_rowmap", fill)) return rc;
+    D4_REQUIRE(rm_Sc >= 1 && rm_nr >= 0 && rm_lo >= 0 && rm_lo <= rm_Sc && rm_S == rm_Sc + rm_nr && rm_S <= 65535, "d4_gemm_run_fill_rowmap: bad row map (Sc=%d S=%d lo=%d nr=%d)", rm_Sc, rm_S, rm_lo, rm_nr);
+    d4::GemmArgs f = gemm_args_of(*fill);
+    f.rm_Sc = (uint16_t)rm_Sc; f.rm_lo = (uint16_t)rm_lo; f.rm_nr = (uint16_t)rm_nr;
+    return d4::gemm_x3sk_fill(gemm_args_of(*main), f, fill_tiles, static_cast<hipStream_t>(stream));
 }
 int d4_gemm_run_pair(const d4_gemm_desc* da, const d4_gemm_desc* db, int target, int config, void* stream) {
     if (int rc = gemm_desc_check("d4_gemm_run_pair", da)) return rc;

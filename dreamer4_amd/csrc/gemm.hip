@@ -770,6 +770,24 @@ static int launch_v3sk(const GemmArgs& p, hipStream_t stream) {
     return 0;
 }
 
+// The filled form of the persistent kernel (gemm_x3sk.hip): accounted under the SAME profile class as the plain form, with the flops of both problems —
+// the class list does not grow (gemm_profile_enable keeps its stride field at bit 27).
+int gemm_x3sk_fill(const GemmArgs& p, const GemmArgs& fill, int fill_tiles, hipStream_t stream) {
+    std::lock_guard<std::recursive_mutex> lock(gemm_mutex());
+    const int cls = N_TILE_CFG + gemm2_configs() + gemm_x3_configs();
+    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
+    if (!timed) return gemm_x3sk_fill_launch(p, fill, fill_tiles, stream);
+    ProfRec rec{};
+    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
+    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
+    rec.bm = 128; rec.bn = 128;
+    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K;
+    if (fill_tiles > 0) rec.flops += 2.0 * fill.M * fill.N * fill.K * fill_tiles / (double)gemm_x3sk_fill_tiles(fill);
+    if (int rc = gemm_x3sk_fill_launch(p, fill, fill_tiles, stream, rec.a, rec.b)) return rc;
+    g_prof.push_back(rec);
+    return 0;
+}
+
 static int autotune_v3(const GemmArgs& p, hipStream_t stream, int* best_out) {
     hipEvent_t e0 = prof_event(), e1 = prof_event();
     const int saved_mask = g_prof_mask;

@@ -14,12 +14,18 @@
 // gemm_x3_kernel, 2.4 rounds -> 2 rounds + one shorter one (a half tile takes ~0.88 of a whole tile's time — the k-tile step is bound by the
 // per-wave split / LDS / barrier chain, not by the MFMAs: 83.3 vs 86.5 us on the SiLU-GLU input projection).
 //
+// FILLED FORM (gemm_x3sk_fill_kernel, below): whole tiles only, and the workgroups the last partial round leaves idle each run one
+// 128 x 64 tile of an independent f32-input product (the LDS-DMA family's 8-wave configuration, gemm2_body.h).  The engine's in-loop feedforwards take it:
+// their input projection carries the first rows of the next pool's key projection (86.9 us per launch against 83.3 with half tiles, for 12 us less in
+// the pool's pair launch: profiles/ff_fill_ab.txt).
+//
 // (Rounds 3-4 also carried a k-cut of the last round — "stream-K" with an integer split, partial tiles exchanged through agent-scope atomics.  Correct on
 // every epilogue but a measured no-go: a 64 KB slice takes 10-20 us to cross between workgroups, which is what the cut saves at K = 512
 // (profiles/r03i_gemm_x3sk.txt).  Removed in round 5 together with its workspace allocation.)
 #include "common.h"
 #include <hip/hip_ext.h>
 #include "kernels.h"
+#include "gemm2_body.h"      // the fill tiles of the filled form
 #include <type_traits>
 
 namespace d4 {
@@ -286,7 +292,8 @@ __device__ __forceinline__ void sk_item(const SkArgs& s, const int bm0, const in
     __syncthreads();                                   // rowscale_s / the LDS tiles are rewritten by the next item
 }
 
-template <bool RMAP>
+// WHOLE (the filled form below): whole tiles only, whatever s.half says — the half-tile items are not instantiated
+template <bool RMAP, bool WHOLE = false>
 __device__ __forceinline__ void sk_walk(const SkArgs s) {
     const GemmArgs& p = s.p;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -309,7 +316,7 @@ __device__ __forceinline__ void sk_walk(const SkArgs s) {
         tm = band * RB + j % rows; tn = j / rows;
     };
     int tm, tn;
-    if (s.half) {
+    if (!WHOLE && s.half) {
         // whole rounds, then the remaining tiles as 2 R half tiles: item h = (remaining tile h / 2, column half h & 1) on workgroup h % P
         for (int i = 0; i < s.F; ++i) {
             tile_of(b + i * s.P, tm, tn);
@@ -344,6 +351,24 @@ __device__ __forceinline__ void sk_walk(const SkArgs s) {
 __global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_kernel(SkArgs s) { sk_walk<false>(s); }
 // the same walk with the row-mapped store (GemmArgs::rm_Sc > 0; plain epilogue only: the launcher checks)
 __global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_rowmap_kernel(SkArgs s) { sk_walk<true>(s); }
+
+// FILLED FORM: the whole-tile walk of the main problem, and in the last partial round — where workgroups R .. P - 1 have nothing left — workgroup b >= R
+// runs tile b - R of an INDEPENDENT f32-input problem (`fill`) through the LDS-DMA family's 8-wave 128 x 64 configuration (gemm2_body.h: 512 threads and
+// 74 KB of LDS, which an idle workgroup of this kernel has).  The engine hands it the pool keys of the slabs that exist before the feedforward starts
+// (engine.hip: ff_fill_pool_keys).  Nothing crosses between the two problems or between workgroups; the main problem keeps the bits of
+// gemm_x3_kernel, the fill tiles those of every configuration of gemm2.hip.  FILL_RMS (the fill's row scale) picks the instantiation: no run-time
+// branch enters either k-loop.  The fill tile starts on the same dynamic LDS block once the workgroup's last whole item has ended on its barrier.
+constexpr int SKF_BM = 128, SKF_BN = 64;
+constexpr size_t SKF_LDS = (size_t)(3 * (SKF_BM + SKF_BN) * 32 + SKF_BM) * sizeof(float);
+static_assert(SKF_LDS <= SK_LDS, "a fill tile runs in the LDS of the workgroup it fills");
+template <bool FILL_RMS>
+__global__ __launch_bounds__(SK_NT, 2) void gemm_x3sk_fill_kernel(SkArgs s, GemmArgs fill, int fill_tiles) {
+    const int b = blockIdx.x;
+    sk_walk<false, true>(s);                           // F rounds, then the R remaining tiles on workgroups 0 .. R - 1
+    if (b < s.R || b - s.R >= fill_tiles) return;
+    __syncthreads();
+    gemm2_body<4, 2, 2, 2, 3, 32, FILL_RMS>(fill, b - s.R, 0);
+}
 
 static std::atomic<int> g_sk_cus[64];            // per device id (a process may drive several devices); 0 = not queried yet
 
@@ -405,6 +430,61 @@ int gemm_x3sk_launch(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEv
     if (ea) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)SK_LDS, stream, ea, eb, 0, a);
     else hipLaunchKernelGGL(k, grid, block, SK_LDS, stream, a);
     D4_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the filled form -------------------------------------------------------------------------------------------------------------------------
+// Workgroups the last round of `main` leaves idle under the whole-tile plan (shape and CU count only); 0 where the call is not persistent (less than
+// one whole round) or has no partial round.
+int gemm_x3sk_fill_capacity(const GemmArgs& main) {
+    if (!gemm_x3sk_applicable(main)) return 0;
+    int F, R, P;
+    (void)gemm_x3sk_half_plan(main, &F, &R, &P);
+    return F >= 1 && R > 0 ? P - R : 0;
+}
+
+unsigned g_fill_launches = 0;         // filled launches that carried fill tiles (host side; read / reset through d4_debug_switch("ff_fill_launches"))
+
+int gemm_x3sk_fill_tiles(const GemmArgs& fill) { return cdiv(fill.M, SKF_BM) * cdiv(fill.N, SKF_BN); }
+
+// what a fill tile can be: an f32-input product of the LDS-DMA family, one problem, plain epilogue (row scale, bias)
+bool gemm_x3sk_fill_applicable(const GemmArgs& fill) {
+    return gemm2_applicable(fill) && fill.batch <= 1 && fill.rm_Sc == 0 && fill.C && !fill.C2 && !fill.R && !fill.Cb && !fill.C2b && !(fill.flags & ~GEMM_RMS_ROWSCALE) &&
+           ((uintptr_t)fill.A % 16) == 0 && ((uintptr_t)fill.W % 16) == 0;
+}
+
+// `main` as gemm_x3sk_launch would run it, whole tiles only, with the first `fill_tiles` tiles (128 x 64, in the LDS-DMA family's block order) of `fill`
+// on the workgroups main's last round leaves idle.  fill_tiles == 0: the whole-tile walk of main alone (`fill` is not looked at).
+int gemm_x3sk_fill_launch(const GemmArgs& main, const GemmArgs& fill, int fill_tiles, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
+    D4_REQUIRE(gemm_x3sk_applicable(main) && main.rm_Sc == 0, "gemm_x3sk fill: main call not supported (M=%d N=%d K=%d flags=%d batch=%d row map %d)", main.M, main.N,
+               main.K, main.flags, main.batch, (int)main.rm_Sc);
+    SkArgs a;
+    a.p = main;
+    (void)gemm_x3sk_half_plan(main, &a.F, &a.R, &a.P);
+    a.half = 0;
+    D4_REQUIRE(a.F >= 1, "gemm_x3sk fill: the main call (M=%d N=%d: %d tiles on %d workgroups) has no whole round, it is not persistent", main.M, main.N, a.R, a.P);
+    const int cap = a.R > 0 ? a.P - a.R : 0;
+    D4_REQUIRE(fill_tiles >= 0 && fill_tiles <= cap, "gemm_x3sk fill: %d fill tiles exceed the capacity of %d idle workgroups", fill_tiles, cap);
+    GemmArgs f{};
+    bool rms = false;
+    if (fill_tiles > 0) {
+        D4_REQUIRE(gemm_x3sk_fill_applicable(fill), "gemm_x3sk fill: fill problem not supported (M=%d N=%d K=%d flags=%d batch=%d row map %d: an f32-input product of "
+                   "K %% 32 == 0, no batch, row map, second output or epilogue other than row scale / bias)", fill.M, fill.N, fill.K, fill.flags, fill.batch, (int)fill.rm_Sc);
+        D4_REQUIRE(fill_tiles <= gemm_x3sk_fill_tiles(fill), "gemm_x3sk fill: %d fill tiles, the fill problem (M=%d N=%d) has %d", fill_tiles, fill.M, fill.N, gemm_x3sk_fill_tiles(fill));
+        f = fill;
+        rms = (fill.flags & GEMM_RMS_ROWSCALE) != 0;
+    }
+    auto k = rms ? gemm_x3sk_fill_kernel<true> : gemm_x3sk_fill_kernel<false>;
+    static DeviceOnce attr_set[2];
+    if (attr_set[rms].need()) {
+        D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS));
+        attr_set[rms].done();
+    }
+    const dim3 grid(a.P), block(SK_NT);
+    if (ea) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)SK_LDS, stream, ea, eb, 0, a, f, fill_tiles);
+    else hipLaunchKernelGGL(k, grid, block, SK_LDS, stream, a, f, fill_tiles);
+    D4_LAUNCH_CHECK();
+    if (fill_tiles > 0) ++g_fill_launches;
     return 0;
 }
 

@@ -108,6 +108,14 @@ bool gemm_x3sk_applicable(const GemmArgs& p);
 bool gemm_x3sk_rule(const GemmArgs& p);                    // the calls that take it (a rule on the shape and the CU count)
 const char* gemm_x3sk_name();
 int gemm_x3sk_launch(const GemmArgs& p, hipStream_t stream, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
+// ... its filled form (gemm_x3sk_fill_kernel): `main` walked in whole tiles, and the first `fill_tiles` 128 x 64 tiles of an independent f32-input product
+// (LDS-DMA family, gemm2_body.h: that family's bits) on the workgroups main's last partial round leaves idle
+int gemm_x3sk_fill_capacity(const GemmArgs& main);         // those workgroups, by shape and CU count; 0: main is not persistent or has no partial round
+int gemm_x3sk_fill_tiles(const GemmArgs& fill);            // 128 x 64 tiles of a fill problem
+bool gemm_x3sk_fill_applicable(const GemmArgs& fill);      // one problem of gemm2_applicable, plain epilogue (row scale / bias), no row map or second output
+int gemm_x3sk_fill_launch(const GemmArgs& main, const GemmArgs& fill, int fill_tiles, hipStream_t stream, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
+extern unsigned g_fill_launches;                           // gemm_x3sk.hip: launches of the filled form that carried fill tiles (test hook)
+int gemm_x3sk_fill(const GemmArgs& main, const GemmArgs& fill, int fill_tiles, hipStream_t stream);   // gemm.hip: the launch under the dispatcher's lock and profile class
 // second fp32 family (gemm2.hip): 16x16x4 MFMA fed by an LDS-DMA ring; non-transposed operands, K % 32 == 0
 bool gemm2_applicable(const GemmArgs& p);
 bool gemm2_config_valid(int c, const GemmArgs& p);

@@ -633,6 +633,15 @@ int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream);
  * goes to row (r / rm_Sc) * rm_S + (r % rm_Sc) + ((r % rm_Sc) >= rm_lo ? rm_nr : 0) and the gap rows are not written.  D4_GEMM_X3SK and D4_GEMM_V2 (single
  * and batched) implement it for the plain epilogue (bias, row scale); every other family, and any other epilogue, fails with an error. */
 int d4_gemm_run_rowmap(const d4_gemm_desc* d, int family, int config, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream);
+/* The filled form of the persistent split-operand kernel (csrc/gemm_x3sk.hip: gemm_x3sk_fill_launch).  `main` (a D4_GEMM_X3SK call of at least one whole
+ * round of 128 x 128 tiles, no row map) is walked in whole tiles, and the first `fill_tiles` 128 x 64 tiles of `fill` — an independent f32-input product of
+ * the LDS-DMA family: no batch, row map, second output or epilogue other than row scale / bias; tiles in that family's block order — run on the workgroups
+ * main's last partial round leaves idle.  d4_gemm_fill_capacity: how many those are on the current device (0: not persistent, or no partial round).  More
+ * tiles than the capacity or than the fill problem has, an unsupported fill, or a main call the plain launcher refuses fail with an error.  Both outputs
+ * carry the bits of the two plain launches.  d4_gemm_run_fill_rowmap puts an output row map (as d4_gemm_run_rowmap) on the fill, which is refused. */
+int d4_gemm_fill_capacity(const d4_gemm_desc* main_call);
+int d4_gemm_run_fill(const d4_gemm_desc* main_call, const d4_gemm_desc* fill, int fill_tiles, void* stream);
+int d4_gemm_run_fill_rowmap(const d4_gemm_desc* main_call, const d4_gemm_desc* fill, int fill_tiles, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream);
 #define D4_PAIR_SKINNY 0        /* gemm_skinny_pair */
 #define D4_PAIR_BF16A 1         /* gemm_bf16a_pair_launch */
 #define D4_PAIR_V2 2            /* gemm2_pair_launch(config) */
