@@ -88,6 +88,8 @@ struct d4_engine {
     bool h2 = false;                       // opt-in `fp32_fp16x2` mode: mirrors are two fp16 planes + an exact power-of-two scale per weight row (gemm_h2.hip:
                                            // 23-bit operand images, three products, fp32 accumulate); activations stay fp32, their row exponents in `aexp`
     bool fp32_planes() const { return split || h2; }      // an fp32-class engine whose GEMMs read plane mirrors of their weights
+    bool pool_mix_path() const { return c.pool_heads == 4 && D <= 1024; }      // the pools project keys only; values come from one mix of the hiddens (pool_block)
+    int attn_wide() const { return (c.wide_frames & 2) ? 2 : (c.wide_frames & 1); }      // SmallAttnArgs::wide of every attention this engine launches
     uint16_t* bf16_arena = nullptr; size_t bf16_cap = 0, bf16_used = 0;
     float* wscale_arena = nullptr; size_t wscale_cap = 0, wscale_used = 0;      // h2 mode: the inverse row scales, one float per mirrored weight row
     // h2 mode: scale exponents of activation rows (GemmArgs::aexp).  The residual-stream slabs keep theirs for the whole evaluation (every later attention
@@ -97,6 +99,10 @@ struct d4_engine {
     std::vector<char> aexp_valid;
     struct Mirror { const float* src; size_t n; uint16_t* dst; int ld; float* scales; };
     std::vector<Mirror> mirrors;
+    const Mirror* mirror_of(const float* w) const {
+        for (const auto& m : mirrors) if (w >= m.src && w < m.src + m.n) return &m;
+        return nullptr;
+    }
     // bf16 mode (not split): bf16 IMAGES of the activation buffers the trunk GEMMs read (same element offsets / leading dimensions as the fp32
     // buffer).  Producers write them (GEMM epilogue `Cb`, attention / pool-mix `out_b`, a conversion pass elsewhere) and consumers read them
     // through gemm_bf16a.hip (both operands by LDS-DMA) — for the GEMMs numerically the rounding the fp32-activation kernel applied on its way into LDS.
@@ -201,8 +207,9 @@ int engine_resolve(d4_engine* e);
 int engine_prepare(d4_engine* e, hipStream_t s);
 // need_pred = false (with need_agent; the rollout's clean evaluation): the latent prediction is not wanted — to_latent_pred is skipped and, where
 // engine_clean_agent_only(e), the final stage runs on the agent row alone: e->xfc is then [B*Tq][1][D] and e->pred is left as it was
+// sig_uniform >= 0: every frame is at this signal level (the decode loop: e->sig is not read)
 int engine_forward(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev = nullptr, bool need_pred = true);
+                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev = nullptr, bool need_pred = true, int sig_uniform = -1);
 bool engine_clean_agent_only(const d4_engine* e);
 void engine_drop_graphs(d4_engine* e);
 int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, float* out, int ldo,

@@ -148,7 +148,7 @@ int engine_layout(d4_engine* e, bool assign) {
     const int nr = c.num_register_tokens;
     const bool const_rows = !e->encoder && !e->decoder && (!e->bf16 || e->split) && nr > 0;
     const bool const_l0 = const_rows && e->split;                                        // layer 0's projection: the split-operand family only
-    const bool const_keys = const_rows && depth >= 2 && c.pool_heads == 4 && D <= 1024;   // the pools' mix path (keys only, [L][M][hp])
+    const bool const_keys = const_rows && depth >= 2 && e->pool_mix_path();              // (keys only, [L][M][hp])
     if (const_l0 || const_keys) e->slab0r = fl(Fr * (size_t)(S - nr) * D);
     if (const_l0) {
         e->c0_proj = fl((size_t)nr * e->Nproj0);
@@ -197,7 +197,7 @@ int engine_layout(d4_engine* e, bool assign) {
         // the attention pools' projected KEYS (mix path): written as a bf16 image only — the pool's key projection at N = 256 is bound by its output
         // bytes (170 flop per byte with fp32 keys), and the pool mix reads every key row once: half the bytes on both sides.  The scores then see keys
         // rounded to bf16 like every other activation of this mode.
-        if (c.pool_heads == 4 && D <= 1024) sh(e->pool_kv, (size_t)e->nslab * M * 2 * hp, true);
+        if (e->pool_mix_path()) sh(e->pool_kv, (size_t)e->nslab * M * 2 * hp, true);
     }
     e->kall_b = nullptr; e->kall_ld = 0;
     if (!e->pkq_w.empty()) {
@@ -445,12 +445,15 @@ int engine_resolve(d4_engine* e) {
 }
 
 // ------------------------------------------------------------------------------------- bf16 mirrors
-// The trunk's GEMMs run on the bf16 MFMA kernel when the engine was created with matmul_bf16: engine_forward sets the thread's
-// active engine, and every GEMM issued below it swaps its weight pointer for the bf16 mirror made at prepare time.
-static thread_local d4_engine* t_bf16 = nullptr;
-static thread_local int t_sig_uniform = -1;    // >= 0: every frame of the next engine_forward is at this signal level (decode loop: no fill kernel)
-static thread_local int t_keep_lo = 1;         // first token row of a frame the compacted copies keep (set by engine_forward)
-static thread_local int t_keep_hi = 1;         // ... and one past the last (== t_keep_lo: the compacted copies keep the agent row alone)
+// What the launches of one evaluation share (made by engine_forward, and by engine_prepare for its constant blocks).  The trunk's GEMMs read the
+// mirrors `img` made of their weights at prepare time; heads, learner and everything before the mirrors exist call gemm_fp32 instead.
+struct EvalCtx {
+    d4_engine* img;            // the engine whose weight mirrors (and bf16 activation images) the trunk's GEMMs read; null: an engine without mirrors
+    hipStream_t s;
+    int keep_lo = 1;           // first token row of a frame the compacted copies keep
+    int keep_hi = 1;           // ... and one past the last (== keep_lo: the compacted copies keep the agent row alone)
+    int sig_uniform = -1;      // >= 0: every frame of the evaluation is at this signal level (decode loop: no fill kernel)
+};
 
 static int mirror_weight(d4_engine* e, const float* src, size_t rows, int ld, hipStream_t s) {
     size_t n = rows * (size_t)ld;
@@ -475,21 +478,38 @@ static int mirror_weight(d4_engine* e, const float* src, size_t rows, int ld, hi
     return cvt_f32_to_bf16(src, dst, (int64_t)n, s);
 }
 
-// fp16x2 mode: attach the fp16 planes and row scales of g's weight view (whole rows of a mirrored matrix at its leading dimension) and — when the
-// dispatcher's rule sends the call to gemm_h2.hip — the scale exponents of A's rows: a residual-stream slab keeps them for the evaluation
-// (computed once, by the first GEMM that reads the slab), any other activation buffer gets them right here (row_scale_exp: one small launch)
-static int attach_h2(d4_engine* e, GemmArgs& g, hipStream_t s) {
+// The weight of a trunk GEMM as gemm() will see it: g's mirror image attached by the engine's mode, or left off where that mode's kernels do not take
+// the call (which then runs on the f32-input kernels).  engine_gemm launches exactly this, and every gemm_rule_takes_* question about a trunk call is
+// asked of exactly this.  Returns whether g.W has a mirror; img == null (an engine without mirrors) leaves g as it is.
+//   split-operand fp32: the three bf16 planes, if gemm_x3_applicable        bf16: the bf16 image, if gemm_bf16_applicable (e.g. not at K % 32)
+//   fp16x2: the two fp16 planes + row scales of a view of whole rows of the mirrored matrix at its leading dimension, if gemm_h2_takes
+static bool trunk_call(const d4_engine* img, GemmArgs& g) {
+    if (!img) return false;
     g.Wb = nullptr; g.wplane = 0; g.wscale = nullptr; g.strideWs = 0; g.aexp = nullptr;
-    const int nb = g.batch > 1 ? g.batch : 1;
-    for (const auto& m : e->mirrors) {
-        if (g.W < m.src || g.W >= m.src + m.n) continue;
-        const size_t off = (size_t)(g.W - m.src);
-        if (g.ldw != m.ld || (off % (size_t)m.ld) != 0 || (nb > 1 && (g.strideW % m.ld) != 0)) return 0;     // not a row view: f32-input kernels
-        g.Wb = m.dst + off; g.wplane = (int64_t)e->bf16_cap; g.wscale = m.scales + off / (size_t)m.ld; g.strideWs = nb > 1 ? g.strideW / m.ld : 0;
-        break;
+    const d4_engine::Mirror* m = img->mirror_of(g.W);
+    if (!m) return false;
+    const size_t off = (size_t)(g.W - m->src);
+    if (img->h2) {
+        const int nb = g.batch > 1 ? g.batch : 1;
+        if (g.ldw != m->ld || (off % (size_t)m->ld) != 0 || (nb > 1 && (g.strideW % m->ld) != 0)) return true;     // not a row view
+        g.wscale = m->scales + off / (size_t)m->ld; g.strideWs = nb > 1 ? g.strideW / m->ld : 0;
     }
-    if (!g.Wb || !gemm_h2_takes(g)) { g.Wb = nullptr; g.wplane = 0; g.wscale = nullptr; g.strideWs = 0; return 0; }
-    if (nb > 1) return 0;                                   // batched views: the kernel finds the row exponents itself
+    g.Wb = m->dst + off;
+    g.wplane = img->fp32_planes() ? (int64_t)img->bf16_cap : 0;
+    if (!(img->h2 ? gemm_h2_takes(g) : img->split ? gemm_x3_applicable(g) : gemm_bf16_applicable(g))) { g.Wb = nullptr; g.wplane = 0; g.wscale = nullptr; g.strideWs = 0; }
+    return true;
+}
+// Would the dispatcher run this trunk call on the kernel family `rule` asks about (gemm_rule_takes_*)?  The kernels that replace, split or fill such a
+// product carry that family's bits, so each reduced form is taken only where this says yes for the product and for its parts (rule_M: the full rows).
+static bool family_takes(bool (*rule)(const GemmArgs&), const d4_engine* img, GemmArgs g) {
+    trunk_call(img, g);
+    return rule(g);
+}
+
+// fp16x2 mode, a call gemm_h2.hip takes: the scale exponents of A's rows.  A residual-stream slab keeps them for the evaluation (computed once, by
+// the first GEMM that reads the slab), any other activation buffer gets them right here (row_scale_exp: one small launch)
+static int attach_row_exps(d4_engine* e, GemmArgs& g, hipStream_t s) {
+    if (!g.Wb || g.batch > 1) return 0;                     // (batched views: the kernel finds the row exponents itself)
     const size_t M = e->aexp_M;
     if (M > 0 && g.A >= e->slabs && g.A < e->slabs + (size_t)e->nslab * M * e->D && g.lda == e->D && g.K == e->D && ((size_t)(g.A - e->slabs) % (size_t)e->D) == 0) {
         const size_t row0 = (size_t)(g.A - e->slabs) / e->D;
@@ -510,44 +530,47 @@ static int attach_h2(d4_engine* e, GemmArgs& g, hipStream_t s) {
     return 0;
 }
 
-static int engine_gemm(GemmArgs& g, hipStream_t s) {
-    if (d4_engine* e = t_bf16) {
-        if (e->h2) {
-            if (int rc = attach_h2(e, g, s)) return rc;
-            return gemm(g, s);
-        }
-        g.Wb = nullptr;
-        for (const auto& m : e->mirrors)
-            if (g.W >= m.src && g.W < m.src + m.n) { g.Wb = m.dst + (g.W - m.src); break; }
-        D4_REQUIRE(g.Wb != nullptr, "bf16 engine: a trunk GEMM weight has no bf16 mirror (M=%d N=%d K=%d)", g.M, g.N, g.K);
-        if (e->split) {
-            g.wplane = (int64_t)e->bf16_cap;
-            if (!gemm_x3_applicable(g)) { g.Wb = nullptr; g.wplane = 0; }
-        } else
-        if (!gemm_bf16_applicable(g)) g.Wb = nullptr;       // e.g. K not a multiple of 32: this call stays on the fp32 kernel
-        if (!e->fp32_planes() && !e->shadows.empty()) {
-            // bf16 activation images: read A's when it has one (and the bf16-activation kernel takes the call), refresh C's either in the
-            // epilogue of that kernel or by a conversion pass after any other kernel
-            uint16_t* cb = (!g.C && g.Cb) ? g.Cb : e->shadow_of(g.C);     // (a caller may name a bf16-only output itself: the wide key projection)
-            g.Ab = g.Wb ? e->shadow_of(g.A) : nullptr;
-            if (g.Ab && !gemm_bf16a_applicable(g)) g.Ab = nullptr;
-            D4_REQUIRE(g.Ab || g.C, "bf16 engine: a GEMM (M=%d N=%d K=%d) with a bf16-only output cannot take the bf16-activation kernel", g.M, g.N, g.K);
-            D4_REQUIRE(g.Ab || !e->shadow_only(g.A), "bf16 engine: a GEMM (M=%d N=%d K=%d) reads a bf16-only activation buffer but cannot take the bf16-activation kernel", g.M, g.N, g.K);
-            if (g.Ab) {
-                g.Cb = cb;
-                if (cb && e->shadow_only(g.C) && !(g.flags & GEMM_ACCUMULATE)) g.C = nullptr;
-                return gemm(g, s);
-            }
-            if (int rc = gemm(g, s)) return rc;
-            if (!cb) return 0;
-            const int nb = g.batch > 1 ? g.batch : 1;
-            const int ncol = (g.flags & GEMM_SWIGLU) ? g.N / 2 : g.N;
-            if (nb == 1) return cvt_rows_bf16(g.C, g.ldc, cb, g.ldc, g.M, ncol, s);
-            for (int b = 0; b < nb; ++b)
-                if (int rc = cvt_rows_bf16(g.C + b * g.strideC, g.ldc, cb + b * g.strideC, g.ldc, g.M, ncol, s)) return rc;
-            return 0;
-        }
+// bf16 activation images (engine.h: shadows) of a call whose weight trunk_call attached: read A's when it has one and the bf16-activation kernel takes
+// the call; that kernel's epilogue then refreshes C's image (alone, where nothing reads the fp32 values).  *cb = C's image either way.
+static int attach_images(const d4_engine* e, GemmArgs& g, uint16_t** cb) {
+    *cb = (!g.C && g.Cb) ? g.Cb : e->shadow_of(g.C);     // (a caller may name a bf16-only output itself: the wide key projection)
+    g.Ab = g.Wb ? e->shadow_of(g.A) : nullptr;
+    if (g.Ab && !gemm_bf16a_applicable(g)) g.Ab = nullptr;
+    D4_REQUIRE(g.Ab || g.C, "bf16 engine: a GEMM (M=%d N=%d K=%d) with a bf16-only output cannot take the bf16-activation kernel", g.M, g.N, g.K);
+    D4_REQUIRE(g.Ab || !e->shadow_only(g.A), "bf16 engine: a GEMM (M=%d N=%d K=%d) reads a bf16-only activation buffer but cannot take the bf16-activation kernel", g.M, g.N, g.K);
+    if (!g.Ab) return 0;
+    g.Cb = *cb;
+    if (*cb && e->shadow_only(g.C) && !(g.flags & GEMM_ACCUMULATE)) g.C = nullptr;
+    return 0;
+}
+
+static int engine_gemm(const EvalCtx& cx, GemmArgs& g) {
+    d4_engine* e = cx.img;
+    hipStream_t s = cx.s;
+    const bool mirrored = trunk_call(e, g);
+    if (!e) return gemm(g, s);
+    if (e->h2) {              // (a matrix too narrow for the plane rows has no mirror: mirror_weight)
+        if (int rc = attach_row_exps(e, g, s)) return rc;
+        return gemm(g, s);
     }
+    D4_REQUIRE(mirrored, "bf16 engine: a trunk GEMM weight has no bf16 mirror (M=%d N=%d K=%d)", g.M, g.N, g.K);
+    if (e->split || e->shadows.empty()) return gemm(g, s);
+    uint16_t* cb;
+    if (int rc = attach_images(e, g, &cb)) return rc;
+    if (int rc = gemm(g, s)) return rc;
+    if (g.Ab || !cb) return 0;
+    // any other kernel: a conversion pass refreshes C's image
+    const int nb = g.batch > 1 ? g.batch : 1;
+    const int ncol = (g.flags & GEMM_SWIGLU) ? g.N / 2 : g.N;
+    for (int b = 0; b < nb; ++b)
+        if (int rc = cvt_rows_bf16(g.C + b * g.strideC, g.ldc, cb + b * g.strideC, g.ldc, g.M, ncol, s)) return rc;
+    return 0;
+}
+
+// a product that stays on plain fp32 whatever the engine's mode: heads, learner, and prepare before the mirrors exist
+static int gemm_fp32(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
+                     int flags, const float* bias, const float* R, int ldr, hipStream_t s) {
+    GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, RMS_EPS};
     return gemm(g, s);
 }
 
@@ -562,62 +585,41 @@ static int prep_ff(const FfW& f, FfPrep& p, d4_engine* e, hipStream_t s) {
     return pad_cols(f.out_w, p.w2, e->D, e->inner, e->inner_pad, s);
 }
 
-static int gemm_simple(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                       int flags, const float* bias, const float* R, int ldr, hipStream_t s) {
+static int gemm_simple(const EvalCtx& cx, const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
+                       int flags, const float* bias, const float* R, int ldr) {
     GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, RMS_EPS};
-    return engine_gemm(g, s);
+    return engine_gemm(cx, g);
 }
 
 // Two independent projections of equal K: one launch when both are few-row problems (fp32 engine), else one after the other.
-static int gemm_two(GemmArgs a, GemmArgs b, hipStream_t s) {
-    if ((!t_bf16 || t_bf16->fp32_planes()) && gemm_skinny_pair_applicable(a, b)) return gemm_skinny_pair(a, b, s);
-    if (t_bf16 && t_bf16->h2) {
-        // fp16x2 mode: each call by the rule (the key projection of many rows on gemm_h2.hip, the small query projection on the f32-input kernels)
-        int rc;
-        if ((rc = engine_gemm(a, s))) return rc;
-        return engine_gemm(b, s);
+static int gemm_two(const EvalCtx& cx, GemmArgs a, GemmArgs b) {
+    d4_engine* e = cx.img;
+    if ((!e || e->fp32_planes()) && gemm_skinny_pair_applicable(a, b)) return gemm_skinny_pair(a, b, cx.s);
+    if (!e || e->split) {
+        // fp32 engine: one grid for both when the dispatcher's pair form applies (gemm_pair falls back to two launches itself).  A weight without
+        // a mirror (the last layer's regrouped image) is a plain f32-input call here, as it is to the gemm_rule_takes_* questions
+        trunk_call(e, a); trunk_call(e, b);
+        return gemm_pair(a, b, cx.s);
     }
-    if (!t_bf16 || t_bf16->split) {
-        // fp32 engine: one grid for both when the dispatcher's pair form applies (gemm_pair falls back to two launches itself)
-        if (d4_engine* e = t_bf16) {
-            for (GemmArgs* g : {&a, &b}) {
-                g->Wb = nullptr;
-                for (const auto& m : e->mirrors)
-                    if (g->W >= m.src && g->W < m.src + m.n) { g->Wb = m.dst + (g->W - m.src); break; }
-                g->wplane = g->Wb ? (int64_t)e->bf16_cap : 0;
-                if (!g->Wb || !gemm_x3_applicable(*g)) { g->Wb = nullptr; g->wplane = 0; }
-            }
-        }
-        return gemm_pair(a, b, s);
+    // bf16 engine: both activations have bf16 images and the bf16-activation kernel takes both calls -> one grid (the pool's query projection rides
+    // in the key projection's launch).  fp16x2 mode: each call by the rule (the key projection of many rows on gemm_h2.hip, the small query projection on the f32-input kernels)
+    if (!e->h2 && !e->shadows.empty()) {
+        GemmArgs pa = a, pb = b;
+        uint16_t* cb;
+        trunk_call(e, pa); trunk_call(e, pb);
+        if (int rc = attach_images(e, pa, &cb)) return rc;
+        if (int rc = attach_images(e, pb, &cb)) return rc;
+        if (pa.Ab && pb.Ab && gemm_bf16a_pair_applicable(pa, pb)) return gemm_bf16a_pair(pa, pb, cx.s);
     }
-    // bf16 engine: both activations have bf16 images and neither output has one -> one grid on the bf16-activation kernel (the pool's query
-    // projection rides in the key projection's launch)
-    if (d4_engine* e = t_bf16) {
-        if (!e->fp32_planes() && !e->shadows.empty()) {
-            GemmArgs pa = a, pb = b;
-            bool ok = true;
-            for (GemmArgs* g : {&pa, &pb}) {
-                g->Wb = nullptr;
-                for (const auto& m : e->mirrors)
-                    if (g->W >= m.src && g->W < m.src + m.n) { g->Wb = m.dst + (g->W - m.src); break; }
-                g->Ab = e->shadow_of(g->A);
-                ok = ok && g->Wb && g->Ab;
-                g->Cb = e->shadow_of(g->C);                                   // an output with an image: written by the same epilogue,
-                if (g->Cb && e->shadow_only(g->C)) g->C = nullptr;            // ... alone when nothing reads the fp32 values (the pools' keys)
-            }
-            if (ok && gemm_bf16a_pair_applicable(pa, pb)) return gemm_bf16a_pair(pa, pb, s);
-        }
-    }
-    int rc;
-    if ((rc = engine_gemm(a, s))) return rc;
-    return engine_gemm(b, s);
+    if (int rc = engine_gemm(cx, a)) return rc;
+    return engine_gemm(cx, b);
 }
 
-static int gemm_c2(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K, int flags,
-                   const float* bias, const float* R, int ldr, float* C2, int S, int ns, int has_agent, hipStream_t s) {
+static int gemm_c2(const EvalCtx& cx, const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K, int flags,
+                   const float* bias, const float* R, int ldr, float* C2, int S, int has_agent) {
     GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, RMS_EPS, 0};
-    g.C2 = C2; g.ldc2 = N; g.c2_S = S; g.c2_lo = t_keep_lo; g.c2_hi = t_keep_lo + ns; g.c2_last = has_agent;
-    return engine_gemm(g, s);
+    g.C2 = C2; g.ldc2 = N; g.c2_S = S; g.c2_lo = cx.keep_lo; g.c2_hi = cx.keep_hi; g.c2_last = has_agent;
+    return engine_gemm(cx, g);
 }
 
 int engine_prepare(d4_engine* e, hipStream_t s) {
@@ -692,7 +694,7 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
             }
             float* out = last ? e->pos_emb : other;
             const int act = (!last && !m.post_norm(i)) ? GEMM_SILU : 0;
-            if ((rc = gemm_simple(lin_in, ld_in, w, ld_in, out, dout, P, dout, ld_in, act, m.b[i], nullptr, 0, s))) return rc;
+            if ((rc = gemm_fp32(lin_in, ld_in, w, ld_in, out, dout, P, dout, ld_in, act, m.b[i], nullptr, 0, s))) return rc;
             if (m.post_norm(i) && (rc = layernorm_rows(out, dout, m.g[i], m.nb[i], out, dout, P, dout, 1e-5f, 1, s))) return rc;
             other = cur; cur = out;
         }
@@ -723,17 +725,17 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
     if ((rc = fold_rows(e->lq_in.to_k, e->lq_in.norm_ctx, e->lin_kv_w, hd, dl, dl, s))) return rc;
     if ((rc = fold_rows(e->lq_in.to_v, e->lq_in.norm_ctx, e->lin_kv_w + (size_t)hd * dl, hd, dl, dl, s))) return rc;
     if ((rc = rmsnorm_rows(e->lq_in_queries, D, e->lq_in.norm, e->qtmp, D, ns, D, RMS_EPS, s))) return rc;
-    if ((rc = gemm_simple(e->qtmp, D, e->lq_in.to_q, D, e->lin_q, hd, ns, hd, D, 0, nullptr, nullptr, 0, s))) return rc;
-    if ((rc = gemm_simple(e->qtmp, D, e->lq_in.to_gates, D, e->lin_gate, h, ns, h, D, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_fp32(e->qtmp, D, e->lq_in.to_q, D, e->lin_q, hd, ns, hd, D, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_fp32(e->qtmp, D, e->lq_in.to_gates, D, e->lin_gate, h, ns, h, D, 0, nullptr, nullptr, 0, s))) return rc;
     // to_latent_pred: both norms are applied explicitly on the gathered rows -> plain K/V weights
     if ((rc = fold_rows(e->lq_out.to_k, nullptr, e->lout_kv_w, hd, D, D, s))) return rc;
     if ((rc = fold_rows(e->lq_out.to_v, nullptr, e->lout_kv_w + (size_t)hd * D, hd, D, D, s))) return rc;
     if ((rc = rmsnorm_rows(e->lq_out_queries, D, e->lq_out.norm, e->qtmp, D, n, D, RMS_EPS, s))) return rc;
-    if ((rc = gemm_simple(e->qtmp, D, e->lq_out.to_q, D, e->lout_q, hd, n, hd, D, 0, nullptr, nullptr, 0, s))) return rc;
-    if ((rc = gemm_simple(e->qtmp, D, e->lq_out.to_gates, D, e->lout_gate, h, n, h, D, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_fp32(e->qtmp, D, e->lq_out.to_q, D, e->lout_q, hd, n, hd, D, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_fp32(e->qtmp, D, e->lq_out.to_gates, D, e->lout_gate, h, n, h, D, 0, nullptr, nullptr, 0, s))) return rc;
     // the pool's output projection and the latent Linear are back-to-back linear maps with nothing in between
     // (D4:2068, 4833): fold them, W[dl][hd] = W_latent[dl][D] . W_out[D][hd]
-    if ((rc = gemm_simple(e->latent_w, D, e->lq_out.to_out, hd, e->lout_w, hd, dl, hd, D, GEMM_TRANS_B, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_fp32(e->latent_w, D, e->lq_out.to_out, hd, e->lout_w, hd, dl, hd, D, GEMM_TRANS_B, nullptr, nullptr, 0, s))) return rc;
     }
 
     // ---- bf16 mirrors of everything the trunk's GEMMs read (prepared images above + the raw output projections)
@@ -776,20 +778,13 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
     e->l0_ready = e->ck_ready = false;
     if (e->c0_proj || e->ck) {
         const int nr = c.num_register_tokens, lo = 1 + ns, pin = 4096;
-        t_bf16 = e->bf16 ? e : nullptr;
-        auto planes = [e](GemmArgs g) {                      // the call as engine_gemm hands it to gemm()
-            if (e->bf16)
-                for (const auto& m : e->mirrors)
-                    if (g.W >= m.src && g.W < m.src + m.n) { g.Wb = m.dst + (g.W - m.src); break; }
-            if (g.Wb && e->split) { g.wplane = (int64_t)e->bf16_cap; if (!gemm_x3_applicable(g)) { g.Wb = nullptr; g.wplane = 0; } }
-            return g;
-        };
+        const EvalCtx cx{e->bf16 ? e : nullptr, s};
         rc = 0;
         if (e->c0_proj) {
             GemmArgs g{e->registers, D, e->proj_w[0], D, e->c0_proj, e->Nproj0, e->proj_b[0], nullptr, 0, nr, e->Nproj0, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             g.rule_M = pin;
-            if (gemm_rule_takes_x3sk(planes(g))) {
-                rc = engine_gemm(g, s);
+            if (family_takes(gemm_rule_takes_x3sk, cx.img, g)) {
+                rc = engine_gemm(cx, g);
                 for (int ly = 0; ly < 2 && !rc; ++ly) {
                     const int Sl = e->S - 1 + ly;
                     rc = copy_rows(e->c0_proj, 0, e->proj0r[ly] + (size_t)lo * e->Nproj0, Sl * e->Nproj0, e->Fr, nr * e->Nproj0, s);
@@ -798,16 +793,16 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
             }
         }
         if (!rc && e->ck && e->pkv_stride > 0) {
+            auto key_block = [&](int p) {
+                GemmArgs g{e->registers, D, e->pkv_w[p], D, e->ck + (size_t)p * nr * hp, hp, nullptr, nullptr, 0, nr, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
+                g.rule_M = pin;
+                return g;
+            };
             bool ok = true;
-            for (int p = 0; p < c.depth - 1; ++p) {
-                GemmArgs g{e->registers, D, e->pkv_w[p], D, e->ck + (size_t)p * nr * hp, hp, nullptr, nullptr, 0, nr, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
-                g.rule_M = pin;
-                ok = ok && gemm_rule_takes_v2(planes(g));
-            }
+            for (int p = 0; p < c.depth - 1; ++p) ok = ok && family_takes(gemm_rule_takes_v2, cx.img, key_block(p));
             for (int p = 0; ok && p < c.depth - 1 && !rc; ++p) {
-                GemmArgs g{e->registers, D, e->pkv_w[p], D, e->ck + (size_t)p * nr * hp, hp, nullptr, nullptr, 0, nr, hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
-                g.rule_M = pin;
-                rc = engine_gemm(g, s);
+                GemmArgs g = key_block(p);
+                rc = engine_gemm(cx, g);
                 for (int ly = 0; ly < 2 && !rc; ++ly) {
                     const int Sl = e->S - 1 + ly;
                     rc = copy_rows(e->ck + (size_t)p * nr * hp, 0, e->kvr[ly] + (size_t)p * e->kvr_stride[ly] + (size_t)lo * hp, Sl * hp, e->Fr, nr * hp, s);
@@ -815,7 +810,6 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
             }
             e->ck_ready = ok && !rc;
         }
-        t_bf16 = nullptr;
         if (rc) return rc;
     }
 
@@ -830,33 +824,27 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------- forward
-// A feedforward's input projection as ff_block makes it and as engine_gemm hands it to gemm() on a split-operand engine (the weight's three planes)
-static GemmArgs ff_in_call(d4_engine* e, const FfPrep& fp, const float* x, int ldx, int rows) {
-    GemmArgs g1{x, ldx, fp.w1, e->D, e->ffh, e->inner_pad, fp.b1, nullptr, 0, rows, 2 * e->inner_pad, e->D,
-                GEMM_RMS_ROWSCALE | GEMM_SWIGLU, RMS_EPS, 2.0 * rows * (2.0 * e->inner) * e->D};
-    if (e->bf16 && e->split) {
-        for (const auto& m : e->mirrors)
-            if (g1.W >= m.src && g1.W < m.src + m.n) { g1.Wb = m.dst + (g1.W - m.src); break; }
-        if (g1.Wb) { g1.wplane = (int64_t)e->bf16_cap; if (!gemm_x3_applicable(g1)) { g1.Wb = nullptr; g1.wplane = 0; } }
-    }
-    return g1;
+// A feedforward's input projection as ff_block makes it (engine_forward_impl asks the dispatcher about the same call before it hands ff_block a fill)
+static GemmArgs ff_in_call(const d4_engine* e, const FfPrep& fp, const float* x, int ldx, int rows) {
+    return GemmArgs{x, ldx, fp.w1, e->D, e->ffh, e->inner_pad, fp.b1, nullptr, 0, rows, 2 * e->inner_pad, e->D,
+                    GEMM_RMS_ROWSCALE | GEMM_SWIGLU, RMS_EPS, 2.0 * rows * (2.0 * e->inner) * e->D};
 }
 
 // fill (ff_fill_pool_keys; engine_forward_impl has checked the rules): the input projection runs as the filled form of the persistent kernel and carries
 // the first rows of the next pool's key problem on the workgroups its last round leaves idle
-static int ff_block(d4_engine* e, const FfPrep& fp, const float* out_b, const float* x, int ldx, float* y, int ldy,
-                    int rows, hipStream_t s, float* y_compact = nullptr, int S = 0, int has_agent = 1, const GemmArgs* fill = nullptr) {
+static int ff_block(const EvalCtx& cx, d4_engine* e, const FfPrep& fp, const float* out_b, const float* x, int ldx, float* y, int ldy,
+                    int rows, float* y_compact = nullptr, int S = 0, int has_agent = 1, const GemmArgs* fill = nullptr) {
     int rc;
-    GemmArgs g1{x, ldx, fp.w1, e->D, e->ffh, e->inner_pad, fp.b1, nullptr, 0, rows, 2 * e->inner_pad, e->D,
-                GEMM_RMS_ROWSCALE | GEMM_SWIGLU, RMS_EPS, 2.0 * rows * (2.0 * e->inner) * e->D};
+    GemmArgs g1 = ff_in_call(e, fp, x, ldx, rows);
     if (fill) {
-        if ((rc = gemm_x3sk_fill(ff_in_call(e, fp, x, ldx, rows), *fill, gemm_x3sk_fill_tiles(*fill), s))) return rc;
+        trunk_call(cx.img, g1);
+        if ((rc = gemm_x3sk_fill(g1, *fill, gemm_x3sk_fill_tiles(*fill), cx.s))) return rc;
     } else
-    if ((rc = engine_gemm(g1, s))) return rc;
+    if ((rc = engine_gemm(cx, g1))) return rc;
     GemmArgs g2{e->ffh, e->inner_pad, fp.w2, e->inner_pad, y, ldy, out_b, x, ldx, rows, e->D, e->inner_pad, 0, RMS_EPS,
                 2.0 * rows * (double)e->D * e->inner};
-    if (y_compact) { g2.C2 = y_compact; g2.ldc2 = e->D; g2.c2_S = S; g2.c2_lo = t_keep_lo; g2.c2_hi = t_keep_hi; g2.c2_last = has_agent; }
-    return engine_gemm(g2, s);
+    if (y_compact) { g2.C2 = y_compact; g2.ldc2 = e->D; g2.c2_S = S; g2.c2_lo = cx.keep_lo; g2.c2_hi = cx.keep_hi; g2.c2_last = has_agent; }
+    return engine_gemm(cx, g2);
 }
 
 int g_pool_wide_keys = 1;             // test hook d4_debug_switch("pool_wide_keys")
@@ -883,7 +871,7 @@ static GemmArgs pool_key_call(d4_engine* e, int p, const float* hiddens, int L, 
 
 // rule_M > 0 (the final pool of an evaluation that keeps the agent row alone): the rows the same pool has when the spatial rows are kept too — every
 // product and the mix are dispatched as for that row count (GemmArgs::rule_M), so the rows computed carry the bits they have there
-static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int M, hipStream_t s, const float* hiddens = nullptr,
+static int pool_block(const EvalCtx& cx, d4_engine* e, int p, const float* x, float* y, int L, int M, const float* hiddens = nullptr,
                       float* y_compact = nullptr, int S = 0, int has_agent = 1, int rule_M = 0, float* keys0 = nullptr, int keys_done = 0) {
     // keys0 (an in-loop pool of an evaluation that takes the constant register rows): the pool's keys [L][M][hp] with slab 0's block already in place
     // (prefilled register rows + the evaluation's batched launch) — the key problem covers slabs 1 .. L - 1, pinned to the family of all L
@@ -893,8 +881,9 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
     const d4_config& c = e->c;
     const int D = e->D, hp = e->hp;
     const AttnW& a = e->pools[p];
+    hipStream_t s = cx.s;
     int rc;
-    const bool mix_path = c.pool_heads == 4 && D <= 1024;
+    const bool mix_path = e->pool_mix_path();
     // (mix path: the head-gate logits are computed inside pool_mix; hp = 256 columns are exactly two / four tile columns)
     GemmArgs gq{x, D, e->pq_w[p], D, e->pool_q, e->ldpq, nullptr, nullptr, 0, M, mix_path ? hp : hp + e->php, D, GEMM_RMS_ROWSCALE, RMS_EPS};
     gq.rule_M = rule_M;
@@ -904,7 +893,7 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
         // key weights of this and every later pool plus this pool's query weights — one launch of N = (depth - p) * 256 per pool instead of a query
         // launch and a key launch of L M rows x 256 (every hidden re-read by every pool: quadratic in depth).  Same products, same row scales
         // (1 / rms of the hidden; both norms' gammas are folded into the weight rows); the queries become bf16 like the keys.
-        const bool wide = g_pool_wide_keys && t_bf16 && e->kall_b && hiddens == e->slabs && p < c.depth - 1 && L == 2 * p + 3 && x == e->slabs + (size_t)(L - 1) * M * D;
+        const bool wide = g_pool_wide_keys && cx.img && e->kall_b && hiddens == e->slabs && p < c.depth - 1 && L == 2 * p + 3 && x == e->slabs + (size_t)(L - 1) * M * D;
         PoolMixArgs pm{};
         pm.q = e->pool_q; pm.ldq = e->ldpq; pm.k = e->pool_kv; pm.ldk = hp;
         if (wide) {
@@ -912,38 +901,38 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
             GemmArgs gw{hiddens + (size_t)j0 * M * D, D, e->pkq_w[p], D, nullptr, ld, nullptr, nullptr, 0, (L - j0) * M, (c.depth - p) * hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             gw.algo_flops = 2.0 * M * hp * (double)D * ((double)(L - j0) * (c.depth - 1 - p) + 1.0);       // (the query columns of the other slabs are not wanted)
             gw.Cb = e->kall_b + (size_t)j0 * M * ld + (size_t)p * hp;
-            if ((rc = engine_gemm(gw, s))) return rc;
+            if ((rc = engine_gemm(cx, gw))) return rc;
             pm.k = nullptr; pm.k_b = e->kall_b + (size_t)p * hp; pm.ldk = ld;
             pm.q = nullptr; pm.q_b = e->kall_b + (size_t)(L - 1) * M * ld + (size_t)(c.depth - 1) * hp; pm.ldq = ld;
         } else {
         GemmArgs gk = pool_key_call(e, p, hiddens, L, M, rule_M, keys0);
         if (keys0) pm.k = keys0;
         if (keys_done > 0) { gk.A += (size_t)keys_done * D; gk.C += (size_t)keys_done * hp; gk.M -= keys_done; gk.rule_M = L * M; }
-        if ((rc = gemm_two(gq, gk, s))) return rc;
-        if (t_bf16) pm.k_b = t_bf16->shadow_of(e->pool_kv);               // bf16 keys (the only copy of them in this mode)
+        if ((rc = gemm_two(cx, gq, gk))) return rc;
+        if (cx.img) pm.k_b = cx.img->shadow_of(e->pool_kv);               // bf16 keys (the only copy of them in this mode)
         }
         pm.x = x; pm.ldx = D; pm.gate_w = e->pq_w[p] + (size_t)hp * D; pm.hid = hiddens; pm.D = D; pm.k_gamma = a.k_gamma;
         pm.u = e->pool_u; pm.M = M; pm.L = L; pm.heads = c.pool_heads; pm.eps = RMS_EPS; pm.rule_M = rule_M;
-        if (t_bf16 && D > 512) pm.hid_b = t_bf16->shadow_of(hiddens);     // (D <= 512 may take the block-per-row form, which reads fp32)
-        if (t_bf16) if (uint16_t* ub = t_bf16->shadow_of(e->pool_u)) { pm.u_b = ub; if (t_bf16->shadow_only(e->pool_u)) pm.u = nullptr; }   // only the value GEMM reads the mixes
+        if (cx.img && D > 512) pm.hid_b = cx.img->shadow_of(hiddens);     // (D <= 512 may take the block-per-row form, which reads fp32)
+        if (cx.img) if (uint16_t* ub = cx.img->shadow_of(e->pool_u)) { pm.u_b = ub; if (cx.img->shadow_only(e->pool_u)) pm.u = nullptr; }   // only the value GEMM reads the mixes
         // per-frame fused form (mix -> value projection -> output projection + residual in one kernel) where a frame per workgroup fills the chip;
         // frame_fused mode 2 (test hook): the mix stays its own kernel and only the tail is fused
         // more than 64 hiddens (deep trunks): the chunked mix, always as its own kernel — the per-frame fused mix stays at L <= 64, its tail does not
         // depend on L (test hook g_pool_mix_deep: the pools of <= 64 hiddens take the chunked kernel too)
         const bool deep = L > 64 || g_pool_mix_deep;
-        if (S > 0 && M % S == 0 && !e->pv_t.empty() && (!t_bf16 || t_bf16->fp32_planes()) && frame_pool_tail_applicable(M / S, S, D, c.pool_heads)) {
+        if (S > 0 && M % S == 0 && !e->pv_t.empty() && (!cx.img || cx.img->fp32_planes()) && frame_pool_tail_applicable(M / S, S, D, c.pool_heads)) {
             const bool tail_only = deep || frame_fused_mode() == 2;
-            if (!tail_only) return frame_pool(pm, e->pv_t[p], e->po_t[p], M / S, S, x, D, y, D, y_compact, D, t_keep_lo, t_keep_hi, has_agent, s);
+            if (!tail_only) return frame_pool(pm, e->pv_t[p], e->po_t[p], M / S, S, x, D, y, D, y_compact, D, cx.keep_lo, cx.keep_hi, has_agent, s);
             if ((rc = deep ? pool_mix_deep(pm, s) : pool_mix(pm, s))) return rc;
-            return frame_pool_tail(e->pool_u, e->pv_t[p], e->po_t[p], M / S, S, D, c.pool_heads, x, D, y, D, y_compact, D, t_keep_lo, t_keep_hi, has_agent, s);
+            return frame_pool_tail(e->pool_u, e->pv_t[p], e->po_t[p], M / S, S, D, c.pool_heads, x, D, y, D, y_compact, D, cx.keep_lo, cx.keep_hi, has_agent, s);
         }
         if ((rc = deep ? pool_mix_deep(pm, s) : pool_mix(pm, s))) return rc;
         GemmArgs gv{e->pool_u, c.pool_heads * D, e->pkv_w[p] + (size_t)hp * D, D, e->pool_att, hp, nullptr, nullptr, 0, M, 64, D, 0, RMS_EPS};
         gv.batch = c.pool_heads; gv.strideA = D; gv.strideW = (int64_t)64 * D; gv.strideC = 64; gv.rule_M = rule_M;
-        if ((rc = engine_gemm(gv, s))) return rc;
+        if ((rc = engine_gemm(cx, gv))) return rc;
     } else {
     const GemmArgs gkv{hiddens, D, e->pkv_w[p], D, e->pool_kv, 2 * hp, nullptr, nullptr, 0, L * M, 2 * hp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
-    if ((rc = gemm_two(gq, gkv, s))) return rc;
+    if ((rc = gemm_two(cx, gq, gkv))) return rc;
     SmallAttnArgs sa{};
     sa.q = e->pool_q; sa.q_group_stride = e->ldpq; sa.q_item_stride = 0;
     sa.k = e->pool_kv; sa.k_group_stride = 2 * hp; sa.k_item_stride = (int64_t)M * 2 * hp;
@@ -952,14 +941,14 @@ static int pool_block(d4_engine* e, int p, const float* x, float* y, int L, int 
     sa.k_gamma = a.k_gamma;
     sa.out = e->pool_att; sa.o_group_stride = hp; sa.o_item_stride = 0;
     sa.groups = M; sa.heads = c.pool_heads; sa.nq = 1; sa.nk = L;
-    sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
-    sa.out_b = t_bf16 ? t_bf16->shadow_of(e->pool_att) : nullptr;
+    sa.wide = e->attn_wide();
+    sa.out_b = cx.img ? cx.img->shadow_of(e->pool_att) : nullptr;
     if ((rc = small_attn(sa, s))) return rc;
     }
-    if (y_compact) return gemm_c2(e->pool_att, hp, a.to_out, hp, y, D, M, D, hp, 0, nullptr, x, D, y_compact, S, t_keep_hi - t_keep_lo, has_agent, s);
+    if (y_compact) return gemm_c2(cx, e->pool_att, hp, a.to_out, hp, y, D, M, D, hp, 0, nullptr, x, D, y_compact, S, has_agent);
     GemmArgs go{e->pool_att, hp, a.to_out, hp, y, D, nullptr, x, D, M, D, hp, 0, RMS_EPS};
     go.rule_M = rule_M;
-    return engine_gemm(go, s);
+    return engine_gemm(cx, go);
 }
 
 // Inputs expected in e->sig / e->pact (device).  Results: e->pred [B*Tq][n][dl], e->xfc [B*Tq][ns+1][D] (agent = row ns;
@@ -969,30 +958,28 @@ void engine_drop_graphs(d4_engine* e) {
     e->graphs.clear();
 }
 
-static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                               const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred, bool agent_only);
+static int engine_forward_impl(const EvalCtx& cx, d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
+                               const int64_t* tasks, bool need_agent, const int* t0_dev, bool need_pred, bool agent_only);
 
 // The engines whose clean evaluation can keep the agent row alone: the final pool's products are then pinned (GemmArgs::rule_M) to the kernel
 // family they have with the spatial rows present, which the f32-input families and the pool's mix path provide (row-count rules by shape only, every
 // configuration of a family the same bits).  The bf16-image and fp16x2 engines, pools of other than 4 heads and dim > 1024 keep the ns + 1 rows.
 bool engine_clean_agent_only(const d4_engine* e) {
-    return !e->encoder && !e->decoder && (!e->bf16 || e->split) && e->c.pool_heads == 4 && e->D <= 1024;
+    return !e->encoder && !e->decoder && (!e->bf16 || e->split) && e->pool_mix_path();
 }
 
 int engine_forward(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred) {
-    t_bf16 = e->bf16 ? e : nullptr;           // the trunk's GEMMs below pick their bf16 weight mirrors; heads and learner stay fp32
+                   const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred, int sig_uniform) {
     need_pred = need_pred || !need_agent || e->encoder || e->decoder;
     const bool agent_only = !need_pred && engine_clean_agent_only(e);
-    t_keep_lo = e->keep_lo;
-    t_keep_hi = agent_only ? e->keep_lo : e->keep_hi;
-    const int rc = engine_forward_impl(e, latents, B, Tq, t0, step_log2, tasks, need_agent, s, t0_dev, need_pred, agent_only);
-    t_bf16 = nullptr;
-    return rc;
+    // the trunk's GEMMs below read their weights' mirrors where the engine has them
+    const EvalCtx cx{e->bf16 ? e : nullptr, s, e->keep_lo, agent_only ? e->keep_lo : e->keep_hi, sig_uniform};
+    return engine_forward_impl(cx, e, latents, B, Tq, t0, step_log2, tasks, need_agent, t0_dev, need_pred, agent_only);
 }
 
-static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
-                               const int64_t* tasks, bool need_agent, hipStream_t s, const int* t0_dev, bool need_pred, bool agent_only) {
+static int engine_forward_impl(const EvalCtx& cx, d4_engine* e, const float* latents, int B, int Tq, int t0, int step_log2,
+                               const int64_t* tasks, bool need_agent, const int* t0_dev, bool need_pred, bool agent_only) {
+    hipStream_t s = cx.s;
     const d4_config& c = e->c;
     D4_REQUIRE(e->prepared, "engine not prepared");
     D4_REQUIRE(B >= 1 && B <= e->maxB, "batch %d exceeds max_batch %d", B, e->maxB);
@@ -1007,41 +994,26 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     const int Fr = B * Tq, M = Fr * S;
     const bool denoise_only = !need_agent && !e->encoder && !e->decoder;        // dynamics evaluation whose last layer only feeds the spatial rows
     const bool fp32_engine = !e->bf16 || e->split;                              // every product of the latent ends on the f32-input kernels
-    // Would the dispatcher run this product of the evaluation on the LDS-DMA family (gemm2.hip)?  The kernels that replace or split such a product carry
-    // that family's bits.  The call is described as engine_gemm hands it to gemm(): its flags, rule_M and, on a split-operand engine, the weight's planes.
-    auto tiled_family = [e](int M_, int N_, int K_, int flags, const float* W, int rule_M = 0) {
+    // Would the dispatcher run this product of the evaluation on the family `rule` asks about — v2: the LDS-DMA family (gemm2.hip), x3sk: the persistent
+    // split-operand kernel?  The call is described as engine_gemm makes it: its flags, rule_M and the weight's mirror (family_takes).
+    constexpr auto v2 = gemm_rule_takes_v2, x3sk = gemm_rule_takes_x3sk;
+    auto takes = [&cx](bool (*rule)(const GemmArgs&), int M_, int N_, int K_, int flags, const float* W, int rule_M = 0) {
         GemmArgs g{};
         g.M = M_; g.N = N_; g.K = K_; g.lda = K_; g.ldw = K_; g.ldc = N_; g.flags = flags; g.rms_eps = RMS_EPS; g.rule_M = rule_M; g.W = W;
-        if (e->bf16) {
-            for (const auto& m : e->mirrors)
-                if (W >= m.src && W < m.src + m.n) { g.Wb = m.dst + (W - m.src); break; }
-            if (g.Wb && e->split) { g.wplane = (int64_t)e->bf16_cap; if (!gemm_x3_applicable(g)) { g.Wb = nullptr; g.wplane = 0; } }
-        }
-        return gemm_rule_takes_v2(g);
+        return family_takes(rule, cx.img, g);
     };
     // The register rows of slab 0 (rows [1 + ns, 1 + ns + nr) of every frame) are the parameter `registers`: their share of layer 0's projection and of
     // the in-loop pools' keys was computed at prepare.  Each reduced form is taken only where the full product AND its reduced parts run on the family
     // the constant block was made by, by the dispatcher's own rule on the calls as they are made (rule_M = the full row count).
     const int nr = c.num_register_tokens, Sc = S - nr, reg_lo = 1 + ns, ly = has_agent;
-    auto x3sk_family = [e](int M_, int N_, int K_, int flags, const float* W, int rule_M = 0) {
-        GemmArgs g{};
-        g.M = M_; g.N = N_; g.K = K_; g.lda = K_; g.ldw = K_; g.ldc = N_; g.flags = flags; g.rms_eps = RMS_EPS; g.rule_M = rule_M; g.W = W;
-        if (!e->split) return false;
-        for (const auto& m : e->mirrors)
-            if (W >= m.src && W < m.src + m.n) { g.Wb = m.dst + (W - m.src); break; }
-        if (!g.Wb) return false;
-        g.wplane = (int64_t)e->bf16_cap;
-        if (!gemm_x3_applicable(g)) return false;
-        return gemm_rule_takes_x3sk(g);
-    };
     const bool dynamics = !e->encoder && !e->decoder;
     const bool l0_const = g_layer0_const_rows && dynamics && e->l0_ready && Sc >= 1 &&
-                          x3sk_family(M, e->Nproj0, D, GEMM_RMS_ROWSCALE, e->proj_w[0]) && x3sk_family(Fr * Sc, e->Nproj0, D, GEMM_RMS_ROWSCALE, e->proj_w[0], M);
+                          takes(x3sk, M, e->Nproj0, D, GEMM_RMS_ROWSCALE, e->proj_w[0]) && takes(x3sk, Fr * Sc, e->Nproj0, D, GEMM_RMS_ROWSCALE, e->proj_w[0], M);
     bool ck_const = g_pool_const_keys && dynamics && e->ck_ready && Sc >= 1 && c.depth >= 2;
     for (int p = 0; ck_const && p < c.depth - 1; ++p) {
         const int L = 2 * p + 3;
-        ck_const = tiled_family(L * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p]) && tiled_family((L - 1) * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p], L * M) &&
-                   tiled_family(Fr * Sc, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p], 3 * M);
+        ck_const = takes(v2, L * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p]) && takes(v2, (L - 1) * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p], L * M) &&
+                   takes(v2, Fr * Sc, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[p], 3 * M);
     }
     float* P0 = l0_const ? e->proj0r[ly] : e->proj0;          // layer 0's projection of this evaluation (the same layout either way)
     auto keys0 = [&](int p) { return ck_const ? e->kvr[ly] + (size_t)p * e->kvr_stride[ly] + (size_t)e->Fr * S * e->hp - (size_t)M * e->hp : nullptr; };
@@ -1060,28 +1032,28 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
     if (e->encoder) {
         // tokens = [patch tokens of the video | learned latent tokens] (D4:4307, 4361-4376); patch rows were laid out in e->dec_in
         const int P = e->P, dp = e->dim_patch;
-        if ((rc = gemm_simple(e->dec_in, dp, e->ptt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->ptt_b, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, e->dec_in, dp, e->ptt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->ptt_b, nullptr, 0))) return rc;
         if ((rc = layernorm_rows(e->img_tok, D, e->ptt_ln, nullptr, e->img_tok, D, Fr * P, D, 1e-5f, 0, s))) return rc;
         if ((rc = encoder_pack_tokens(slab0, e->cslabs, e->img_tok, e->latent_tokens, Fr, P, n, D, s))) return rc;
     } else if (e->decoder) {
         // tokens = [pos_emb + patch tokens of the noised video | latent tokens] (D4:3625-3654); `latents` here are the latent TOKENS
         // input row-major [Fr][n][dl]; the noised video's patch rows were laid out in e->dec_in by d4_decoder_forward
         const int P = e->P, dp = e->dim_patch;
-        if ((rc = gemm_simple(e->dec_in, dp, e->npt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->npt_b, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, e->dec_in, dp, e->npt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->npt_b, nullptr, 0))) return rc;
         if ((rc = layernorm_rows(e->img_tok, D, e->npt_ln, nullptr, e->img_tok, D, Fr * P, D, 1e-5f, 0, s))) return rc;
-        if ((rc = gemm_simple(latents, dl, e->ld_w, dl, e->lat_tok, D, Fr * n, D, dl, 0, e->time_embed + (size_t)step_log2 * D, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, latents, dl, e->ld_w, dl, e->lat_tok, D, Fr * n, D, dl, 0, e->time_embed + (size_t)step_log2 * D, nullptr, 0))) return rc;
         if ((rc = decoder_pack_tokens(slab0, e->cslabs, e->pos_emb, e->img_tok, e->lat_tok, Fr, P, n - 1, n, D, s))) return rc;
     } else {
     // ---- latents -> spatial tokens (LearnedQueriesAttentionPool, D4:7168; a plain Linear when there is one per latent)
     if (same_len) {
-        if ((rc = gemm_simple(latents, dl, e->lin_w, dl, e->space, D, Fr * n, D, dl, 0, e->lin_b, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, latents, dl, e->lin_w, dl, e->space, D, Fr * n, D, dl, 0, e->lin_b, nullptr, 0))) return rc;
     } else if (g_lqap_in_fused && fp32_engine && !g_small_attn_wide && lqap_in_applicable(h, c.attn_dim_head, n, ns, dl) && frame_fused_frames_ok(Fr) &&
-               tiled_family(Fr * n, 2 * hd, dl, GEMM_RMS_ROWSCALE, e->lin_kv_w)) {
+               takes(v2, Fr * n, 2 * hd, dl, GEMM_RMS_ROWSCALE, e->lin_kv_w)) {
         // one workgroup per frame: K | V of the latents on the matrix pipe, straight into the learned queries' attention (e->lkv is not written)
         if ((rc = lqap_in(latents, dl, e->lin_kv_w, dl, e->lin_q, e->lin_gate, e->lq_in.k_gamma, e->latt, Fr, h, n, ns, dl, RMS_EPS, s))) return rc;
-        if ((rc = gemm_simple(e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0))) return rc;
     } else {
-    if ((rc = gemm_simple(latents, dl, e->lin_kv_w, dl, e->lkv, 2 * hd, Fr * n, 2 * hd, dl, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_simple(cx, latents, dl, e->lin_kv_w, dl, e->lkv, 2 * hd, Fr * n, 2 * hd, dl, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0))) return rc;
     {
         SmallAttnArgs sa{};
         sa.dh = c.attn_dim_head;
@@ -1092,10 +1064,10 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->lq_in.k_gamma;
         sa.out = e->latt; sa.o_group_stride = (int64_t)ns * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = ns; sa.nk = n;
-        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
+        sa.wide = e->attn_wide();
         if ((rc = small_attn(sa, s))) return rc;
     }
-    if ((rc = gemm_simple(e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_simple(cx, e->latt, hd, e->lq_in.to_out, hd, e->space, D, Fr * ns, D, hd, 0, nullptr, nullptr, 0))) return rc;
     }
 
     // ---- pack tokens (D4:7182-7222)
@@ -1104,7 +1076,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         a.tokens = slab0; a.space = e->space; a.signal_embed = e->signal_embed; a.step_embed = e->step_embed;
         a.registers = e->registers; a.agent_embed = e->agent_learned; a.task_embed = e->task_embed;
         a.action_embed = e->action_embed; a.action_learned = e->action_learned;
-        a.signal_levels = t_sig_uniform >= 0 ? nullptr : e->sig; a.signal_uniform = t_sig_uniform; a.prev_actions = e->na > 0 ? e->pact : nullptr; a.tasks = tasks;
+        a.signal_levels = cx.sig_uniform >= 0 ? nullptr : e->sig; a.signal_uniform = cx.sig_uniform; a.prev_actions = e->na > 0 ? e->pact : nullptr; a.tasks = tasks;
         a.prev_cont = e->nc > 0 ? e->pcont : nullptr; a.cont_embed = e->cont_embed; a.nc = e->nc;
         a.action_offsets = e->action_offsets;
         a.B = B; a.Tq = Tq; a.S = S; a.D = D; a.ns = ns; a.nr = c.num_register_tokens; a.na = e->na; a.step_log2 = step_log2;
@@ -1119,16 +1091,20 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         gb.batch = c.depth - 1; gb.strideA = 0; gb.strideW = e->pkv_stride; gb.strideC = (int64_t)e->kvr_stride[ly];
         gb.rule_M = 3 * M;
         gb.rm_Sc = (uint16_t)Sc; gb.rm_lo = (uint16_t)reg_lo; gb.rm_nr = (uint16_t)nr;
-        if ((rc = engine_gemm(gb, s))) return rc;
+        if ((rc = engine_gemm(cx, gb))) return rc;
     }
     }
-    if (t_bf16) if (uint16_t* sb = t_bf16->shadow_of(slab0)) { if ((rc = cvt_rows_bf16(slab0, D, sb, D, M, D, s))) return rc; }
+    if (cx.img) if (uint16_t* sb = cx.img->shadow_of(slab0)) { if ((rc = cvt_rows_bf16(slab0, D, sb, D, M, D, s))) return rc; }
 
     // ---- trunk (AxialSpaceTimeTransformer.forward, D4:3040-3223)
+    // Denoise steps (no agent embedding wanted): nothing downstream reads the last layer's flow / register / action rows, so a last space layer attends
+    // from the spatial rows only, and its output projection and feedforward run on the compacted rows.
+    auto compact_tail_at = [&](int l) { return denoise_only && l == c.depth - 1 && !e->is_time[l] && c.depth >= 2 && S <= 16 && S >= 8; };
     const float* x_in = slab0;
     const float* vres = P0 + 3 * hd + 2 * h;
     for (int l = 0; l < c.depth; ++l) {
         const AttnW& a = e->layer_attn[l];
+        const bool compact_tail = compact_tail_at(l);
         float* P = l == 0 ? P0 : e->proj;
         const int ldp = l == 0 ? e->Nproj0 : e->Nproj;
         // Last layer of a denoise evaluation (the compact tail below): its attention reads the queries and head gates of the ns spatial rows only, so
@@ -1136,22 +1112,22 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         // row — two problems of one launch on the regrouped image.  Taken only where the whole projection and both parts run on the LDS-DMA family by the
         // dispatcher's own rule (gemm_rule_takes_v2 on the calls as they are made: weight planes of a split-operand engine, rule_M), so the bits are
         // those of the single launch; a projection the split-operand kernels take (N >= 2048) keeps its one launch.
-        const bool compact_q = g_last_layer_compact_q && fp32_engine && e->proj_wc && denoise_only && l == c.depth - 1 && !e->is_time[l] && c.depth >= 2 && S <= 16 && S >= 8 &&
-                               c.attn_dim_head == 64 && !g_small_attn_wide && tiled_family(M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_w[l]) &&
-                               tiled_family(M, 2 * hd + h, D, GEMM_RMS_ROWSCALE, e->proj_wc) && tiled_family(Mc, hd + h, D, GEMM_RMS_ROWSCALE, e->proj_wc, M);
+        const bool compact_q = g_last_layer_compact_q && fp32_engine && e->proj_wc && compact_tail &&
+                               c.attn_dim_head == 64 && !g_small_attn_wide && takes(v2, M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_w[l]) &&
+                               takes(v2, M, 2 * hd + h, D, GEMM_RMS_ROWSCALE, e->proj_wc) && takes(v2, Mc, hd + h, D, GEMM_RMS_ROWSCALE, e->proj_wc, M);
         if (compact_q) {
             GemmArgs ga{x_in, D, e->proj_wc, D, P, ldp, e->proj_bc, nullptr, 0, M, 2 * hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             GemmArgs gb{e->xpool_c, D, e->proj_wc + (size_t)(2 * hd + h) * D, D, e->qc, e->ldqc, e->proj_bc + 2 * hd + h, nullptr, 0, Mc, hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             gb.rule_M = M;
-            if ((rc = gemm_two(ga, gb, s))) return rc;
+            if ((rc = gemm_two(cx, ga, gb))) return rc;
         } else if (l == 0 && l0_const) {
             // the rows that change, from their dense image, into their places around the prefilled register rows
             GemmArgs g0{e->slab0r, D, e->proj_w[0], D, P, ldp, e->proj_b[0], nullptr, 0, Fr * Sc, ldp, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             g0.rule_M = M;
             g0.rm_Sc = (uint16_t)Sc; g0.rm_lo = (uint16_t)reg_lo; g0.rm_nr = (uint16_t)nr;
-            if ((rc = engine_gemm(g0, s))) return rc;
+            if ((rc = engine_gemm(cx, g0))) return rc;
         } else
-        if ((rc = gemm_simple(x_in, D, e->proj_w[l], D, P, ldp, M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_b[l], nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, x_in, D, e->proj_w[l], D, P, ldp, M, ldp, D, GEMM_RMS_ROWSCALE, e->proj_b[l], nullptr, 0))) return rc;
         bool fused_out = false;
         if (e->is_time[l]) {
             TimeAttnArgs ta{};
@@ -1162,7 +1138,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             ta.softclamp = c.attn_softclamp_value;
             ta.cache_batch = e->maxB; ta.cache_S = e->S;
             ta.t0_dev = t0_dev;
-            ta.out_b = t_bf16 ? t_bf16->shadow_of(e->att) : nullptr;
+            ta.out_b = cx.img ? cx.img->shadow_of(e->att) : nullptr;
             if ((rc = time_attn_append(ta, s))) return rc;
         } else {
             SmallAttnArgs sa{};
@@ -1177,10 +1153,10 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
             sa.k_gamma = a.k_gamma;
             sa.out = e->att; sa.o_group_stride = (int64_t)S * hd; sa.o_item_stride = hd;
             sa.groups = Fr; sa.heads = h; sa.nq = S; sa.nk = S;
-            sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
+            sa.wide = e->attn_wide();
             sa.softclamp = c.attn_softclamp_value; sa.mask_special = e->encoder ? n : has_agent; sa.belief = 1;
-            sa.out_b = t_bf16 ? t_bf16->shadow_of(e->att) : nullptr;
-            if (denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8) {
+            sa.out_b = cx.img ? cx.img->shadow_of(e->att) : nullptr;
+            if (compact_tail) {
                 sa.q_lo = 1; sa.q_hi = 1 + ns; sa.q_last = 0;
                 sa.out = e->att_c; sa.o_group_stride = (int64_t)nkeep * hd; sa.out_b = nullptr;
                 if (compact_q) {
@@ -1192,54 +1168,51 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
                 }
             }
             // per-frame fused form: attention of all heads of a frame, then its output projection + residual, in one kernel
-            const bool tail_compact = denoise_only && l == c.depth - 1 && c.depth >= 2 && S <= 16 && S >= 8;
-            if (!tail_compact && !e->wo_t.empty() && (!t_bf16 || t_bf16->fp32_planes()) && frame_attn_out_applicable(sa, D)) {
-                if ((rc = frame_attn_out(sa, e->wo_t[l], D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, t_keep_lo, t_keep_hi, has_agent, s))) return rc;
+            if (!compact_tail && !e->wo_t.empty() && (!cx.img || cx.img->fp32_planes()) && frame_attn_out_applicable(sa, D)) {
+                if ((rc = frame_attn_out(sa, e->wo_t[l], D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, cx.keep_lo, cx.keep_hi, has_agent, s))) return rc;
                 fused_out = true;
-            } else if (!tail_compact && hd == 512 && (!t_bf16 || t_bf16->fp32_planes()) && attn_out_cols_applicable(sa, D)) {
+            } else if (!compact_tail && hd == 512 && (!cx.img || cx.img->fp32_planes()) && attn_out_cols_applicable(sa, D)) {
                 // few frames (launch-bound decode): attention recomputed inside every column workgroup of the output projection, one launch for two
-                if ((rc = attn_out_cols(sa, a.to_out, hd, D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, t_keep_lo, t_keep_hi, has_agent, s))) return rc;
+                if ((rc = attn_out_cols(sa, a.to_out, hd, D, x_in, D, slab(2 * l + 1), D, cslab(2 * l + 1), D, cx.keep_lo, cx.keep_hi, has_agent, s))) return rc;
                 fused_out = true;
             } else
             if ((rc = small_attn(sa, s))) return rc;
         }
-        // Denoise steps (no agent embedding wanted): nothing downstream reads the last layer's flow / register /
-        // action rows, so its output projection and feedforward run on the compacted rows only.
-        const bool compact_tail = denoise_only && l == c.depth - 1 && !e->is_time[l] && c.depth >= 2 && S <= 16 && S >= 8;
         if (compact_tail) {
-            if ((rc = gemm_simple(e->att_c, hd, a.to_out, hd, cslab(2 * l + 1), D, Mc, D, hd, 0, nullptr, e->xpool_c, D, s))) return rc;
-            if ((rc = ff_block(e, e->ffp[l], e->layer_ff[l].out_b, cslab(2 * l + 1), D, cslab(2 * l + 2), D, Mc, s))) return rc;
+            if ((rc = gemm_simple(cx, e->att_c, hd, a.to_out, hd, cslab(2 * l + 1), D, Mc, D, hd, 0, nullptr, e->xpool_c, D))) return rc;
+            if ((rc = ff_block(cx, e, e->ffp[l], e->layer_ff[l].out_b, cslab(2 * l + 1), D, cslab(2 * l + 2), D, Mc))) return rc;
             break;
         }
         float* h1 = slab(2 * l + 1);
         float* h2 = slab(2 * l + 2);
-        if (!fused_out && (rc = gemm_c2(e->att, hd, a.to_out, hd, h1, D, M, D, hd, 0, nullptr, x_in, D, cslab(2 * l + 1), S, t_keep_hi - t_keep_lo, has_agent, s))) return rc;
+        if (!fused_out && (rc = gemm_c2(cx, e->att, hd, a.to_out, hd, h1, D, M, D, hd, 0, nullptr, x_in, D, cslab(2 * l + 1), S, has_agent))) return rc;
         // The pool behind this feedforward projects every hidden so far to keys, and all but the newest slab exist before the feedforward starts: their
         // first rows ride on the workgroups the input projection's last round leaves idle (gemm_x3sk.hip: the filled form).  Taken only where
         // the dispatcher runs the input projection on the persistent kernel by its own rule, that launch has a partial round, the pool takes the mix
         // path with separate keys, and the full key problem and the shortened one both stay on the LDS-DMA family (whose bits the fill tiles carry).
         GemmArgs kfill{};
         int keys_done = 0;
-        if (g_ff_fill_pool_keys && dynamics && e->split && l < c.depth - 1 && c.pool_heads == 4 && D <= 1024 && !e->kall_b) {
+        if (g_ff_fill_pool_keys && dynamics && e->split && l < c.depth - 1 && e->pool_mix_path() && !e->kall_b) {
             const int L = 2 * l + 3;
-            const GemmArgs g1 = ff_in_call(e, e->ffp[l], h1, D, M);
-            const int cap = g1.Wb && gemm_rule_takes_x3sk(g1) ? gemm_x3sk_fill_capacity(g1) : 0;
+            GemmArgs g1 = ff_in_call(e, e->ffp[l], h1, D, M);
+            trunk_call(cx.img, g1);
+            const int cap = gemm_rule_takes_x3sk(g1) ? gemm_x3sk_fill_capacity(g1) : 0;
             const GemmArgs gk = pool_key_call(e, l, e->slabs, L, M, 0, keys0(l));
             const int ready = (gk.M - M) / 128;                              // whole 128-row blocks of the slabs <= 2 l + 1 (the problem ends with slab 2 l + 2)
             const int per_block = (e->hp + 63) / 64;                          // 128 x 64 tiles per 128-row block
             const int blocks = cap / per_block < ready ? cap / per_block : ready;
-            if (blocks > 0 && tiled_family(L * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[l]) &&
-                tiled_family(gk.M - 128 * blocks, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[l], L * M)) {
+            if (blocks > 0 && takes(v2, L * M, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[l]) &&
+                takes(v2, gk.M - 128 * blocks, e->hp, D, GEMM_RMS_ROWSCALE, e->pkv_w[l], L * M)) {
                 keys_done = 128 * blocks;
                 kfill = gk;
                 kfill.M = keys_done; kfill.rule_M = 0;
                 D4_REQUIRE(gemm_x3sk_fill_applicable(kfill), "ff_fill_pool_keys: the key problem of pool %d is no fill problem", l);
             }
         }
-        if ((rc = ff_block(e, e->ffp[l], e->layer_ff[l].out_b, h1, D, h2, D, M, s, cslab(2 * l + 2), S, has_agent, keys_done ? &kfill : nullptr))) return rc;
+        if ((rc = ff_block(cx, e, e->ffp[l], e->layer_ff[l].out_b, h1, D, h2, D, M, cslab(2 * l + 2), S, has_agent, keys_done ? &kfill : nullptr))) return rc;
         if (l != c.depth - 1) {
-            float* xc = (denoise_only && l == c.depth - 2 && !e->is_time[c.depth - 1] && S <= 16 && S >= 8) ? e->xpool_c : nullptr;
-            if ((rc = pool_block(e, l, h2, e->xpool, 2 * l + 3, M, s, nullptr, xc, S, has_agent, 0, keys0(l), keys_done))) return rc;
+            float* xc = compact_tail_at(l + 1) ? e->xpool_c : nullptr;
+            if ((rc = pool_block(cx, e, l, h2, e->xpool, 2 * l + 3, M, nullptr, xc, S, has_agent, 0, keys0(l), keys_done))) return rc;
             x_in = e->xpool;
         }
     }
@@ -1258,8 +1231,8 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         // xfc = compact latent rows [Fr][n][D]
         const int P = e->P;
         const float* spec = cslab(2 * c.depth);
-        if ((rc = gemm_simple(spec, D, e->cq_w, D, e->cq, e->ldcq, Mc, hd + h, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0, s))) return rc;
-        if ((rc = gemm_simple(last, D, e->ckv_w, D, e->ckv, 2 * hd, M, 2 * hd, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, spec, D, e->cq_w, D, e->cq, e->ldcq, Mc, hd + h, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0))) return rc;
+        if ((rc = gemm_simple(cx, last, D, e->ckv_w, D, e->ckv, 2 * hd, M, 2 * hd, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0))) return rc;
         SmallAttnArgs sa{};
         sa.dh = c.attn_dim_head;
         sa.q = e->cq; sa.q_group_stride = (int64_t)n * e->ldcq; sa.q_item_stride = e->ldcq;
@@ -1269,19 +1242,19 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->cross.k_gamma;
         sa.out = e->catt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = P;
-        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
+        sa.wide = e->attn_wide();
         if ((rc = small_attn(sa, s))) return rc;
-        if ((rc = gemm_simple(e->catt, hd, e->cross.to_out, hd, xfc, D, Mc, D, hd, 0, nullptr, spec, D, s))) return rc;
-        if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, xfc, D, xfc, D, Mc, s))) return rc;
-        if ((rc = pool_block(e, c.depth - 1, xfc, xfc, e->nslab, Mc, s, e->cslabs))) return rc;
+        if ((rc = gemm_simple(cx, e->catt, hd, e->cross.to_out, hd, xfc, D, Mc, D, hd, 0, nullptr, spec, D))) return rc;
+        if ((rc = ff_block(cx, e, e->ffp[c.depth], e->sff.out_b, xfc, D, xfc, D, Mc))) return rc;
+        if ((rc = pool_block(cx, e, c.depth - 1, xfc, xfc, e->nslab, Mc, e->cslabs))) return rc;
         // final RMSNorm (folded) -> encoded_to_latents -> tanh                                   D4:3246, 4408, 4417
-        if ((rc = gemm_simple(xfc, D, e->t2p_wf, D, e->enc_out, c.dim_latent, Mc, c.dim_latent, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = gemm_simple(cx, xfc, D, e->t2p_wf, D, e->enc_out, c.dim_latent, Mc, c.dim_latent, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0))) return rc;
         return tanh_rows(e->enc_out, e->enc_out, (int64_t)Mc * c.dim_latent, s);
     }
     if (e->decoder) {
         // final attention pool on the patch rows, then final RMSNorm (folded) -> Linear(dim, channels * patch^2)   D4:3242-3246, 3555
-        if ((rc = pool_block(e, c.depth - 1, xfc, xfc, e->nslab, Mc, s, e->cslabs))) return rc;
-        return gemm_simple(xfc, D, e->t2p_wf, D, e->dec_out, e->dim_patch, Mc, e->dim_patch, D, GEMM_RMS_ROWSCALE, e->t2p_b, nullptr, 0, s);
+        if ((rc = pool_block(cx, e, c.depth - 1, xfc, xfc, e->nslab, Mc, e->cslabs))) return rc;
+        return gemm_simple(cx, xfc, D, e->t2p_wf, D, e->dec_out, e->dim_patch, Mc, e->dim_patch, D, GEMM_RMS_ROWSCALE, e->t2p_b, nullptr, 0);
     }
     if (need_agent) {
         // agent token cross-attends the non-special tokens of its frame, then its own feedforward (D4:3227-3238)
@@ -1291,7 +1264,7 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         {
             const GemmArgs gq{agent_in, lda, e->cq_w, D, e->cq, e->ldcq, nullptr, nullptr, 0, Fr, hd + h, D, GEMM_RMS_ROWSCALE, RMS_EPS};
             const GemmArgs gkv{last, D, e->ckv_w, D, e->ckv, 2 * hd, nullptr, nullptr, 0, M, 2 * hd, D, GEMM_RMS_ROWSCALE, RMS_EPS};
-            if ((rc = gemm_two(gq, gkv, s))) return rc;
+            if ((rc = gemm_two(cx, gq, gkv))) return rc;
         }
         SmallAttnArgs sa{};
         sa.dh = c.attn_dim_head;
@@ -1302,25 +1275,25 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->cross.k_gamma;
         sa.out = e->catt; sa.o_group_stride = hd; sa.o_item_stride = 0;
         sa.groups = Fr; sa.heads = h; sa.nq = 1; sa.nk = S - 1;
-        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
+        sa.wide = e->attn_wide();
         if ((rc = small_attn(sa, s))) return rc;
-        if ((rc = gemm_simple(e->catt, hd, e->cross.to_out, hd, agent_rows, ldc, Fr, D, hd, 0, nullptr, agent_in, lda, s))) return rc;
-        if ((rc = ff_block(e, e->ffp[c.depth], e->sff.out_b, agent_rows, ldc, agent_rows, ldc, Fr, s))) return rc;
+        if ((rc = gemm_simple(cx, e->catt, hd, e->cross.to_out, hd, agent_rows, ldc, Fr, D, hd, 0, nullptr, agent_in, lda))) return rc;
+        if ((rc = ff_block(cx, e, e->ffp[c.depth], e->sff.out_b, agent_rows, ldc, agent_rows, ldc, Fr))) return rc;
     }
     // ---- final attention pool over every layer hidden (D4:3242-3243), compact rows
-    if ((rc = pool_block(e, c.depth - 1, xfc, xfc, e->nslab, Mc, s, e->cslabs, nullptr, 0, 1, agent_only ? Fr * (ns + 1) : 0))) return rc;
+    if ((rc = pool_block(cx, e, c.depth - 1, xfc, xfc, e->nslab, Mc, e->cslabs, nullptr, 0, 1, agent_only ? Fr * (ns + 1) : 0))) return rc;
     if (!need_pred) return 0;                 // the clean step of a rollout: the prediction is never read (d4_rollout breaks before the Euler step)
 
     // ---- to_latent_pred: RMSNorm -> LQAP (n queries over the ns spatial tokens) -> Linear  (D4:7251)
     if (same_len) {
         // RMSNorm -> Linear on the spatial rows (gamma folded into the weight, 1/rms in the GEMM)
         if ((rc = copy_rows(xfc, nkeep * D, e->gs, ns * D, Fr, ns * D, s))) return rc;
-        return gemm_simple(e->gs, D, e->lout_w, D, e->pred, dl, Fr * n, dl, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0, s);
+        return gemm_simple(cx, e->gs, D, e->lout_w, D, e->pred, dl, Fr * n, dl, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0);
     }
     if ((rc = gather_space_double_norm(xfc, e->gs, e->latent_norm, e->lq_out.norm_ctx, Fr, nkeep, 0, D, ns, RMS_EPS, s))) return rc;
-    if ((rc = gemm_simple(e->gs, D, e->lout_kv_w, D, e->okv, 2 * hd, Fr * ns, 2 * hd, D, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_simple(cx, e->gs, D, e->lout_kv_w, D, e->okv, 2 * hd, Fr * ns, 2 * hd, D, 0, nullptr, nullptr, 0))) return rc;
     if (g_lqap_out_fused && fp32_engine && !g_small_attn_wide && lqap_out_applicable(h, c.attn_dim_head, n, ns, dl) && dl % 4 == 0 && frame_fused_frames_ok(Fr) &&
-        tiled_family(Fr * n, dl, hd, 0, e->lout_w))
+        takes(v2, Fr * n, dl, hd, 0, e->lout_w))
         // one workgroup per frame: the learned queries' attention into LDS, the latent projection as its tail (e->oatt is not written)
         return lqap_out(e->okv, 2 * hd, e->lout_q, e->lout_gate, e->lq_out.k_gamma, e->lout_w, hd, e->pred, dl, Fr, h, n, ns, dl, s);
     {
@@ -1333,10 +1306,10 @@ static int engine_forward_impl(d4_engine* e, const float* latents, int B, int Tq
         sa.k_gamma = e->lq_out.k_gamma;
         sa.out = e->oatt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = ns;
-        sa.wide = (c.wide_frames & 2) ? 2 : (c.wide_frames & 1);
+        sa.wide = e->attn_wide();
         if ((rc = small_attn(sa, s))) return rc;
     }
-    if ((rc = gemm_simple(e->oatt, hd, e->lout_w, hd, e->pred, dl, Fr * n, dl, hd, 0, nullptr, nullptr, 0, s))) return rc;
+    if ((rc = gemm_simple(cx, e->oatt, hd, e->lout_w, hd, e->pred, dl, Fr * n, dl, hd, 0, nullptr, nullptr, 0))) return rc;
     return 0;
 }
 
@@ -1369,7 +1342,7 @@ int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, f
                 lin_in = sxh;
             }
             if (ldz != dout && (rc = fill_f32(sz, 0.f, (int64_t)rows * ldz, s))) return rc;
-            if ((rc = gemm_simple(lin_in, din, m.w[i], din, sz, ldz, rows, dout, din, 0, m.b[i], nullptr, 0, s))) return rc;
+            if ((rc = gemm_fp32(lin_in, din, m.w[i], din, sz, ldz, rows, dout, din, 0, m.b[i], nullptr, 0, s))) return rc;
             if (last) { if ((rc = copy_rows(sz, ldz, out, ldo, rows, dout, s))) return rc; }
             else {
                 float *nx, *nxh, *nz;
@@ -1391,7 +1364,7 @@ int mlp_forward(d4_engine* e, const Mlp& m, const float* x, int ldx, int rows, f
         // ONE launch per layer (bias + SiLU in the epilogue).  Rounds 1-4 sliced K over the grid and combined the slices in a reduce kernel (few rows x
         // long K on 64 x 64 tiles); with the 32 x 32 tiles of the LDS-DMA family the direct form is level on the 2048 x 2048 layers (30.1 us vs 22.8 + a
         // 5 us reduce + a boundary) and ahead on the first and last layers (K = 512: 9.7 vs 13.7 us) — tools/splitk_probe.py — so the reduce launches are gone
-        if ((rc = gemm_simple(lin_in, ld_in, m.w[i], din, y, ldy, rows, dout, din, act ? GEMM_SILU : 0, m.b[i], nullptr, 0, s))) return rc;
+        if ((rc = gemm_fp32(lin_in, ld_in, m.w[i], din, y, ldy, rows, dout, din, act ? GEMM_SILU : 0, m.b[i], nullptr, 0, s))) return rc;
         if (post && (rc = layernorm_rows(y, ldy, m.g[i], m.nb[i], y, ldy, rows, dout, LN_EPS, 1, s))) return rc;
         cur = y; ld = ldy;
     }
@@ -1407,7 +1380,7 @@ static int rollout_heads_batched(d4_engine* e, const d4_rollout_io* io, const fl
     int rc;
     if (F == 1) {
         if ((rc = rmsnorm_rows(hist, D, e->reward_norm, e->hnorm, D, B, D, RMS_EPS, s))) return rc;
-        if ((rc = gemm_simple(e->hnorm, D, e->reward_w, D, e->rlogits, rb, B, rb, D, 0, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = gemm_fp32(e->hnorm, D, e->reward_w, D, e->rlogits, rb, B, rb, D, 0, nullptr, nullptr, 0, s))) return rc;
         if ((rc = hl_gauss_scalar(e->rlogits, rb, e->reward_centers, io->rewards + P, T, B, rb, s))) return rc;
         if (!io->sample_actions) return 0;
         float* vb = e->hbuf[(e->value.nl - 1) & 1];
@@ -1421,7 +1394,7 @@ static int rollout_heads_batched(d4_engine* e, const d4_rollout_io* io, const fl
         const float* x = hist + (size_t)b0 * F * D;
         // reward: Ensemble member 0 of [RMSNorm -> Linear]                     D4:6598-6601
         if ((rc = rmsnorm_rows(x, D, e->reward_norm, e->hb_norm, D, rows, D, RMS_EPS, s))) return rc;
-        if ((rc = gemm_simple(e->hb_norm, D, e->reward_w, D, e->hb_rlogits, rb, rows, rb, D, 0, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = gemm_fp32(e->hb_norm, D, e->reward_w, D, e->hb_rlogits, rb, rows, rb, D, 0, nullptr, nullptr, 0, s))) return rc;
         if ((rc = hl_gauss_scalar(e->hb_rlogits, rb, e->reward_centers, e->hb_scal, 1, rows, rb, s))) return rc;
         if ((rc = copy_rows(e->hb_scal, F, io->rewards + (size_t)b0 * T + P, T, nb, F, s))) return rc;      // [nb][F] -> frames P .. T-1 of [B][T]
         if (!io->sample_actions) continue;
@@ -1744,6 +1717,17 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                 D4_HIP(hipMemcpyAsync(e->tasks_dev, io->tasks, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
                 tasks = e->tasks_dev;
             }
+            // the K + 1 evaluations and Euler steps of the frame, enqueued on `st` (captured once per graph key, else on the caller's stream)
+            auto frame_evals = [&](hipStream_t st) {
+                for (int step = 0; step <= K; ++step) {
+                    const int sig_val = step * step_size < c.max_steps - 1 ? step * step_size : c.max_steps - 1;
+                    if (int r = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, st, e->fstate, !(step == K && lean), sig_val)) return r;
+                    if (step == K) break;
+                    const float tt = (float)sig_val / (float)c.max_steps;
+                    if (int r = d4::euler_step(e->x_lat, n_el, e->pred, n_el, B, n_el, 1.f - tt, (float)step_size / (float)c.max_steps, st)) return r;
+                }
+                return 0;
+            };
             hipGraphExec_t exec = nullptr;
             const int bucket = e->Lt > 0 ? d4::time_history_bucket(t0) : 0;
             for (auto& g : e->graphs) if (g.B == B && g.K == K && g.sl == sl && g.tasks == (tasks != nullptr) && g.bucket == bucket && g.variant == variant) exec = g.exec;
@@ -1758,17 +1742,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                     hipStream_t cs = e->capture_stream;
                     hipGraph_t graph;
                     D4_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-                    int crc = 0;
-                    for (int step = 0; step <= K && !crc; ++step) {
-                        const int sig_val = step * step_size < c.max_steps - 1 ? step * step_size : c.max_steps - 1;
-                        d4::t_sig_uniform = sig_val;
-                        crc = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, cs, e->fstate, !(step == K && lean));
-                        d4::t_sig_uniform = -1;
-                        if (crc) break;
-                        if (step == K) break;
-                        const float tt = (float)sig_val / (float)c.max_steps;
-                        crc = d4::euler_step(e->x_lat, n_el, e->pred, n_el, B, n_el, 1.f - tt, (float)step_size / (float)c.max_steps, cs);
-                    }
+                    const int crc = frame_evals(cs);
                     hipError_t ce = hipStreamEndCapture(cs, &graph);
                     if (crc) { if (ce == hipSuccess) (void)hipGraphDestroy(graph); return crc; }
                     D4_HIP(ce);
@@ -1777,20 +1751,8 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
                     e->graphs.push_back({B, K, sl, tasks != nullptr, bucket, variant, exec});
                 }
             }
-            if (exec) {
-                D4_HIP(hipGraphLaunch(exec, s));
-            } else {
-                for (int step = 0; step <= K; ++step) {
-                    const int sig_val = step * step_size < c.max_steps - 1 ? step * step_size : c.max_steps - 1;
-                    d4::t_sig_uniform = sig_val;
-                    rc = d4::engine_forward(e, e->x_lat, B, 1, t0, sl, tasks, step == K, s, e->fstate, !(step == K && lean));
-                    d4::t_sig_uniform = -1;
-                    if (rc) return rc;
-                    if (step == K) break;
-                    const float tt = (float)sig_val / (float)c.max_steps;
-                    if ((rc = d4::euler_step(e->x_lat, n_el, e->pred, n_el, B, n_el, 1.f - tt, (float)step_size / (float)c.max_steps, s))) return rc;
-                }
-            }
+            if (exec) D4_HIP(hipGraphLaunch(exec, s));
+            else if ((rc = frame_evals(s))) return rc;
             if (commit) e->cache_frames = t0 + 1;
         } else
         for (int step = 0; step <= K; ++step) {
@@ -1819,7 +1781,7 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
         if (!heads_after) {
         // reward: Ensemble member 0 of [RMSNorm -> Linear]                     D4:6598-6601
         if ((rc = d4::rmsnorm_rows(e->agent_c, D, e->reward_norm, e->hnorm, D, B, D, d4::RMS_EPS, s))) return rc;
-        if ((rc = d4::gemm_simple(e->hnorm, D, e->reward_w, D, e->rlogits, c.reward_num_bins, B, c.reward_num_bins, D, 0, nullptr, nullptr, 0, s))) return rc;
+        if ((rc = d4::gemm_fp32(e->hnorm, D, e->reward_w, D, e->rlogits, c.reward_num_bins, B, c.reward_num_bins, D, 0, nullptr, nullptr, 0, s))) return rc;
         if ((rc = d4::hl_gauss_scalar(e->rlogits, c.reward_num_bins, e->reward_centers, io->rewards + cur, T, B, c.reward_num_bins, s))) return rc;
         }
         // terminal logit from the mean-pooled denoised latent                    D4:6605-6607
@@ -1834,13 +1796,13 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
             float* pe = e->hbuf[(e->policy.nl - 1) & 1];   // the buffer mlp_forward's last hidden does not occupy
             if ((rc = d4::mlp_forward(e, e->policy, e->agent_c, D, B, pe, 4 * D, nullptr, s))) return rc;
             float* logits = na > 0 ? io->action_logits + (size_t)f * A : nullptr;
-            if (na > 0 && (rc = d4::gemm_simple(pe, 4 * D, e->action_unembed, c.multi_token_pred_len * 4 * D, logits, F * A, B, A, 4 * D, 0, nullptr, nullptr, 0, s))) return rc;
+            if (na > 0 && (rc = d4::gemm_fp32(pe, 4 * D, e->action_unembed, c.multi_token_pred_len * 4 * D, logits, F * A, B, A, 4 * D, 0, nullptr, nullptr, 0, s))) return rc;
             float* cparams = nc > 0 ? io->cont_params + (size_t)f * nc * 2 : nullptr;
             if (nc > 0) {
                 // raw Beta parameters of prediction head 0: the [nc][mtp][4D][2] parameter is read through a K-contiguous copy of
                 // its head-0 slice (a trained head changes every optimiser step, so the copy is refreshed per frame: 2 nc x 4D floats)
                 if ((rc = d4::cunembed_gather(e->cont_unembed, e->cu_w, nc, c.multi_token_pred_len, 4 * D, s))) return rc;
-                if ((rc = d4::gemm_simple(pe, 4 * D, e->cu_w, 4 * D, cparams, F * nc * 2, B, 2 * nc, 4 * D, 0, nullptr, nullptr, 0, s))) return rc;
+                if ((rc = d4::gemm_fp32(pe, 4 * D, e->cu_w, 4 * D, cparams, F * nc * 2, B, 2 * nc, 4 * D, 0, nullptr, nullptr, 0, s))) return rc;
             }
             // value                                                                    D4:6659-6662
             if (!heads_after) {
@@ -1880,17 +1842,6 @@ int d4_rollout(d4_engine* e, const d4_rollout_io* io, void* stream) {
     return 0;
 }
 
-int d4_profile_bf16_enable(int stride) { d4::gemm_bf16_profile_enable(stride); return 0; }
-int d4_profile_bf16_read(double* ms, double* flops, int64_t* count) { return d4::gemm_bf16_profile_read(ms, flops, count); }
-int d4_profile_enable(int on) { return d4::gemm_profile_enable(on); }
-int d4_profile_read(double* ms, double* flops, int64_t* count, int nclass) { return d4::gemm_profile_read(ms, flops, count, nclass); }
-int d4_profile_classes(void) { return d4::gemm_profile_classes(); }
-int d4_profile_glue_enable(int mask) { return d4::glue_profile_enable(mask); }
-int d4_profile_glue_read(double* ms, double* bytes, int64_t* count, int nclass) { return d4::glue_profile_read(ms, bytes, count, nclass); }
-int d4_profile_glue_classes(void) { return d4::GL_N; }
-int d4_profile_glue_read_flops(double* flops, int nclass) { return d4::glue_profile_read_flops(flops, nclass); }
-const char* d4_profile_glue_class_name(int c) { return d4::glue_class_name(c); }
-int d4_frame_fused_set(int mode) { return d4::frame_fused_set(mode); }
 
 int d4_debug_switch(const char* name, int value) {
     int* sw = nullptr;
@@ -1939,7 +1890,6 @@ int d4_gemm_force_config(int id) {
     d4::gemm_force_config(id);                                                                      // < 100 first fp32 family, 100 + c second (gemm2.hip)
     return id >= 100 ? d4::gemm2_configs() : n_main;
 }
-const char* d4_profile_class_name(int c) { return d4::gemm_profile_class_name(c); }
 
 int d4_debug_buffer(d4_engine* e, const char* name, float** ptr) {
     D4_REQUIRE(e && name && ptr, "null argument");
@@ -1962,537 +1912,6 @@ int d4_debug_buffer(d4_engine* e, const char* name, float** ptr) {
 int d4_learn(d4_engine* e, const d4_learn_io* io, void* stream) {
     D4_REQUIRE(e && io, "null argument");
     return d4::learn(e, io, static_cast<hipStream_t>(stream));
-}
-
-int d4_gemm(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
-            const float* R, int ldr, int M, int N, int K, int flags, float rms_eps, void* stream) {
-    d4::GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    return d4::gemm(g, static_cast<hipStream_t>(stream));
-}
-
-int d4_gemm_pair(const float* A1, int lda1, const float* W1, float* C1, int ldc1, int M1, int N1, const float* A2, int lda2, const float* W2, float* C2,
-                 int ldc2, int M2, int N2, int K, int flags, float rms_eps, void* stream) {
-    d4::GemmArgs a{A1, lda1, W1, K, C1, ldc1, nullptr, nullptr, 0, M1, N1, K, flags, rms_eps};
-    d4::GemmArgs b{A2, lda2, W2, K, C2, ldc2, nullptr, nullptr, 0, M2, N2, K, flags, rms_eps};
-    return d4::gemm_pair(a, b, static_cast<hipStream_t>(stream));
-}
-
-int d4_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, float* part, int64_t part_floats,
-               int tile_n, int slices, void* stream) {
-    return d4::gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, part, (size_t)part_floats, static_cast<hipStream_t>(stream), tile_n, slices);
-}
-
-int d4_gemm_batched(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
-                    const float* R, int ldr, int M, int N, int K, int flags, float rms_eps, int batch,
-                    int64_t strideA, int64_t strideW, int64_t strideC, void* stream) {
-    d4::GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.batch = batch; g.strideA = strideA; g.strideW = strideW; g.strideC = strideC;
-    return d4::gemm(g, static_cast<hipStream_t>(stream));
-}
-
-int d4_split_bf16x3(const float* src, uint16_t* dst, int64_t n, int64_t plane_stride, void* stream) {
-    D4_REQUIRE(src && dst && n >= 0 && plane_stride >= n && (plane_stride % 8) == 0, "d4_split_bf16x3: bad arguments");
-    return d4::split_bf16x3(src, dst, n, plane_stride, static_cast<hipStream_t>(stream));
-}
-int d4_gemm_split(const float* A, int lda, const uint16_t* W3, int64_t plane_stride, int ldw, float* C, int ldc, const float* bias,
-                  const float* R, int ldr, int M, int N, int K, int flags, float rms_eps, int config, void* stream) {
-    d4::GemmArgs g{A, lda, reinterpret_cast<const float*>(W3), ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.Wb = W3; g.wplane = plane_stride;
-    D4_REQUIRE(d4::gemm_x3_applicable(g), "d4_gemm_split: call not supported (M=%d N=%d K=%d flags=%d: K %% 32, ldw %% 8, plane_stride %% 8, 16-byte alignment)", M, N, K, flags);
-    if (M == 0) return 0;
-    if (config == d4::gemm_x3_configs()) return d4::gemm_x3sk_launch(g, static_cast<hipStream_t>(stream));      // 6: the persistent form (the engine's)
-    if (config >= 0) return d4::gemm_x3_launch(config, g, static_cast<hipStream_t>(stream));
-    return d4::gemm_x3_launch(d4::gemm_x3_heuristic(g), g, static_cast<hipStream_t>(stream));
-}
-int d4_split_f16x2(const float* src, uint16_t* dst, int rows, int cols, int ld, int64_t plane_stride, float* inv_scale, void* stream) {
-    D4_REQUIRE(src && dst && inv_scale && rows >= 0 && cols >= 1 && ld >= cols && (ld % 8) == 0 && plane_stride >= (int64_t)rows * ld && (plane_stride % 8) == 0,
-               "d4_split_f16x2: bad arguments");
-    return d4::split_f16x2_rows(src, dst, rows, cols, ld, plane_stride, inv_scale, static_cast<hipStream_t>(stream));
-}
-int d4_row_scale_exp(const float* A, int64_t lda, int rows, int K, int32_t* exp_out, void* stream) {
-    D4_REQUIRE(A && exp_out && rows >= 0 && K >= 4 && lda >= K, "d4_row_scale_exp: bad arguments");
-    return d4::row_scale_exp(A, lda, rows, K, exp_out, static_cast<hipStream_t>(stream));
-}
-int d4_gemm_split2(const float* A, int lda, const uint16_t* W2, int64_t plane_stride, int ldw, const float* w_inv_scale, float* C, int ldc, const float* bias,
-                   const float* R, int ldr, int M, int N, int K, int flags, float rms_eps, int config, const int32_t* a_exp, void* stream) {
-    d4::GemmArgs g{A, lda, reinterpret_cast<const float*>(W2), ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.Wb = W2; g.wplane = plane_stride; g.wscale = w_inv_scale; g.aexp = a_exp;
-    D4_REQUIRE(d4::gemm_h2_applicable(g), "d4_gemm_split2: call not supported (M=%d N=%d K=%d flags=%d: K %% 32, lda %% 4, ldw %% 8, plane_stride %% 8, 16-byte alignment)", M, N, K, flags);
-    if (M == 0) return 0;
-    return d4::gemm_h2_launch(config >= 0 ? config : d4::gemm_h2_heuristic(g), g, static_cast<hipStream_t>(stream));
-}
-int d4_gemm_bf16(const float* A, int lda, const uint16_t* Wb, int ldw, float* C, int ldc, const float* bias,
-                 const float* R, int ldr, int M, int N, int K, int flags, float rms_eps, void* stream) {
-    d4::GemmArgs g{A, lda, reinterpret_cast<const float*>(Wb), ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.Wb = Wb;
-    return d4::gemm_bf16(g, static_cast<hipStream_t>(stream));
-}
-
-int d4_cvt_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) { return d4::cvt_f32_to_bf16(src, dst, n, static_cast<hipStream_t>(stream)); }
-
-int d4_gemm_bf16a(const uint16_t* Ab, int lda, const uint16_t* Wb, int ldw, float* C, int ldc, uint16_t* Cb, const float* bias, const float* R, int ldr,
-                  int M, int N, int K, int flags, float rms_eps, int config, void* stream) {
-    d4::GemmArgs g{nullptr, lda, nullptr, ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.Ab = Ab; g.Wb = Wb; g.Cb = Cb;
-    D4_REQUIRE(d4::gemm_bf16a_applicable(g), "d4_gemm_bf16a: call not supported (K %% 64, lda / ldw %% 8, 16-byte aligned operands)");
-    if (config >= 100) { g.group_m = -1; config -= 100; }       // 100 + c: configuration c with the plain row-major tile order (A/B of the grouped order)
-    return d4::gemm_bf16a_launch(config >= 0 ? config : d4::gemm_bf16a_rule(g), g, static_cast<hipStream_t>(stream));
-}
-
-int d4_gemm_bf16a_compact(const uint16_t* Ab, int lda, const uint16_t* Wb, int ldw, float* C, int ldc, uint16_t* Cb, const float* bias, const float* R, int ldr,
-                          int M, int N, int K, int flags, float rms_eps, float* C2, uint16_t* C2b, int ldc2, int c2_S, int c2_lo, int c2_hi, int c2_last,
-                          int config, void* stream) {
-    d4::GemmArgs g{nullptr, lda, nullptr, ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.Ab = Ab; g.Wb = Wb; g.Cb = Cb;
-    g.C2 = C2; g.C2b = C2b; g.ldc2 = ldc2; g.c2_S = c2_S; g.c2_lo = c2_lo; g.c2_hi = c2_hi; g.c2_last = c2_last;
-    D4_REQUIRE(C2 && c2_S >= 1 && c2_lo >= 0 && c2_hi >= c2_lo && c2_hi <= c2_S, "d4_gemm_bf16a_compact: bad compaction arguments");
-    D4_REQUIRE(d4::gemm_bf16a_applicable(g), "d4_gemm_bf16a_compact: call not supported (K %% 64, lda / ldw %% 8, 16-byte aligned operands)");
-    return d4::gemm_bf16a_launch(config >= 0 ? config : d4::gemm_bf16a_rule(g), g, static_cast<hipStream_t>(stream));
-}
-
-int d4_gemm_bf16a_batched(const uint16_t* Ab, int lda, const uint16_t* Wb, int ldw, float* C, int ldc, uint16_t* Cb, const float* bias, const float* R, int ldr,
-                          int M, int N, int K, int flags, float rms_eps, int batch, int64_t strideA, int64_t strideW, int64_t strideC, int config, void* stream) {
-    d4::GemmArgs g{nullptr, lda, nullptr, ldw, C, ldc, bias, R, ldr, M, N, K, flags, rms_eps};
-    g.Ab = Ab; g.Wb = Wb; g.Cb = Cb;
-    g.batch = batch; g.strideA = strideA; g.strideW = strideW; g.strideC = strideC;
-    D4_REQUIRE(C || Cb, "d4_gemm_bf16a_batched: no output");
-    if (M == 0) return 0;
-    D4_REQUIRE(d4::gemm_bf16a_applicable(g), "d4_gemm_bf16a_batched: call not supported (K %% 64, lda / ldw / strides %% 8, 16-byte aligned operands)");
-    return d4::gemm_bf16a_launch(config >= 0 ? config : d4::gemm_bf16a_rule(g), g, static_cast<hipStream_t>(stream));
-}
-int d4_cvt_rows_bf16(const float* src, int64_t lds, uint16_t* dst, int64_t ldd, int rows, int cols, void* stream) {
-    D4_REQUIRE(src && dst && rows >= 0 && cols >= 0 && lds >= cols && ldd >= cols, "d4_cvt_rows_bf16: bad arguments");
-    return d4::cvt_rows_bf16(src, lds, dst, ldd, rows, cols, static_cast<hipStream_t>(stream));
-}
-
-int d4_rmsnorm(const float* x, int ldx, const float* gamma, float* y, int ldy, int rows, int dim, float eps, void* stream) {
-    return d4::rmsnorm_rows(x, ldx, gamma, y, ldy, rows, dim, eps, static_cast<hipStream_t>(stream));
-}
-
-// Operator-level test entry points of the glue launchers of elementwise.hip: each checks its pointers and sizes, fills the launcher's
-// arguments and calls it.
-int d4_layernorm_rows(const float* x, int ldx, const float* g, const float* b, float* y, int ldy, int rows, int dim, float eps, int silu, void* stream) {
-    D4_REQUIRE(x && g && y && rows >= 0 && dim >= 1 && ldx >= dim && ldy >= dim, "d4_layernorm_rows: bad arguments");
-    return d4::layernorm_rows(x, ldx, g, b, y, ldy, rows, dim, eps, silu, static_cast<hipStream_t>(stream));
-}
-int d4_assemble_tokens(const d4_assemble_desc* d, void* stream) {
-    D4_REQUIRE(d && d->tokens && d->signal_embed && d->step_embed && d->agent_embed, "d4_assemble_tokens: null argument");
-    D4_REQUIRE(d->B >= 0 && d->Tq >= 0 && d->D >= 2 && d->D % 2 == 0 && d->ns >= 0 && d->nr >= 0 && d->na >= 0 && d->nc >= 0 && d->step_log2 >= 0 &&
-               (d->has_agent == 0 || d->has_agent == 1), "d4_assemble_tokens: bad sizes");
-    D4_REQUIRE(d->S == 1 + d->ns + d->nr + (d->na > 0 || d->nc > 0 ? 1 : 0) + d->has_agent, "d4_assemble_tokens: S %d is not 1 + ns + nr (+ action) (+ agent)", d->S);
-    D4_REQUIRE((d->ns == 0 || d->space) && (d->nr == 0 || d->registers) && (d->signal_levels || d->signal_uniform >= 0), "d4_assemble_tokens: table missing");
-    D4_REQUIRE((d->na == 0 && d->nc == 0) || d->action_learned, "d4_assemble_tokens: action_learned missing");
-    D4_REQUIRE(d->na == 0 || !d->prev_actions || (d->action_embed && d->action_offsets), "d4_assemble_tokens: action tables missing");
-    D4_REQUIRE(d->nc == 0 || !d->prev_cont || d->cont_embed, "d4_assemble_tokens: cont_embed missing");
-    D4_REQUIRE(!d->tasks || d->task_embed, "d4_assemble_tokens: task_embed missing");
-    d4::AssembleArgs a{};
-    a.tokens = d->tokens; a.space = d->space; a.signal_embed = d->signal_embed; a.step_embed = d->step_embed; a.registers = d->registers;
-    a.agent_embed = d->agent_embed; a.task_embed = d->task_embed; a.action_embed = d->action_embed; a.action_learned = d->action_learned;
-    a.signal_levels = d->signal_levels; a.signal_uniform = d->signal_uniform; a.prev_actions = d->prev_actions; a.prev_cont = d->prev_cont;
-    a.cont_embed = d->cont_embed; a.tasks = d->tasks; a.action_offsets = d->action_offsets;
-    a.B = d->B; a.Tq = d->Tq; a.S = d->S; a.D = d->D; a.ns = d->ns; a.nr = d->nr; a.na = d->na; a.nc = d->nc; a.step_log2 = d->step_log2;
-    a.compact = d->compact; a.has_agent = d->has_agent;
-    return d4::assemble_tokens(a, static_cast<hipStream_t>(stream));
-}
-int d4_gather_space_double_norm(const float* tokens, float* out, const float* g0, const float* g1, int frames, int S, int first, int dim, int ns,
-                                float eps, void* stream) {
-    D4_REQUIRE(tokens && out && g0 && g1 && frames >= 0 && dim >= 1 && ns >= 1 && first >= 0 && first + ns <= S, "d4_gather_space_double_norm: bad arguments");
-    return d4::gather_space_double_norm(tokens, out, g0, g1, frames, S, first, dim, ns, eps, static_cast<hipStream_t>(stream));
-}
-int d4_euler_step_rows(float* x, int ldx, const float* pred, int ldp, int B, int n_el, float one_minus_t, float dt, void* stream) {
-    D4_REQUIRE(x && pred && B >= 0 && n_el >= 0 && ldx >= n_el && ldp >= n_el, "d4_euler_step_rows: bad arguments");
-    return d4::euler_step(x, ldx, pred, ldp, B, n_el, one_minus_t, dt, static_cast<hipStream_t>(stream));
-}
-int d4_splitk_reduce(const float* part, int S, int M, int N, const float* bias, int silu, float* y, int ldy, void* stream) {
-    D4_REQUIRE(part && y && S >= 1 && M >= 0 && N >= 1 && ldy >= N, "d4_splitk_reduce: bad arguments");
-    return d4::splitk_reduce(part, S, M, N, bias, silu, y, ldy, static_cast<hipStream_t>(stream));
-}
-int d4_mean_tokens(const float* x, float* out, int B, int n, int d, void* stream) {
-    D4_REQUIRE(x && out && B >= 0 && n >= 1 && d >= 1, "d4_mean_tokens: bad arguments");
-    return d4::mean_tokens(x, out, B, n, d, static_cast<hipStream_t>(stream));
-}
-int d4_hl_gauss_scalar_strided(const float* logits, int ld, const float* centers, float* out, int out_stride, int rows, int bins, void* stream) {
-    D4_REQUIRE(logits && centers && out && rows >= 0 && bins >= 1 && ld >= bins && out_stride >= 1, "d4_hl_gauss_scalar_strided: bad arguments");
-    return d4::hl_gauss_scalar(logits, ld, centers, out, out_stride, rows, bins, static_cast<hipStream_t>(stream));
-}
-int d4_fold_rows(const float* W, const float* gamma, float* out, int rows, int K, int ld_out, void* stream) {
-    D4_REQUIRE(W && out && rows >= 0 && K >= 1 && ld_out >= K, "d4_fold_rows: bad arguments");
-    return d4::fold_rows(W, gamma, out, rows, K, ld_out, static_cast<hipStream_t>(stream));
-}
-int d4_swiglu_pack_rows(const float* W, const float* bias, const float* gamma, float* Wp, float* bp, int inner, int inner_pad, int K, void* stream) {
-    D4_REQUIRE(W && bias && gamma && Wp && bp && inner >= 1 && inner_pad >= inner && inner_pad % 32 == 0 && K >= 1, "d4_swiglu_pack_rows: bad arguments (inner_pad %% 32)");
-    return d4::swiglu_pack_rows(W, bias, gamma, Wp, bp, inner, inner_pad, K, static_cast<hipStream_t>(stream));
-}
-int d4_build_latent_input(float* out, const float* hist, const float* ctx_noise, const float* x, int B, int Tq, int n_el, int hist_t_stride, float w, void* stream) {
-    D4_REQUIRE(out && x && B >= 0 && Tq >= 1 && n_el >= 0 && (Tq == 1 || (hist && hist_t_stride >= Tq - 1)), "d4_build_latent_input: bad arguments");
-    return d4::build_latent_input(out, hist, ctx_noise, x, B, Tq, n_el, hist_t_stride, w, static_cast<hipStream_t>(stream));
-}
-int d4_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, void* stream) {
-    D4_REQUIRE(src && dst && rows >= 0 && cols >= 0 && lds >= cols && ldd >= cols, "d4_copy_rows: bad arguments");
-    return d4::copy_rows(src, lds, dst, ldd, rows, cols, static_cast<hipStream_t>(stream));
-}
-int d4_pad_cols(const float* W, float* out, int rows, int cols, int cols_pad, void* stream) {
-    D4_REQUIRE(W && out && rows >= 1 && cols >= 1 && cols_pad >= cols, "d4_pad_cols: bad arguments");
-    return d4::pad_cols(W, out, rows, cols, cols_pad, static_cast<hipStream_t>(stream));
-}
-int d4_video_patches(const float* src, float* dst, int B, int C, int T, int nh, int nw, int ps, int to_patches, void* stream) {
-    D4_REQUIRE(src && dst && B >= 0 && C >= 1 && T >= 1 && nh >= 1 && nw >= 1 && ps >= 1, "d4_video_patches: bad arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return to_patches ? d4::video_to_patches(src, dst, B, C, T, nh, nw, ps, s) : d4::patches_to_video(src, dst, B, C, T, nh, nw, ps, s);
-}
-int d4_cache_transfer(float* cache, float* ext, int Lt, int cache_batch, int B, int S, int H, int Tcap, int frames, int to_ext, int dh, void* stream) {
-    D4_REQUIRE(cache && ext && Lt >= 0 && B >= 0 && cache_batch >= B && S >= 1 && H >= 1 && frames >= 0 && Tcap >= frames && dh >= 1, "d4_cache_transfer: bad arguments");
-    return d4::cache_transfer(cache, ext, Lt, cache_batch, B, S, H, Tcap, frames, to_ext, dh, static_cast<hipStream_t>(stream));
-}
-int d4_cunembed(int op, const float* src, float* dst, int nc, int mtp, int d, void* stream) {
-    D4_REQUIRE(src && dst && nc >= 0 && mtp >= 1 && d >= 1 && (op == 0 || op == 1), "d4_cunembed: op 0 (gather) or 1 (scatter the gradient)");
-    return op == 0 ? d4::cunembed_gather(src, dst, nc, mtp, d, static_cast<hipStream_t>(stream)) : d4::cunembed_scatter_grad(src, dst, nc, mtp, d, static_cast<hipStream_t>(stream));
-}
-int d4_coord_grid(float* out, int nh, int nw, int ld, void* stream) {
-    D4_REQUIRE(out && nh >= 1 && nw >= 1 && ld >= 2, "d4_coord_grid: bad arguments");
-    return d4::coord_grid(out, nh, nw, ld, static_cast<hipStream_t>(stream));
-}
-int d4_pack_tokens(int which, float* tokens, float* compact, const float* pos, const float* img, const float* lat, int frames, int P, int n_lat, int n_total,
-                   int D, void* stream) {
-    D4_REQUIRE(tokens && compact && img && lat && frames >= 0 && P >= 0 && n_lat >= 0 && D >= 1 && (which == 0 || which == 1), "d4_pack_tokens: bad arguments");
-    D4_REQUIRE(which == 1 || (pos && n_total >= n_lat), "d4_pack_tokens: the decoder form needs pos and n_total >= n_lat");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return which == 0 ? d4::decoder_pack_tokens(tokens, compact, pos, img, lat, frames, P, n_lat, n_total, D, s)
-                      : d4::encoder_pack_tokens(tokens, compact, img, lat, frames, P, n_lat, D, s);
-}
-int d4_prep_eval_inputs(int32_t* sig, int64_t* pact, const int64_t* actions_hist, int B, int Tq, int na, int frame_base, int hist_stride, int sig_val, int ctx_sig,
-                        float* pcont, const float* cont_hist, int nc, void* stream) {
-    D4_REQUIRE(sig && B >= 1 && Tq >= 1 && na >= 0 && nc >= 0 && frame_base >= 0 && hist_stride >= frame_base + Tq - 1, "d4_prep_eval_inputs: bad arguments");
-    D4_REQUIRE((na == 0 || pact) && (nc == 0 || pcont), "d4_prep_eval_inputs: pact / pcont missing");
-    return d4::prep_eval_inputs(sig, pact, actions_hist, B, Tq, na, frame_base, hist_stride, sig_val, ctx_sig, static_cast<hipStream_t>(stream), pcont, cont_hist, nc);
-}
-int d4_unary_rows(int op, const float* x, float* y, int64_t n, void* stream) {
-    D4_REQUIRE(x && y && n >= 0 && (op == 0 || op == 1), "d4_unary_rows: op 0 (silu) or 1 (tanh)");
-    return op == 0 ? d4::silu_rows(x, y, n, static_cast<hipStream_t>(stream)) : d4::tanh_rows(x, y, n, static_cast<hipStream_t>(stream));
-}
-
-// Operator-level test entry points of the inference attention cores (attn.hip): each fills the launcher's argument struct and calls it.
-static int small_attn_entry(int wide, const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
-                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
-    d4::SmallAttnArgs sa{};
-    sa.wide = wide;
-    sa.q = q; sa.q_group_stride = q_group_stride; sa.q_item_stride = q_item_stride;
-    sa.k = k; sa.k_group_stride = k_group_stride; sa.k_item_stride = k_item_stride;
-    sa.v = v; sa.v_group_stride = v_group_stride; sa.v_item_stride = v_item_stride;
-    sa.gate = gate; sa.g_group_stride = g_group_stride; sa.g_item_stride = g_item_stride;
-    sa.k_gamma = k_gamma;
-    sa.vres = vres; sa.r_group_stride = r_group_stride; sa.r_item_stride = r_item_stride;
-    sa.mix = mix; sa.m_group_stride = m_group_stride; sa.m_item_stride = m_item_stride;
-    sa.out = out; sa.o_group_stride = o_group_stride; sa.o_item_stride = o_item_stride; sa.out_b = out_b;
-    sa.groups = groups; sa.heads = heads; sa.nq = nq; sa.nk = nk;
-    sa.softclamp = softclamp; sa.mask_special = mask_special; sa.belief = belief;
-    sa.q_lo = q_lo; sa.q_hi = q_hi; sa.q_last = q_last; sa.dh = dh;
-    return d4::small_attn(sa, static_cast<hipStream_t>(stream));
-}
-int d4_small_attn(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
-                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
-    return small_attn_entry(0, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
-                            k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
-                            nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
-}
-int d4_small_attn_wide(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
-                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
-    return small_attn_entry(1, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
-                            k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
-                            nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
-}
-
-int d4_small_attn_wide_bf16(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                  const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                  const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                  int64_t m_item_stride, float* out, int64_t o_group_stride, int64_t o_item_stride, uint16_t* out_b, int groups, int heads, int nq, int nk,
-                  float softclamp, int mask_special, int belief, int q_lo, int q_hi, int q_last, int dh, void* stream) {
-    return small_attn_entry(2, q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride, g_item_stride,
-                            k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out, o_group_stride, o_item_stride, out_b, groups, heads,
-                            nq, nk, softclamp, mask_special, belief, q_lo, q_hi, q_last, dh, stream);
-}
-
-int d4_lqap_in(const float* latents, int ldl, const float* w_kv, int ldw, const float* q, const float* gate, const float* k_gamma, float* out, int frames,
-               int heads, int n, int ns, int dl, float eps, void* stream) {
-    D4_REQUIRE(latents && w_kv && q && gate && k_gamma && out, "d4_lqap_in: null argument");
-    return d4::lqap_in(latents, ldl, w_kv, ldw, q, gate, k_gamma, out, frames, heads, n, ns, dl, eps, static_cast<hipStream_t>(stream));
-}
-int d4_lqap_out(const float* kv, int ldkv, const float* q, const float* gate, const float* k_gamma, const float* w_out, int ldw, float* pred, int ldp,
-                int frames, int heads, int n, int ns, int dl, void* stream) {
-    D4_REQUIRE(kv && q && gate && k_gamma && w_out && pred, "d4_lqap_out: null argument");
-    return d4::lqap_out(kv, ldkv, q, gate, k_gamma, w_out, ldw, pred, ldp, frames, heads, n, ns, dl, static_cast<hipStream_t>(stream));
-}
-
-int d4_pool_mix(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
-                const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
-                const uint16_t* hid_b, void* stream) {
-    d4::PoolMixArgs pm{};
-    pm.q = q; pm.ldq = ldq; pm.x = x; pm.ldx = ldx; pm.gate_w = gate_w; pm.k = k; pm.ldk = ldk; pm.hid = hid; pm.D = D; pm.k_gamma = k_gamma;
-    pm.u = u; pm.M = M; pm.L = L; pm.heads = heads; pm.eps = eps; pm.u_b = u_b; pm.k_b = k_b; pm.q_b = q_b; pm.hid_b = hid_b;
-    return d4::pool_mix(pm, static_cast<hipStream_t>(stream));
-}
-
-int d4_time_attn_decode(const float* proj, int ldp, const float* vres, int ldv, const float* k_gamma, const float* inv_freq, float* cache, float* out,
-                        int ldo, uint16_t* out_b, int B, int S, int H, int Tq, int t0, int Tcap, int cache_batch, int cache_S, const int* t0_dev,
-                        float softclamp, int dh, int mode, void* stream) {
-    D4_REQUIRE(mode >= 0 && mode <= 2, "d4_time_attn_decode: mode %d (0 append + attend, 1 append only, 2 attend only)", mode);
-    d4::TimeAttnArgs ta{};
-    ta.proj = proj; ta.ldp = ldp; ta.vres = vres; ta.ldv = ldv; ta.k_gamma = k_gamma; ta.inv_freq = inv_freq; ta.cache = cache;
-    ta.out = out; ta.ldo = ldo; ta.out_b = out_b; ta.B = B; ta.S = S; ta.H = H; ta.Tq = Tq; ta.t0 = t0; ta.Tcap = Tcap;
-    ta.cache_batch = cache_batch; ta.cache_S = cache_S; ta.t0_dev = t0_dev; ta.softclamp = softclamp; ta.dh = dh;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return mode == 0 ? d4::time_attn_append(ta, s) : mode == 1 ? d4::time_kv_append(ta, s) : d4::time_attn(ta, s);
-}
-
-int d4_pool_mix_deep(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
-                     const float* k_gamma, float* u, int M, int L, int heads, float eps, uint16_t* u_b, const uint16_t* k_b, const uint16_t* q_b,
-                     const uint16_t* hid_b, void* stream) {
-    d4::PoolMixArgs pm{};
-    pm.q = q; pm.ldq = ldq; pm.x = x; pm.ldx = ldx; pm.gate_w = gate_w; pm.k = k; pm.ldk = ldk; pm.hid = hid; pm.D = D; pm.k_gamma = k_gamma;
-    pm.u = u; pm.M = M; pm.L = L; pm.heads = heads; pm.eps = eps; pm.u_b = u_b; pm.k_b = k_b; pm.q_b = q_b; pm.hid_b = hid_b;
-    return d4::pool_mix_deep(pm, static_cast<hipStream_t>(stream));
-}
-
-const char* d4_debug_last_form(const char* family) { return d4::attn_last_form(family); }
-int d4_debug_forms(const char* family, int i, const char** name) { return d4::attn_form_name(family, i, name); }
-
-// Operator-level test entry points of the GEMM launches only the engine reaches otherwise: one family / configuration named by the caller, straight to
-// its launcher; and the pair launches.  A refusal names its reason and nothing falls through to another family.
-static d4::GemmArgs gemm_args_of(const d4_gemm_desc& d) {
-    d4::GemmArgs g{d.A, d.lda, d.W, d.ldw, d.C, d.ldc, d.bias, d.R, d.ldr, d.M, d.N, d.K, d.flags, d.rms_eps};
-    g.C2 = d.C2; g.ldc2 = d.ldc2; g.c2_S = d.c2_S; g.c2_lo = d.c2_lo; g.c2_hi = d.c2_hi; g.c2_last = d.c2_last;
-    g.batch = d.batch > 0 ? d.batch : 1; g.strideA = d.strideA; g.strideW = d.strideW; g.strideC = d.strideC;
-    g.Ab = d.Ab; g.Wb = d.Wb; g.Cb = d.Cb; g.C2b = d.C2b; g.wplane = d.wplane; g.wscale = d.wscale; g.strideWs = d.strideWs; g.aexp = d.aexp;
-    return g;
-}
-static int gemm_desc_check(const char* who, const d4_gemm_desc* d) {
-    D4_REQUIRE(d && d->M >= 1 && d->N >= 1 && d->K >= 1 && (d->C || d->Cb), "%s: null descriptor, no output or bad sizes", who);
-    D4_REQUIRE(!(d->C2 || d->C2b) || (d->C2 && d->c2_S >= 1 && d->c2_lo >= 0 && d->c2_hi >= d->c2_lo && d->c2_hi <= d->c2_S && d->ldc2 >= d->N &&
-                                      (d->c2_last == 0 || d->c2_last == 1) && !(d->flags & d4::GEMM_SWIGLU)),
-               "%s: bad compaction arguments", who);
-    return 0;
-}
-int d4_gemm_family_configs(int family) {
-    switch (family) {
-        case D4_GEMM_TILE: return d4::gemm_configs();
-        case D4_GEMM_V2: return d4::gemm2_configs();
-        case D4_GEMM_X3: return d4::gemm_x3_configs();
-        case D4_GEMM_H2: return d4::gemm_h2_configs();
-        case D4_GEMM_BF16: return d4::gemm_bf16_configs();
-        case D4_GEMM_BF16A: return d4::gemm_bf16a_configs();
-        case D4_GEMM_V2_KSPLIT: case D4_GEMM_X3SK: case D4_GEMM_SKINNY: return 1;
-    }
-    return -1;
-}
-static int gemm_run_args(const d4::GemmArgs& g, int family, int config, void* stream);
-int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream) {
-    if (int rc = gemm_desc_check("d4_gemm_run", d)) return rc;
-    return gemm_run_args(gemm_args_of(*d), family, config, stream);
-}
-// ... with the output row map (GemmArgs::rm_*): the families that implement it run it, every other launcher refuses
-int d4_gemm_run_rowmap(const d4_gemm_desc* d, int family, int config, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream) {
-    if (int rc = gemm_desc_check("d4_gemm_run_rowmap", d)) return rc;
-    D4_REQUIRE(rm_Sc >= 1 && rm_nr >= 0 && rm_lo >= 0 && rm_lo <= rm_Sc && rm_S == rm_Sc + rm_nr && rm_S <= 65535, "d4_gemm_run_rowmap: bad row map (Sc=%d S=%d lo=%d nr=%d)", rm_Sc, rm_S, rm_lo, rm_nr);
-    d4::GemmArgs g = gemm_args_of(*d);
-    g.rm_Sc = (uint16_t)rm_Sc; g.rm_lo = (uint16_t)rm_lo; g.rm_nr = (uint16_t)rm_nr;
-    return gemm_run_args(g, family, config, stream);
-}
-static int gemm_run_args(const d4::GemmArgs& g, int family, int config, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool al16 = ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && (g.lda % 4) == 0 && (g.ldw % 4) == 0;
-#define D4_RUN_REFUSE(cond, why) D4_REQUIRE(cond, "d4_gemm_run: call not supported (family %d, configuration %d, M=%d N=%d K=%d flags=%d: " why ")", family, config, g.M, g.N, g.K, g.flags)
-    switch (family) {
-        case D4_GEMM_TILE: {
-            D4_RUN_REFUSE(d4::gemm_config_valid(config, g), "the dispatcher does not run this configuration of the first family here - few-row shape, mirror weights or an epilogue the tile lacks");
-            d4_gemm_force_config(config);
-            const int rc = d4::gemm(g, s);
-            d4_gemm_force_config(-1);
-            return rc;
-        }
-        case D4_GEMM_V2:
-            D4_RUN_REFUSE(al16 && !g.Wb && d4::gemm2_config_valid(config, g), "gemm2_config_valid: K %% 32, lda / ldw %% 4, no transposed operand, SiLU-GLU tiles");
-            return d4::gemm2_launch(config, g, s);
-        case D4_GEMM_V2_KSPLIT:
-            D4_RUN_REFUSE(al16 && d4::gemm2_ksplit_applicable(g), "gemm2_ksplit_applicable: no batch, C2, row scale, bias-free flags other than SiLU; K >= 4 k-tiles");
-            return d4::gemm2_ksplit_launch(g, s);
-        case D4_GEMM_X3:
-            D4_RUN_REFUSE(al16 && !g.wscale && d4::gemm_x3_config_valid(config, g), "gemm_x3_config_valid: three bf16 planes, K %% 32, ldw / plane %% 8, SiLU-GLU tiles");
-            return d4::gemm_x3_launch(config, g, s);
-        case D4_GEMM_X3SK:
-            D4_RUN_REFUSE(al16 && !g.wscale && d4::gemm_x3sk_applicable(g), "gemm_x3sk_applicable: as gemm_x3, no batch");
-            return d4::gemm_x3sk_launch(g, s);
-        case D4_GEMM_H2:
-            D4_RUN_REFUSE(al16 && d4::gemm_h2_config_valid(config, g), "gemm_h2_config_valid: two fp16 planes + row scales, K %% 32, ldw / plane %% 8, SiLU-GLU tiles");
-            return d4::gemm_h2_launch(config, g, s);
-        case D4_GEMM_SKINNY:
-            D4_RUN_REFUSE(al16 && !g.Wb && d4::gemm_skinny_applicable(g) && (!(g.flags & d4::GEMM_SWIGLU) || g.N % 64 == 0),
-                          "gemm_skinny_applicable: at most 256 rows and fewer than 64 tiles, K % 4, no transposed operand, C2 without batch");
-            return d4::gemm_skinny(g, s);
-        case D4_GEMM_BF16: {
-            D4_RUN_REFUSE(((uintptr_t)g.A % 16) == 0 && !g.Ab && g.wplane == 0 && d4::gemm_bf16_config_valid(config, g), "gemm_bf16: bf16 weights, K %% 32, lda %% 4, ldw %% 8, SiLU-GLU tiles");
-            d4::gemm_bf16_force_config(config);
-            const int rc = d4::gemm_bf16(g, s);
-            d4::gemm_bf16_force_config(-1);
-            return rc;
-        }
-        case D4_GEMM_BF16A:
-            D4_RUN_REFUSE(d4::gemm_bf16a_config_valid(config, g), "gemm_bf16a_config_valid: bf16 images of both operands, K %% 64, lda / ldw %% 8, SiLU-GLU tiles");
-            return d4::gemm_bf16a_launch(config, g, s);
-    }
-    D4_REQUIRE(false, "d4_gemm_run: unknown family %d", family);
-#undef D4_RUN_REFUSE
-}
-// The filled form of the persistent split-operand kernel (gemm_x3sk.hip): `main` in whole tiles with the first `fill_tiles` 128 x 64 tiles of `fill` on the
-// workgroups its last round leaves idle; the launcher's refusals come back as errors
-int d4_gemm_fill_capacity(const d4_gemm_desc* main) {
-    if (!main || main->M < 1 || main->N < 1 || main->K < 1) return 0;
-    return d4::gemm_x3sk_fill_capacity(gemm_args_of(*main));
-}
-int d4_gemm_run_fill(const d4_gemm_desc* main, const d4_gemm_desc* fill, int fill_tiles, void* stream) {
-    if (int rc = gemm_desc_check("d4_gemm_run_fill", main)) return rc;
-    D4_REQUIRE(fill_tiles == 0 || fill, "d4_gemm_run_fill: fill tiles without a fill descriptor");
-    if (fill_tiles != 0) if (int rc = gemm_desc_check("d4_gemm_run_fill", fill)) return rc;
-    const d4::GemmArgs g = gemm_args_of(*main);
-    D4_REQUIRE(((uintptr_t)g.A % 16) == 0 && (g.lda % 4) == 0 && !g.wscale, "d4_gemm_run_fill: main operands must be 16-byte aligned split-operand planes");
-    return d4::gemm_x3sk_fill(g, fill ? gemm_args_of(*fill) : d4::GemmArgs{}, fill_tiles, static_cast<hipStream_t>(stream));
-}
-// ... with an output row map on the FILL problem (as d4_gemm_run_rowmap): the filled form does not implement it, so this is an error — the entry exists
-// so that the refusal can be observed
-int d4_gemm_run_fill_rowmap(const d4_gemm_desc* main, const d4_gemm_desc* fill, int fill_tiles, int rm_Sc, int rm_S, int rm_lo, int rm_nr, void* stream) {
-    if (int rc = gemm_desc_check("d4_gemm_run_fill_rowmap", main)) return rc;
-    if (int rc = gemm_desc_check("d4_gemm_run_fill_rowmap", fill)) return rc;
-    D4_REQUIRE(rm_Sc >= 1 && rm_nr >= 0 && rm_lo >= 0 && rm_lo <= rm_Sc && rm_S == rm_Sc + rm_nr && rm_S <= 65535, "d4_gemm_run_fill_rowmap: bad row map (Sc=%d S=%d lo=%d nr=%d)", rm_Sc, rm_S, rm_lo, rm_nr);
-    d4::GemmArgs f = gemm_args_of(*fill);
-    f.rm_Sc = (uint16_t)rm_Sc; f.rm_lo = (uint16_t)rm_lo; f.rm_nr = (uint16_t)rm_nr;
-    return d4::gemm_x3sk_fill(gemm_args_of(*main), f, fill_tiles, static_cast<hipStream_t>(stream));
-}
-int d4_gemm_run_pair(const d4_gemm_desc* da, const d4_gemm_desc* db, int target, int config, void* stream) {
-    if (int rc = gemm_desc_check("d4_gemm_run_pair", da)) return rc;
-    if (int rc = gemm_desc_check("d4_gemm_run_pair", db)) return rc;
-    const d4::GemmArgs a = gemm_args_of(*da), b = gemm_args_of(*db);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    auto al16 = [](const d4::GemmArgs& g) { return ((uintptr_t)g.A % 16) == 0 && ((uintptr_t)g.W % 16) == 0 && (g.lda % 4) == 0 && (g.ldw % 4) == 0; };
-    switch (target) {
-        case D4_PAIR_SKINNY:
-            D4_REQUIRE(al16(a) && al16(b) && d4::gemm_skinny_pair_applicable(a, b),
-                       "d4_gemm_run_pair: call not supported (gemm_skinny_pair_applicable: two few-row products of equal K, no SiLU-GLU, batch or mirror weights)");
-            return d4::gemm_skinny_pair(a, b, s);
-        case D4_PAIR_BF16A:
-            D4_REQUIRE(d4::gemm_bf16a_pair_applicable(a, b),
-                       "d4_gemm_run_pair: call not supported (gemm_bf16a_pair_applicable: equal K, flags == RMS, no bias / R / C2 / batch, a 64 x 64 or 128 x 64 tile by the rule)");
-            return d4::gemm_bf16a_pair_launch(a, b, s);
-        case D4_PAIR_V2:
-            D4_REQUIRE(al16(a) && al16(b) && !a.Wb && !b.Wb && a.K == b.K && d4::gemm2_pair_config_ok(config) && d4::gemm2_pair_applicable(a, b) &&
-                       d4::gemm2_config_valid(config, a) && d4::gemm2_config_valid(config, b),
-                       "d4_gemm_run_pair: call not supported (gemm2 pair configuration %d: gemm2_pair_config_ok / gemm2_pair_applicable)", config);
-            return d4::gemm2_pair_launch(config, a, b, s);
-    }
-    D4_REQUIRE(false, "d4_gemm_run_pair: unknown target %d", target);
-}
-
-// ... and of the per-frame fused block tails (frame_fused.hip)
-int d4_tile16_weights(const float* W, int ldw, float* Wt, int N, int K, void* stream) {
-    D4_REQUIRE(W && Wt && N >= 16 && K >= 4 && ldw >= K && ((uintptr_t)W % 16) == 0 && ((uintptr_t)Wt % 16) == 0, "d4_tile16_weights: bad arguments");
-    return d4::tile16_weights(W, ldw, Wt, N, K, static_cast<hipStream_t>(stream));
-}
-static d4::SmallAttnArgs frame_attn_args(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                                         const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                                         const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                                         int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh) {
-    d4::SmallAttnArgs sa{};
-    sa.q = q; sa.q_group_stride = q_group_stride; sa.q_item_stride = q_item_stride;
-    sa.k = k; sa.k_group_stride = k_group_stride; sa.k_item_stride = k_item_stride;
-    sa.v = v; sa.v_group_stride = v_group_stride; sa.v_item_stride = v_item_stride;
-    sa.gate = gate; sa.g_group_stride = g_group_stride; sa.g_item_stride = g_item_stride;
-    sa.k_gamma = k_gamma;
-    sa.vres = vres; sa.r_group_stride = r_group_stride; sa.r_item_stride = r_item_stride;
-    sa.mix = mix; sa.m_group_stride = m_group_stride; sa.m_item_stride = m_item_stride;
-    sa.out_b = out_b;
-    sa.groups = frames; sa.heads = heads; sa.nq = S; sa.nk = S;
-    sa.softclamp = softclamp; sa.mask_special = mask_special; sa.belief = belief; sa.dh = dh;
-    return sa;
-}
-static int frame_out_check(const char* who, const float* resid, const float* out, const float* c2, int S, int c2_lo, int c2_hi, int c2_last) {
-    D4_REQUIRE(resid && out && ((uintptr_t)resid % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)c2 % 16) == 0, "%s: residual / output missing or not 16-byte aligned", who);
-    D4_REQUIRE(!c2 || (c2_lo >= 0 && c2_hi >= c2_lo && c2_hi <= S && (c2_last == 0 || c2_last == 1)), "%s: bad compaction arguments", who);
-    return 0;
-}
-int d4_frame_attn_out(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                      const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                      const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                      int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh,
-                      const float* wo_t, int D, const float* resid, int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last,
-                      void* stream) {
-    const d4::SmallAttnArgs sa = frame_attn_args(q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride,
-                                                 g_item_stride, k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out_b, frames, heads, S,
-                                                 softclamp, mask_special, belief, dh);
-    if (int rc = frame_out_check("d4_frame_attn_out", resid, out, c2, S, c2_lo, c2_hi, c2_last)) return rc;
-    D4_REQUIRE(wo_t && ((uintptr_t)wo_t % 16) == 0 && ldr >= D && ldo >= D && (!c2 || ldc2 >= D), "d4_frame_attn_out: weight image missing / misaligned or a leading dimension below D");
-    return d4::frame_attn_out(sa, wo_t, D, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
-}
-int d4_attn_out_cols(const float* q, int64_t q_group_stride, int64_t q_item_stride, const float* k, int64_t k_group_stride, int64_t k_item_stride,
-                     const float* v, int64_t v_group_stride, int64_t v_item_stride, const float* gate, int64_t g_group_stride, int64_t g_item_stride,
-                     const float* k_gamma, const float* vres, int64_t r_group_stride, int64_t r_item_stride, const float* mix, int64_t m_group_stride,
-                     int64_t m_item_stride, uint16_t* out_b, int frames, int heads, int S, float softclamp, int mask_special, int belief, int dh,
-                     const float* W, int ldw, int D, const float* resid, int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last,
-                     void* stream) {
-    const d4::SmallAttnArgs sa = frame_attn_args(q, q_group_stride, q_item_stride, k, k_group_stride, k_item_stride, v, v_group_stride, v_item_stride, gate, g_group_stride,
-                                                 g_item_stride, k_gamma, vres, r_group_stride, r_item_stride, mix, m_group_stride, m_item_stride, out_b, frames, heads, S,
-                                                 softclamp, mask_special, belief, dh);
-    D4_REQUIRE(resid && out && (!c2 || (c2_lo >= 0 && c2_hi >= c2_lo && c2_hi <= S && (c2_last == 0 || c2_last == 1))), "d4_attn_out_cols: residual / output missing or bad compaction arguments");
-    D4_REQUIRE(W && ldw >= heads * 64 && ldr >= D && ldo >= D && (!c2 || ldc2 >= D), "d4_attn_out_cols: weights missing or a leading dimension below its width");
-    return d4::attn_out_cols(sa, W, ldw, D, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
-}
-int d4_frame_pool(const float* q, int ldq, const float* x, int ldx, const float* gate_w, const float* k, int ldk, const float* hid, int D,
-                  const float* k_gamma, int M, int L, int heads, float eps, const float* wv_t, const float* wo_t, int frames, int S, const float* resid,
-                  int ldr, float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream) {
-    d4::PoolMixArgs pm{};
-    pm.q = q; pm.ldq = ldq; pm.x = x; pm.ldx = ldx; pm.gate_w = gate_w; pm.k = k; pm.ldk = ldk; pm.hid = hid; pm.D = D; pm.k_gamma = k_gamma;
-    pm.M = M; pm.L = L; pm.heads = heads; pm.eps = eps;
-    if (int rc = frame_out_check("d4_frame_pool", resid, out, c2, S, c2_lo, c2_hi, c2_last)) return rc;
-    D4_REQUIRE(x && gate_w && hid && k_gamma && wv_t && wo_t && ((uintptr_t)wv_t % 16) == 0 && ((uintptr_t)wo_t % 16) == 0 && ((uintptr_t)q % 16) == 0 &&
-               ((uintptr_t)k % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)hid % 16) == 0 && ((uintptr_t)gate_w % 16) == 0 && ((uintptr_t)k_gamma % 16) == 0 &&
-               ldq % 4 == 0 && ldk % 4 == 0 && ldx % 4 == 0 && ldq >= heads * 64 && ldk >= heads * 64 && ldx >= D && ldr >= D && ldo >= D && (!c2 || ldc2 >= D),
-               "d4_frame_pool: operand missing / not 16-byte aligned or a leading dimension below its width");
-    return d4::frame_pool(pm, wv_t, wo_t, frames, S, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
-}
-int d4_frame_pool_tail(const float* u, const float* wv_t, const float* wo_t, int frames, int S, int D, int pool_heads, const float* resid, int ldr,
-                       float* out, int ldo, float* c2, int ldc2, int c2_lo, int c2_hi, int c2_last, void* stream) {
-    if (int rc = frame_out_check("d4_frame_pool_tail", resid, out, c2, S, c2_lo, c2_hi, c2_last)) return rc;
-    D4_REQUIRE(u && wv_t && wo_t && ((uintptr_t)u % 16) == 0 && ((uintptr_t)wv_t % 16) == 0 && ((uintptr_t)wo_t % 16) == 0 && ldr >= D && ldo >= D && (!c2 || ldc2 >= D),
-               "d4_frame_pool_tail: operand missing / not 16-byte aligned or a leading dimension below D");
-    return d4::frame_pool_tail(u, wv_t, wo_t, frames, S, D, pool_heads, resid, ldr, out, ldo, c2, ldc2, c2_lo, c2_hi, c2_last, static_cast<hipStream_t>(stream));
-}
-
-int d4_rmsnorm_backward(const float* x, const float* dy, const float* gamma, float* dx, float* d_gamma, float* scratch, int rows, int dim, float eps, void* stream) {
-    D4_REQUIRE(x && dy && gamma && dx && d_gamma && scratch, "d4_rmsnorm_backward: null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (rows == 0) return 0;
-    if (int rc = d4::rmsnorm_bwd(x, dy, gamma, scratch, dx, rows, dim, eps, s)) return rc;
-    return d4::colsum(scratch, dim, rows, dim, d_gamma, s);
-}
-
-// MultiCategorical.sample + log_prob of the sample (D4:485-497, 1374-1376, 1422-1423), stateless: Gumbel-max per action type from injected
-// uniforms (same shape as the logits), log-softmax gather.  action_sizes: device [na].
-int d4_categorical_sample_logp(const float* logits, int ld, const float* uniform, int ld_u, const int32_t* action_sizes, int rows, int na,
-                               float temperature, int64_t* actions, float* log_probs, void* stream) {
-    D4_REQUIRE(logits && uniform && action_sizes && actions && log_probs && rows >= 0 && na >= 1, "d4_categorical_sample_logp: bad arguments");
-    d4::SampleArgs sa{};
-    sa.logits = logits; sa.ld = ld; sa.gumbel_u = uniform; sa.ld_u = ld_u; sa.actions = actions; sa.act_stride = na; sa.log_probs = log_probs;
-    sa.lp_stride = na; sa.action_sizes = action_sizes; sa.B = rows; sa.na = na; sa.temperature = temperature;
-    return d4::sample_actions_terminals(sa, static_cast<hipStream_t>(stream));
-}
-int d4_hl_gauss_scalar(const float* logits, int ld, const float* centers, float* out, int rows, int bins, void* stream) {
-    return d4::hl_gauss_scalar(logits, ld, centers, out, 1, rows, bins, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
