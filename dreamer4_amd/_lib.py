@@ -282,6 +282,7 @@ SYMBOLS = {
     'd4_mask_rows_fwd': (_I, [_P] * 4 + [_I, _I, _P]),
     'd4_mask_rows_bwd': (_I, [_P] * 5 + [C.c_size_t, _I, _I, _P]),
     'd4_recon_loss_fwd_bwd': (_I, [_P] * 4 + [_I] * 7 + [_P, _P, _P, C.c_size_t, _P]),
+    'd4_pack_tokens_bf16': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

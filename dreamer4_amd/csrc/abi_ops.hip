@@ -215,6 +215,12 @@ int d4_pack_tokens(int which, float* tokens, float* compact, const float* pos, c
     return which == 0 ? d4::decoder_pack_tokens(tokens, compact, pos, img, lat, frames, P, n_lat, n_total, D, s)
                       : d4::encoder_pack_tokens(tokens, compact, img, lat, frames, P, n_lat, D, s);
 }
+int d4_pack_tokens_bf16(int which, float* tokens, uint16_t* tokens_b, float* compact, uint16_t* compact_b, const float* pos, const float* img, const float* lat,
+                        int frames, int P, int n_lat, int n_total, int D, void* stream) {
+    D4_REQUIRE(tokens && tokens_b && compact && img && lat && frames >= 0 && P >= 0 && n_lat >= 0 && D >= 1 && (which == 0 || which == 1), "d4_pack_tokens_bf16: bad arguments");
+    D4_REQUIRE(which == 1 || (pos && n_total >= n_lat), "d4_pack_tokens_bf16: the decoder form needs pos and n_total >= n_lat");
+    return d4::pack_tokens_img(which, tokens, tokens_b, compact, compact_b, pos, img, lat, frames, P, n_lat, which == 0 ? n_total : n_lat, D, static_cast<hipStream_t>(stream));
+}
 int d4_prep_eval_inputs(int32_t* sig, int64_t* pact, const int64_t* actions_hist, int B, int Tq, int na, int frame_base, int hist_stride, int sig_val, int ctx_sig,
                         float* pcont, const float* cont_hist, int nc, void* stream) {
     D4_REQUIRE(sig && B >= 1 && Tq >= 1 && na >= 0 && nc >= 0 && frame_base >= 0 && hist_stride >= frame_base + Tq - 1, "d4_prep_eval_inputs: bad arguments");

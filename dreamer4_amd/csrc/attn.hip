@@ -418,7 +418,10 @@ __global__ __launch_bounds__(256) void attn_wide_kernel(SmallAttnArgs p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] *= gt;
         }
-        if (kr == 0) *reinterpret_cast<f32x4*>(p.out + g * p.o_group_stride + i * p.o_item_stride + h * 64 + fg * 4) = o;
+        if (kr == 0) {
+            *reinterpret_cast<f32x4*>(p.out + g * p.o_group_stride + i * p.o_item_stride + h * 64 + fg * 4) = o;
+            if (p.out_b) store_bf16x4(p.out_b + g * p.o_group_stride + i * p.o_item_stride + h * 64 + fg * 4, o);      // the bf16 image of the same rows (bf16 engine)
+        }
     }
 }
 
@@ -430,6 +433,7 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
         D4_REQUIRE(p.q_lo == 0 && p.q_hi == 0, "attention: query restriction is not implemented in the wide kernel");
         D4_REQUIRE(((uintptr_t)p.q % 16) == 0 && (p.q_group_stride % 4) == 0 && (p.q_item_stride % 4) == 0 && ((uintptr_t)p.out % 16) == 0 &&
                    (p.o_group_stride % 4) == 0 && (p.o_item_stride % 4) == 0, "attention: the wide kernel needs 16-byte aligned query and output rows");
+        D4_REQUIRE(!p.out_b || ((uintptr_t)p.out_b % 8) == 0, "attention: the wide kernel needs an 8-byte aligned bf16 output image");
         const size_t lds = (size_t)(2 * p.nk * 64 + p.nk) * sizeof(float);
         static DeviceOnce attr_set;
         if (attr_set.need()) {
@@ -441,6 +445,7 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
         const double wide_bytes = 4.0 * p.groups * p.heads * p.dh * ((double)p.nq * 2 + (double)p.nk * (p.vres ? 3 : 2));
         D4_GLUE_LAUNCH(GL_ATTN_WIDE, wide_bytes, attn_wide_kernel, dim3(p.groups * p.heads), dim3(256), lds, stream, p);
         D4_LAUNCH_CHECK();
+        *wrote_b = true;                                   // (the kernel writes out_b beside out)
         return 0;
     }
     D4_REQUIRE(p.nk >= 1 && p.nk <= 64, "small_attn: nk=%d out of range [1,64]", p.nk);
@@ -505,8 +510,8 @@ static int small_attn_impl(const SmallAttnArgs& p, hipStream_t stream, bool* wro
     return 0;
 }
 
-// bf16 engine: `out_b` asks for a bf16 copy of the output (the next GEMM's activation image).  The matrix-pipe kernels write it themselves; the
-// other forms are followed by one conversion pass over the (contiguous) output rows.
+// bf16 engine: `out_b` asks for a bf16 copy of the output (the next GEMM's activation image).  The matrix-pipe kernels, attn_wide_kernel and the tiled
+// wide core write it themselves; the other forms are followed by one conversion pass over the (contiguous) output rows.
 int small_attn(const SmallAttnArgs& p, hipStream_t stream) {
     bool wrote_b = false;
     D4_REQUIRE(p.out != nullptr || p.out_b != nullptr, "small_attn: no output");
@@ -515,9 +520,10 @@ int small_attn(const SmallAttnArgs& p, hipStream_t stream) {
         D4_REQUIRE(false, "small_attn: out_b without out is not supported");
     }
     if (p.wide && (g_small_attn_wide || p.nq > 64 || p.nk > 64)) {
-        // wide frames (SmallAttnArgs::wide): the tiled matrix-pipe core (wide == 2: its bf16-product form); it writes the fp32 output only
+        // wide frames (SmallAttnArgs::wide): the tiled matrix-pipe core (wide == 2: its bf16-product form); its epilogue writes out_b beside out
         const char* form = nullptr;
         if (int rc = wide_attn(p, stream, &form)) return rc;
+        wrote_b = true;
         if (form) note_form(p.wide == 2 ? FAM_WIDE_ATTN_BF16 : FAM_WIDE_ATTN, form);
     } else
     if (int rc = small_attn_impl(p, stream, &wrote_b)) return rc;

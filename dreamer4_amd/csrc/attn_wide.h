@@ -162,9 +162,15 @@ __device__ __forceinline__ void wide_attn_body(const SmallAttnArgs& p) {
             for (int s = 0; s < NS; ++s) on[s] -= dot * vi[s];
         }
         const float gt = p.gate ? sigmoidf(p.gate[g * p.g_group_stride + (int64_t)qi * p.g_item_stride + h]) : 1.f;
-        float* orow = p.out + g * p.o_group_stride + (int64_t)qi * p.o_item_stride + h * DH + tok;
+        const int64_t ooff = g * p.o_group_stride + (int64_t)qi * p.o_item_stride + h * DH + tok;
+        float* orow = p.out + ooff;
 #pragma unroll
         for (int s = 0; s < NS; ++s) orow[16 * s] = on[s] * gt;
+        if (p.out_b) {                                      // the bf16 image of the same rows (bf16 engine): the value just stored, rounded to nearest even
+            uint16_t* brow = p.out_b + ooff;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) brow[16 * s] = bf16_bits(on[s] * gt);
+        }
     }
 }
 

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void wide_attn_bf16_kernel(SmallAttnArgs p) { 
 
 }  // namespace
 
-// Launches on arguments wide_attn (attn_wide_mfma.hip) has validated; *form names the kernel that ran.  `out_b` is left to small_attn's conversion pass.
+// Launches on arguments wide_attn (attn_wide_mfma.hip) has validated; *form names the kernel that ran.  `out_b` (optional) is written by the kernel's epilogue.
 int wide_attn_bf16_launch(const SmallAttnArgs& p, hipStream_t stream, const char** form) {
     D4_WIDE_ATTN_LAUNCH(wide_attn_bf16_kernel, p, stream, form);
     return 0;

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void wide_attn_kernel(SmallAttnArgs p) { wide_
 
 }  // namespace
 
-// Validates, then launches; *form names the kernel that ran (nullptr: nothing to do).  `out_b` is left to small_attn's conversion pass.
+// Validates, then launches; *form names the kernel that ran (nullptr: nothing to do).  `out_b` (optional) is written by the kernel's epilogue.
 int wide_attn(const SmallAttnArgs& p, hipStream_t stream, const char** form) {
     *form = nullptr;
     D4_REQUIRE(p.nq >= 1 && p.nk >= 1 && p.nq <= WIDE_ATTN_MAX && p.nk <= WIDE_ATTN_MAX,

@@ -46,6 +46,35 @@ int copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols
     return 0;
 }
 
+// copy_rows that also writes the bf16 image of the destination rows (same leading dimension), in the same pass: V = 4 columns per thread where
+// every row is 16-byte (image: 8-byte) aligned, one otherwise
+template <int V>
+__global__ __launch_bounds__(256) void copy_rows_img_kernel(const float* src, int lds, float* dst, uint16_t* dst_b, int ldd, int rows, int cols) {
+    const int cv = cols / V;
+    const int64_t n = (int64_t)rows * cv;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / cv;
+        const int c = (int)(i % cv) * V;
+        if constexpr (V == 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src + r * lds + c);
+            *reinterpret_cast<f32x4*>(dst + r * ldd + c) = v;
+            store_bf16x4(dst_b + r * ldd + c, v);
+        } else {
+            const float v = src[r * lds + c];
+            dst[r * ldd + c] = v;
+            dst_b[r * ldd + c] = bf16_bits(v);
+        }
+    }
+}
+int copy_rows_img(const float* src, int lds, float* dst, uint16_t* dst_b, int ldd, int rows, int cols, hipStream_t s) {
+    if (rows == 0 || cols == 0) return 0;
+    const bool v4 = cols % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0 && ((uintptr_t)dst_b % 8) == 0;
+    if (v4) hipLaunchKernelGGL(copy_rows_img_kernel<4>, grid1d((int64_t)rows * cols / 4), dim3(256), 0, s, src, lds, dst, dst_b, ldd, rows, cols);
+    else hipLaunchKernelGGL(copy_rows_img_kernel<1>, grid1d((int64_t)rows * cols), dim3(256), 0, s, src, lds, dst, dst_b, ldd, rows, cols);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void fill_kernel(float* dst, float v, int64_t n) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = v;
 }
@@ -580,6 +609,86 @@ int encoder_pack_tokens(float* tokens, float* compact, const float* img, const f
     const int64_t tot = (int64_t)frames * (P + n) * D;
     if (tot == 0) return 0;
     hipLaunchKernelGGL(encoder_pack_kernel, grid1d(tot), dim3(256), 0, s, tokens, compact, img, latent_tokens, frames, P, n, D);
+    D4_LAUNCH_CHECK();
+    return 0;
+}
+// Both pack forms with the bf16 image of the token rows (bf16 tokenizer engine): one thread owns V consecutive columns of one token row — reads the
+// fp32 sources once, writes the fp32 row, the compact copy and the V bf16 values of the row's image (and of the compact copy's, compact_b != null) in one store each (V = 8: 16 bytes; V = 4: 8 bytes for D % 8 == 4;
+// V = 1 otherwise).  The fp32 values are those of decoder_pack_kernel / encoder_pack_kernel (one add or none), the image their round-to-nearest-even.
+//   which 0 (decoder): row s < P = pos[s] + img[f][s], also to compact[f][s]; row s >= P = lat[f][s - P] of n_total rows
+//   which 1 (encoder): row s < P = img[f][s]; row s >= P = lat[s - P] (the learned latent tokens), also to compact[f][s - P]
+template <int V>
+__global__ __launch_bounds__(256) void pack_tokens_img_kernel(int which, float* tokens, uint16_t* tokens_b, float* compact, uint16_t* compact_b, const float* pos,
+                                                              const float* img, const float* lat, int frames, int P, int n_lat, int n_total, int D) {
+    typedef __bf16 bf16v __attribute__((ext_vector_type(V)));
+    typedef float f32v __attribute__((ext_vector_type(V)));
+    const int S = P + n_lat, DV = D / V;
+    const int64_t n = (int64_t)frames * S * DV;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int d = (int)(i % DV) * V;
+        const int s = (int)((i / DV) % S);
+        const int64_t f = i / ((int64_t)DV * S);
+        const int64_t row = f * S + s;
+        float v[V];
+        float* crow = nullptr;
+        int64_t coff = 0;                                    // crow - compact: the compact image's element
+        if (s < P) {
+            const float* a = img + (f * P + s) * D + d;
+            if (which == 0) {
+                const float* b = pos + (int64_t)s * D + d;
+                coff = (f * P + s) * D + d; crow = compact + coff;
+                if constexpr (V > 1) {
+                    const f32v av = *reinterpret_cast<const f32v*>(a), bv = *reinterpret_cast<const f32v*>(b);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) v[e] = bv[e] + av[e];
+                } else v[0] = b[0] + a[0];
+            } else {
+                if constexpr (V > 1) {
+                    const f32v av = *reinterpret_cast<const f32v*>(a);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) v[e] = av[e];
+                } else v[0] = a[0];
+            }
+        } else {
+            const float* a = which == 0 ? lat + (f * n_total + (s - P)) * D + d : lat + (int64_t)(s - P) * D + d;
+            if (which == 1) { coff = (f * n_lat + (s - P)) * D + d; crow = compact + coff; }
+            if constexpr (V > 1) {
+                const f32v av = *reinterpret_cast<const f32v*>(a);
+#pragma unroll
+                for (int e = 0; e < V; ++e) v[e] = av[e];
+            } else v[0] = a[0];
+        }
+        if constexpr (V > 1) {
+            f32v o;
+            bf16v ob;
+#pragma unroll
+            for (int e = 0; e < V; ++e) { o[e] = v[e]; ob[e] = (__bf16)v[e]; }
+            *reinterpret_cast<f32v*>(tokens + row * D + d) = o;
+            if (crow) *reinterpret_cast<f32v*>(crow) = o;
+            *reinterpret_cast<bf16v*>(tokens_b + row * D + d) = ob;
+            if (crow && compact_b) *reinterpret_cast<bf16v*>(compact_b + coff) = ob;
+        } else {
+            tokens[row * D + d] = v[0];
+            if (crow) crow[0] = v[0];
+            tokens_b[row * D + d] = bf16_bits(v[0]);
+            if (crow && compact_b) compact_b[coff] = bf16_bits(v[0]);
+        }
+    }
+}
+int pack_tokens_img(int which, float* tokens, uint16_t* tokens_b, float* compact, uint16_t* compact_b, const float* pos, const float* img, const float* lat,
+                    int frames, int P, int n_lat, int n_total, int D, hipStream_t s) {
+    const int64_t n = (int64_t)frames * (P + n_lat) * D;
+    if (n == 0) return 0;
+    auto al = [](const void* p, int b) { return ((uintptr_t)p % b) == 0; };
+    // the vector forms need every fp32 row 4 V bytes aligned and the image's rows 2 V bytes: whole-buffer alignment + D % V == 0
+    const bool f32_al32 = al(tokens, 32) && al(compact, 32) && al(img, 32) && al(lat, 32) && (!pos || al(pos, 32));
+    const bool f32_al16 = al(tokens, 16) && al(compact, 16) && al(img, 16) && al(lat, 16) && (!pos || al(pos, 16));
+    if (D % 8 == 0 && f32_al32 && al(tokens_b, 16) && (!compact_b || al(compact_b, 16)))
+        hipLaunchKernelGGL(pack_tokens_img_kernel<8>, grid1d(n / 8), dim3(256), 0, s, which, tokens, tokens_b, compact, compact_b, pos, img, lat, frames, P, n_lat, n_total, D);
+    else if (D % 4 == 0 && f32_al16 && al(tokens_b, 8) && (!compact_b || al(compact_b, 8)))
+        hipLaunchKernelGGL(pack_tokens_img_kernel<4>, grid1d(n / 4), dim3(256), 0, s, which, tokens, tokens_b, compact, compact_b, pos, img, lat, frames, P, n_lat, n_total, D);
+    else
+        hipLaunchKernelGGL(pack_tokens_img_kernel<1>, grid1d(n), dim3(256), 0, s, which, tokens, tokens_b, compact, compact_b, pos, img, lat, frames, P, n_lat, n_total, D);
     D4_LAUNCH_CHECK();
     return 0;
 }

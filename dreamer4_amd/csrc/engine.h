@@ -109,6 +109,8 @@ struct d4_engine {
     // One NON-GEMM consumer reads images too at D > 512: the attention pool's mix takes the bf16 images of the layer hiddens for its softmax-weighted
     // VALUE mix and its in-kernel RMS (fp32 before round 4) — an extra rounding of bf16 mode (a precision trade-off of that mode, not of the kernel), inside the
     // engine-level bf16-vs-fp32 bound of tests/test_gpu_bf16.py (config-5 shape: latents 7.7e-3 max, asserted < 3e-2).
+    // Decoder / encoder engines in bf16 mode have the same images plus three of their own — the compact slabs (written through GemmArgs::C2b and by the
+    // pack kernel), the final stage's rows xfc, the encoder's cross-attention output catt — and never hand the pool mix the hiddens' images.
     // `only`: nothing reads the fp32 buffer when the image exists (the producer may skip the fp32 store).
     struct Shadow { const float* src; size_t n; uint16_t* dst; bool only; };
     std::vector<Shadow> shadows;

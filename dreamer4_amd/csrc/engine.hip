@@ -173,11 +173,13 @@ int engine_layout(d4_engine* e, bool assign) {
         e->aexp_valid.assign(e->nslab, 0);
     }
     e->shadows.clear();
-    if (e->bf16 && !e->fp32_planes() && !e->decoder && !e->encoder) {
-        auto sh = [&](const float* src, size_t n, bool only) {
-            uint16_t* dst = reinterpret_cast<uint16_t*>(alloc_bytes(n * sizeof(uint16_t)));
-            e->shadows.push_back({src, n, dst, only});
-        };
+    auto sh = [&](const float* src, size_t n, bool only) {
+        uint16_t* dst = reinterpret_cast<uint16_t*>(alloc_bytes(n * sizeof(uint16_t)));
+        e->shadows.push_back({src, n, dst, only});
+    };
+    // (decoder / encoder engines in bf16 mode take the same images: engine_forward is one walk for the three modes — DESIGN.md 27)
+    const bool images = e->bf16 && !e->fp32_planes();
+    if (images) {
         sh(e->slabs, (size_t)e->nslab * M * D, false);
         sh(e->xpool, M * D, false);
         sh(e->att, M * hd, false);
@@ -207,6 +209,13 @@ int engine_layout(d4_engine* e, bool assign) {
     e->cq = fl(Fr * KQ * e->ldcq);
     e->ckv = fl(M * 2 * hd);
     e->catt = fl(Fr * KQ * hd);
+    if (images && (e->decoder || e->encoder)) {
+        // the tokenizer engines' final stage: the compact rows every product of it reads (the final pool's query projection; encoder: the special
+        // feedforward's input), and the encoder's cross-attention output in front of its output projection
+        sh(e->xfc, Fr * KR * D, false);
+        sh(e->cslabs, (size_t)e->nslab * Fr * KR * D, false);      // the final pool's hiddens: the producers' compact copies carry an image too (GemmArgs::C2b)
+        if (e->encoder) sh(e->catt, Fr * KQ * hd, false);
+    }
     e->lat_in = fl(Fr * n * dl);
     e->lkv = fl(Fr * n * 2 * hd);
     e->latt = fl(Fr * ns * hd);
@@ -540,6 +549,7 @@ static int attach_images(const d4_engine* e, GemmArgs& g, uint16_t** cb) {
     D4_REQUIRE(g.Ab || !e->shadow_only(g.A), "bf16 engine: a GEMM (M=%d N=%d K=%d) reads a bf16-only activation buffer but cannot take the bf16-activation kernel", g.M, g.N, g.K);
     if (!g.Ab) return 0;
     g.Cb = *cb;
+    if (g.C2) g.C2b = e->shadow_of(g.C2);                // (the compact copies have images on the tokenizer engines only)
     if (*cb && e->shadow_only(g.C) && !(g.flags & GEMM_ACCUMULATE)) g.C = nullptr;
     return 0;
 }
@@ -564,6 +574,8 @@ static int engine_gemm(const EvalCtx& cx, GemmArgs& g) {
     const int ncol = (g.flags & GEMM_SWIGLU) ? g.N / 2 : g.N;
     for (int b = 0; b < nb; ++b)
         if (int rc = cvt_rows_bf16(g.C + b * g.strideC, g.ldc, cb + b * g.strideC, g.ldc, g.M, ncol, s)) return rc;
+    if (g.C2) if (uint16_t* c2b = e->shadow_of(g.C2))      // ... and the compact copy's, where it has one: (kept rows per frame) x frames
+        return cvt_rows_bf16(g.C2, g.ldc2, c2b, g.ldc2, (g.M / g.c2_S) * (g.c2_hi - g.c2_lo + (g.c2_last ? 1 : 0)), ncol, s);
     return 0;
 }
 
@@ -620,6 +632,37 @@ static int gemm_c2(const EvalCtx& cx, const float* A, int lda, const float* W, i
     GemmArgs g{A, lda, W, ldw, C, ldc, bias, R, ldr, M, N, K, flags, RMS_EPS, 0};
     g.C2 = C2; g.ldc2 = N; g.c2_S = S; g.c2_lo = cx.keep_lo; g.c2_hi = cx.keep_hi; g.c2_last = has_agent;
     return engine_gemm(cx, g);
+}
+
+// Starts the mirror arena over and mirrors the weights the TRUNK's GEMMs read (prepared images + the raw output projections): the layers, the attention
+// pools and — unless the engine is a decoder, whose special token nothing reads — the final special cross-attention and feedforward.  The decoder and
+// encoder engines mirror nothing else: their four end projections stay on the f32-input kernels (engine_forward: ends).
+static int mirror_trunk(d4_engine* e, hipStream_t s) {
+    const d4_config& c = e->c;
+    const int D = e->D, hd = e->hd, h = c.attn_heads, hp = e->hp;
+    int rc;
+    e->mirrors.clear(); e->bf16_used = 0;
+    e->wscale_used = 0;
+    auto mir = [&](const float* w, size_t rows, int ld) { return mirror_weight(e, w, rows, ld, s); };
+    for (int l = 0; l < c.depth; ++l) {
+        if ((rc = mir(e->proj_w[l], (size_t)(l == 0 ? e->Nproj0 : e->Nproj), D))) return rc;
+        if ((rc = mir(e->layer_attn[l].to_out, (size_t)D, hd))) return rc;
+    }
+    for (int l = 0; l < c.depth + (e->decoder ? 0 : 1); ++l) {
+        if ((rc = mir(e->ffp[l].w1, (size_t)2 * e->inner_pad, D))) return rc;
+        if ((rc = mir(e->ffp[l].w2, (size_t)D, e->inner_pad))) return rc;
+    }
+    for (int p = 0; p < c.depth; ++p) {
+        if ((rc = mir(e->pq_w[p], (size_t)(hp + e->php), D))) return rc;
+        if ((rc = mir(e->pkv_w[p], (size_t)2 * hp, D))) return rc;
+        if ((rc = mir(e->pools[p].to_out, (size_t)D, hp))) return rc;
+    }
+    for (int l = 0; l < (int)e->pkq_w.size(); ++l)
+        if ((rc = mir(e->pkq_w[l], (size_t)(c.depth - l) * hp, D))) return rc;
+    if (e->decoder) return 0;
+    if ((rc = mir(e->cq_w, (size_t)(hd + h), D))) return rc;
+    if ((rc = mir(e->ckv_w, (size_t)2 * hd, D))) return rc;
+    return mir(e->cross.to_out, (size_t)D, hd);
 }
 
 int engine_prepare(d4_engine* e, hipStream_t s) {
@@ -701,6 +744,7 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
         // final RMSNorm of the trunk folded into the patch projection: W . diag(gamma), 1 / rms applied inside the GEMM   D4:3246, 3555
         if ((rc = fold_rows(e->t2p_w, e->final_norm, e->t2p_wf, e->dim_patch, D, D, s))) return rc;
         if ((rc = fill_f32(e->zerosD, 0.f, 2 * D > e->dim_patch ? 2 * D : e->dim_patch, s))) return rc;
+        if (e->bf16 && (rc = mirror_trunk(e, s))) return rc;
         D4_HIP(hipStreamSynchronize(s));
         e->prepared = true;
         return 0;
@@ -712,6 +756,7 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
     if (e->encoder) {
         // final RMSNorm of the trunk folded into the latent bottleneck: W . diag(gamma), 1 / rms inside the GEMM   D4:3246, 4408
         if ((rc = fold_rows(e->e2l_w, e->final_norm, e->t2p_wf, c.dim_latent, D, D, s))) return rc;
+        if (e->bf16 && (rc = mirror_trunk(e, s))) return rc;
         D4_HIP(hipStreamSynchronize(s));
         e->prepared = true;
         return 0;
@@ -740,27 +785,8 @@ int engine_prepare(d4_engine* e, hipStream_t s) {
 
     // ---- bf16 mirrors of everything the trunk's GEMMs read (prepared images above + the raw output projections)
     if (e->bf16) {
-        e->mirrors.clear(); e->bf16_used = 0;
-        e->wscale_used = 0;
+        if ((rc = mirror_trunk(e, s))) return rc;
         auto mir = [&](const float* w, size_t rows, int ld) { return mirror_weight(e, w, rows, ld, s); };
-        for (int l = 0; l < c.depth; ++l) {
-            if ((rc = mir(e->proj_w[l], (size_t)(l == 0 ? e->Nproj0 : e->Nproj), D))) return rc;
-            if ((rc = mir(e->layer_attn[l].to_out, (size_t)D, hd))) return rc;
-        }
-        for (int l = 0; l <= c.depth; ++l) {
-            if ((rc = mir(e->ffp[l].w1, (size_t)2 * e->inner_pad, D))) return rc;
-            if ((rc = mir(e->ffp[l].w2, (size_t)D, e->inner_pad))) return rc;
-        }
-        for (int p = 0; p < c.depth; ++p) {
-            if ((rc = mir(e->pq_w[p], (size_t)(hp + e->php), D))) return rc;
-            if ((rc = mir(e->pkv_w[p], (size_t)2 * hp, D))) return rc;
-            if ((rc = mir(e->pools[p].to_out, (size_t)D, hp))) return rc;
-        }
-        for (int l = 0; l < (int)e->pkq_w.size(); ++l)
-            if ((rc = mir(e->pkq_w[l], (size_t)(c.depth - l) * hp, D))) return rc;
-        if ((rc = mir(e->cq_w, (size_t)(hd + h), D))) return rc;
-        if ((rc = mir(e->ckv_w, (size_t)2 * hd, D))) return rc;
-        if ((rc = mir(e->cross.to_out, (size_t)D, hd))) return rc;
         if (ns == n) {
             if ((rc = mir(e->lin_w, (size_t)D, dl))) return rc;
             if ((rc = mir(e->lout_w, (size_t)dl, D))) return rc;
@@ -913,7 +939,8 @@ static int pool_block(const EvalCtx& cx, d4_engine* e, int p, const float* x, fl
         }
         pm.x = x; pm.ldx = D; pm.gate_w = e->pq_w[p] + (size_t)hp * D; pm.hid = hiddens; pm.D = D; pm.k_gamma = a.k_gamma;
         pm.u = e->pool_u; pm.M = M; pm.L = L; pm.heads = c.pool_heads; pm.eps = RMS_EPS; pm.rule_M = rule_M;
-        if (cx.img && D > 512) pm.hid_b = cx.img->shadow_of(hiddens);     // (D <= 512 may take the block-per-row form, which reads fp32)
+        // (D <= 512 may take the block-per-row form, which reads fp32; the tokenizer engines keep the value mix on the fp32 hiddens at every D: DESIGN.md 27)
+        if (cx.img && D > 512 && !e->decoder && !e->encoder) pm.hid_b = cx.img->shadow_of(hiddens);
         if (cx.img) if (uint16_t* ub = cx.img->shadow_of(e->pool_u)) { pm.u_b = ub; if (cx.img->shadow_only(e->pool_u)) pm.u = nullptr; }   // only the value GEMM reads the mixes
         // per-frame fused form (mix -> value projection -> output projection + residual in one kernel) where a frame per workgroup fills the chip;
         // frame_fused mode 2 (test hook): the mix stays its own kernel and only the tail is fused
@@ -1029,20 +1056,28 @@ static int engine_forward_impl(const EvalCtx& cx, d4_engine* e, const float* lat
     const int nkeep = e->decoder ? e->P : (e->encoder ? n : ck + has_agent), Mc = Fr * nkeep;          // rows the final stage reads
     auto cslab = [&](int j) { return e->cslabs + (size_t)j * Mc * D; };
     const bool same_len = ns == n;
+    // The tokenizer engines' four END projections (patch rows -> tokens, latents -> decoder tokens, tokens -> patch rows, latent tokens -> latents) read or
+    // write pixels and latents directly: they stay on the f32-input kernels in every mode — `ends` is the context without mirrors
+    const EvalCtx ends{nullptr, s, cx.keep_lo, cx.keep_hi, cx.sig_uniform};
+    uint16_t* slab0_b = cx.img ? cx.img->shadow_of(slab0) : nullptr;
+    uint16_t* cslab0_b = cx.img ? cx.img->shadow_of(e->cslabs) : nullptr;
+    bool slab0_b_done = false;                // the pack kernel wrote slab 0's image in its own pass
     if (e->encoder) {
         // tokens = [patch tokens of the video | learned latent tokens] (D4:4307, 4361-4376); patch rows were laid out in e->dec_in
         const int P = e->P, dp = e->dim_patch;
-        if ((rc = gemm_simple(cx, e->dec_in, dp, e->ptt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->ptt_b, nullptr, 0))) return rc;
+        if ((rc = gemm_simple(ends, e->dec_in, dp, e->ptt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->ptt_b, nullptr, 0))) return rc;
         if ((rc = layernorm_rows(e->img_tok, D, e->ptt_ln, nullptr, e->img_tok, D, Fr * P, D, 1e-5f, 0, s))) return rc;
-        if ((rc = encoder_pack_tokens(slab0, e->cslabs, e->img_tok, e->latent_tokens, Fr, P, n, D, s))) return rc;
+        if (slab0_b) { if ((rc = pack_tokens_img(1, slab0, slab0_b, e->cslabs, cslab0_b, nullptr, e->img_tok, e->latent_tokens, Fr, P, n, n, D, s))) return rc; slab0_b_done = true; }
+        else if ((rc = encoder_pack_tokens(slab0, e->cslabs, e->img_tok, e->latent_tokens, Fr, P, n, D, s))) return rc;
     } else if (e->decoder) {
         // tokens = [pos_emb + patch tokens of the noised video | latent tokens] (D4:3625-3654); `latents` here are the latent TOKENS
         // input row-major [Fr][n][dl]; the noised video's patch rows were laid out in e->dec_in by d4_decoder_forward
         const int P = e->P, dp = e->dim_patch;
-        if ((rc = gemm_simple(cx, e->dec_in, dp, e->npt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->npt_b, nullptr, 0))) return rc;
+        if ((rc = gemm_simple(ends, e->dec_in, dp, e->npt_w, dp, e->img_tok, D, Fr * P, D, dp, 0, e->npt_b, nullptr, 0))) return rc;
         if ((rc = layernorm_rows(e->img_tok, D, e->npt_ln, nullptr, e->img_tok, D, Fr * P, D, 1e-5f, 0, s))) return rc;
-        if ((rc = gemm_simple(cx, latents, dl, e->ld_w, dl, e->lat_tok, D, Fr * n, D, dl, 0, e->time_embed + (size_t)step_log2 * D, nullptr, 0))) return rc;
-        if ((rc = decoder_pack_tokens(slab0, e->cslabs, e->pos_emb, e->img_tok, e->lat_tok, Fr, P, n - 1, n, D, s))) return rc;
+        if ((rc = gemm_simple(ends, latents, dl, e->ld_w, dl, e->lat_tok, D, Fr * n, D, dl, 0, e->time_embed + (size_t)step_log2 * D, nullptr, 0))) return rc;
+        if (slab0_b) { if ((rc = pack_tokens_img(0, slab0, slab0_b, e->cslabs, cslab0_b, e->pos_emb, e->img_tok, e->lat_tok, Fr, P, n - 1, n, D, s))) return rc; slab0_b_done = true; }
+        else if ((rc = decoder_pack_tokens(slab0, e->cslabs, e->pos_emb, e->img_tok, e->lat_tok, Fr, P, n - 1, n, D, s))) return rc;
     } else {
     // ---- latents -> spatial tokens (LearnedQueriesAttentionPool, D4:7168; a plain Linear when there is one per latent)
     if (same_len) {
@@ -1094,7 +1129,7 @@ static int engine_forward_impl(const EvalCtx& cx, d4_engine* e, const float* lat
         if ((rc = engine_gemm(cx, gb))) return rc;
     }
     }
-    if (cx.img) if (uint16_t* sb = cx.img->shadow_of(slab0)) { if ((rc = cvt_rows_bf16(slab0, D, sb, D, M, D, s))) return rc; }
+    if (slab0_b && !slab0_b_done) { if ((rc = cvt_rows_bf16(slab0, D, slab0_b, D, M, D, s))) return rc; }
 
     // ---- trunk (AxialSpaceTimeTransformer.forward, D4:3040-3223)
     // Denoise steps (no agent embedding wanted): nothing downstream reads the last layer's flow / register / action rows, so a last space layer attends
@@ -1225,6 +1260,9 @@ static int engine_forward_impl(const EvalCtx& cx, d4_engine* e, const float* lat
     // [Fr][1][D], and the pool's products run on Fr rows in the kernel family they have at Fr * (ns + 1) rows (pool_block: rule_M).
     float* xfc = e->xfc;
     const float* last = slab(2 * c.depth);
+    if (uint16_t* xb = cx.img ? cx.img->shadow_of(xfc) : nullptr) {          // (tokenizer engines in bf16 mode: the copy writes the rows' image too)
+        if ((rc = copy_rows_img(cslab(2 * c.depth), D, xfc, xb, D, Mc, D, s))) return rc;
+    } else
     if ((rc = copy_rows(cslab(2 * c.depth), D, xfc, D, Mc, D, s))) return rc;
     if (e->encoder) {
         // the n latent (special) tokens of each frame cross-attend its P patch tokens, then their own feedforward (D4:3227-3238);
@@ -1243,18 +1281,19 @@ static int engine_forward_impl(const EvalCtx& cx, d4_engine* e, const float* lat
         sa.out = e->catt; sa.o_group_stride = (int64_t)n * hd; sa.o_item_stride = hd;
         sa.groups = Fr; sa.heads = h; sa.nq = n; sa.nk = P;
         sa.wide = e->attn_wide();
+        sa.out_b = cx.img ? cx.img->shadow_of(e->catt) : nullptr;
         if ((rc = small_attn(sa, s))) return rc;
         if ((rc = gemm_simple(cx, e->catt, hd, e->cross.to_out, hd, xfc, D, Mc, D, hd, 0, nullptr, spec, D))) return rc;
         if ((rc = ff_block(cx, e, e->ffp[c.depth], e->sff.out_b, xfc, D, xfc, D, Mc))) return rc;
         if ((rc = pool_block(cx, e, c.depth - 1, xfc, xfc, e->nslab, Mc, e->cslabs))) return rc;
         // final RMSNorm (folded) -> encoded_to_latents -> tanh                                   D4:3246, 4408, 4417
-        if ((rc = gemm_simple(cx, xfc, D, e->t2p_wf, D, e->enc_out, c.dim_latent, Mc, c.dim_latent, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0))) return rc;
+        if ((rc = gemm_simple(ends, xfc, D, e->t2p_wf, D, e->enc_out, c.dim_latent, Mc, c.dim_latent, D, GEMM_RMS_ROWSCALE, nullptr, nullptr, 0))) return rc;
         return tanh_rows(e->enc_out, e->enc_out, (int64_t)Mc * c.dim_latent, s);
     }
     if (e->decoder) {
         // final attention pool on the patch rows, then final RMSNorm (folded) -> Linear(dim, channels * patch^2)   D4:3242-3246, 3555
         if ((rc = pool_block(cx, e, c.depth - 1, xfc, xfc, e->nslab, Mc, e->cslabs))) return rc;
-        return gemm_simple(cx, xfc, D, e->t2p_wf, D, e->dec_out, e->dim_patch, Mc, e->dim_patch, D, GEMM_RMS_ROWSCALE, e->t2p_b, nullptr, 0);
+        return gemm_simple(ends, xfc, D, e->t2p_wf, D, e->dec_out, e->dim_patch, Mc, e->dim_patch, D, GEMM_RMS_ROWSCALE, e->t2p_b, nullptr, 0);
     }
     if (need_agent) {
         // agent token cross-attends the non-special tokens of its frame, then its own feedforward (D4:3227-3238)
@@ -1443,7 +1482,9 @@ int d4_engine_create(const d4_config* cfg, d4_engine** out) {
                    "decoder mode: image %d x %d must be a positive multiple of the patch size %d", c.image_height, c.image_width, c.patch_size);
         D4_REQUIRE((c.channels * c.patch_size * c.patch_size) % 4 == 0, "decoder mode: channels * patch_size^2 must be a multiple of 4");
         D4_REQUIRE(encoder || c.decoder_flow_steps >= 1, "decoder mode: decoder_flow_steps >= 1 (the flow decoder is the reference's default, D4:3875)");
-        D4_REQUIRE(c.num_discrete_action_types == 0 && c.num_continuous_actions == 0 && c.matmul_bf16 == 0, "decoder mode: no actions / bf16");
+        D4_REQUIRE(c.num_discrete_action_types == 0 && c.num_continuous_actions == 0, "decoder mode: no actions");
+        D4_REQUIRE(c.matmul_bf16 == 0 || c.matmul_bf16 == 1,
+                   "decoder / encoder mode: matmul_bf16=%d: 0 (fp32) or 1 (bf16) is implemented; 2 (split-operand fp32) and 3 (fp32_fp16x2) are dynamics-only", c.matmul_bf16);
         D4_REQUIRE(c.decoder_pos_mlp_depth >= 0 && c.decoder_pos_mlp_depth <= 6, "decoder_pos_mlp_depth out of range");
     }
     D4_REQUIRE((c.max_steps & (c.max_steps - 1)) == 0, "max_steps must be a power of two");

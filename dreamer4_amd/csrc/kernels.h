@@ -282,6 +282,7 @@ int attn_form_name(const char* family, int i, const char** name); // number of f
 // ------------------------------------------------------------------------------------ elementwise / glue
 int fold_rows(const float* W, const float* gamma, float* out, int rows, int K, int ld_out, hipStream_t s);
 int copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, hipStream_t s);
+int copy_rows_img(const float* src, int lds, float* dst, uint16_t* dst_b, int ldd, int rows, int cols, hipStream_t s);      // ... and dst's bf16 image in the same pass
 int fill_f32(float* dst, float v, int64_t n, hipStream_t s);
 int swiglu_pack_rows(const float* W, const float* bias, const float* gamma, float* Wp, float* bp,
                      int inner, int inner_pad, int K, hipStream_t s);
@@ -391,6 +392,10 @@ int patches_to_video(const float* patches, float* video, int B, int C, int T, in
 int decoder_pack_tokens(float* tokens, float* compact, const float* pos, const float* img, const float* lat, int frames, int P, int n_lat, int n_total, int D, hipStream_t s);
 int coord_grid(float* out, int nh, int nw, int ld, hipStream_t s);
 int encoder_pack_tokens(float* tokens, float* compact, const float* img, const float* latent_tokens, int frames, int P, int n, int D, hipStream_t s);
+// either pack form (which 0: decoder, 1: encoder; lat = the latent rows / the learned latent tokens) that also writes the bf16 image of the token rows
+// and, compact_b != null, of the compact copy
+int pack_tokens_img(int which, float* tokens, uint16_t* tokens_b, float* compact, uint16_t* compact_b, const float* pos, const float* img, const float* lat,
+                    int frames, int P, int n_lat, int n_total, int D, hipStream_t s);
 int tanh_rows(const float* x, float* y, int64_t n, hipStream_t s);
 int cunembed_gather(const float* U, float* w, int nc, int mtp, int d, hipStream_t s);
 int cunembed_scatter_grad(const float* g, float* dU, int nc, int mtp, int d, hipStream_t s);

@@ -48,7 +48,7 @@ class VideoTokenizer(SaveLoad, nn.Module):
     def __init__(self, dim, dim_latent, patch_size, image_size=None, image_height=None, image_width=None, num_latent_tokens=64,
                  encoder_depth=4, decoder_depth=4, time_block_every=4, attn_dim_head=64, attn_heads=8, decoder_pos_mlp_depth=2,
                  channels=3, decoder_flow_steps=1, head_mlp_recipe='pre_rms', wide_frames=False, attn_products='fp32',
-                 train_wide_frames=False, lpips_loss_weight=0.2, decoder_v_space_loss=True, **kwargs):
+                 train_wide_frames=False, lpips_loss_weight=0.2, decoder_v_space_loss=True, matmul_dtype='fp32', **kwargs):
         """`wide_frames` is not a reference argument: False (default) the decoder and encoder engines take at most 160 tokens (patches +
         latents) and 64 latent tokens per frame; True up to 1024 of each, on the tiled attention core of csrc/attn_wide_mfma.hip above 64
         items per side, and encoder / decoder trunks of depth >= 32 (up to 1024 pooled layer hiddens, the chunked pool mix of
@@ -58,6 +58,13 @@ class VideoTokenizer(SaveLoad, nn.Module):
         (csrc/attn_wide_bf16.hip).  Attentions of at most 64 items per side keep their kernels and bits.
         `train_wide_frames` (not a reference argument, the meaning it has on DynamicsWorldModel): False (default) the training forward takes at
         most 64 tokens (patches + latents) per frame; True up to 1024, on the tiled training attention core.
+        `matmul_dtype` is not a reference argument either: 'fp32' (default) every GEMM of `decode` and `tokenize` on the f32-input MFMA, as ever
+        and bit for bit; 'bf16' the Linears inside the two trunks (fused q|k|v|gates|mix projection, attention output, both feedforward projections,
+        the attention pools' key / value / output projections, the encoder's final special cross-attention and feedforward) on bf16-rounded operands
+        with fp32 accumulation — the kernels of the bf16 dynamics engine.  Norms, attention cores (unless `attn_products='bf16'`), softmax, the
+        residual stream, the Euler step and the four end projections (patch rows -> tokens and its LayerNorm, latents -> decoder tokens, tokens ->
+        patch rows, latent tokens -> latents and the tanh) stay fp32.  Independent of `wide_frames`, `attn_products`,
+        `train_wide_frames` and of a world model's own `matmul_dtype`.  The training `forward` stays fp32 whatever the option says.
         `lpips_loss_weight` and `decoder_v_space_loss` are the reference's; the first is only stored (any value constructs, `forward` needs 0.)."""
         config = dict(locals())
         super().__init__()
@@ -92,6 +99,9 @@ class VideoTokenizer(SaveLoad, nn.Module):
         if attn_products == 'bf16' and not self.wide_frames:
             raise ValueError("attn_products='bf16' needs wide_frames=True: only the wide attention core has a bf16 form")
         self.attn_products = attn_products
+        if matmul_dtype not in ('fp32', 'bf16'):
+            raise ValueError("matmul_dtype must be 'fp32' or 'bf16'")
+        self.matmul_dtype = matmul_dtype
         self.latent_shape = (num_latent_tokens, dim_latent)
         self.ff_inner = int(dim * 4 * 2 / 3)
         self._build_parameters()
@@ -215,6 +225,24 @@ class VideoTokenizer(SaveLoad, nn.Module):
         except Exception:
             pass
 
+    def _make_config(self, mode, caps):
+        """The engine configuration of `mode` (1 decoder, 2 encoder) sized for caps = (batch, frames).  Host only: no device is touched."""
+        c = _lib.Config()
+        c.mode = mode
+        c.dim, c.dim_latent, c.num_latent_tokens = self.dim, self.dim_latent, self.num_latent_tokens
+        c.depth = self.decoder_depth if mode == 1 else self.encoder_depth
+        c.time_block_every, c.attn_heads, c.attn_dim_head, c.attn_softclamp_value = self.time_block_every, self.attn_heads, self.attn_dim_head, 50.
+        c.num_spatial_tokens, c.num_register_tokens, c.max_steps, c.multi_token_pred_len = 0, 0, 64, 1
+        c.reward_num_bins = c.value_num_bins = 3
+        c.pool_heads, c.pool_dim_head = 4, 64
+        c.head_mlp_recipe = MLP_RECIPES[self.head_mlp_recipe]
+        c.patch_size, c.channels, c.image_height, c.image_width = self.patch_size, self.channels, self.image_height, self.image_width
+        c.decoder_flow_steps, c.decoder_pos_mlp_depth = self.decoder_flow_steps, self.decoder_pos_mlp_depth
+        c.max_batch, c.max_frames, c.max_parallel_frames, c.max_learn_rows = caps[0], caps[1], caps[1], 0
+        c.wide_frames = 3 if self.attn_products == 'bf16' else int(self.wide_frames)
+        c.matmul_bf16 = 1 if self.matmul_dtype == 'bf16' else 0
+        return c
+
     def _ensure_engine(self, batch, frames, mode=1):
         if self.device.type != 'cuda':
             raise _lib.D4Error('VideoTokenizer runs only on an MI355X (HIP) device: there is no CPU fallback')
@@ -226,19 +254,7 @@ class VideoTokenizer(SaveLoad, nn.Module):
             if st['engine'] is not None:
                 lib.d4_engine_destroy(st['engine'])
                 st['engine'] = None
-            c = _lib.Config()
-            c.mode = mode
-            c.dim, c.dim_latent, c.num_latent_tokens = self.dim, self.dim_latent, self.num_latent_tokens
-            c.depth = self.decoder_depth if mode == 1 else self.encoder_depth
-            c.time_block_every, c.attn_heads, c.attn_dim_head, c.attn_softclamp_value = self.time_block_every, self.attn_heads, self.attn_dim_head, 50.
-            c.num_spatial_tokens, c.num_register_tokens, c.max_steps, c.multi_token_pred_len = 0, 0, 64, 1
-            c.reward_num_bins = c.value_num_bins = 3
-            c.pool_heads, c.pool_dim_head = 4, 64
-            c.head_mlp_recipe = MLP_RECIPES[self.head_mlp_recipe]
-            c.patch_size, c.channels, c.image_height, c.image_width = self.patch_size, self.channels, self.image_height, self.image_width
-            c.decoder_flow_steps, c.decoder_pos_mlp_depth = self.decoder_flow_steps, self.decoder_pos_mlp_depth
-            c.max_batch, c.max_frames, c.max_parallel_frames, c.max_learn_rows = caps[0], caps[1], caps[1], 0
-            c.wide_frames = 3 if self.attn_products == 'bf16' else int(self.wide_frames)
+            c = self._make_config(mode, caps)
             eng = C.c_void_p()
             _lib.check(lib.d4_engine_create(C.byref(c), C.byref(eng)))
             st['engine'], st['caps'] = eng, caps
@@ -349,7 +365,8 @@ class VideoTokenizer(SaveLoad, nn.Module):
         """VideoTokenizer.forward (dreamer4.py:4239-4603) for the supported subset: video (b, c, t, h, w) or images (b, c, h, w) -> total loss, or
         (total, (TokenizerLosses, reconstruction)) with `return_intermediates`, or the latents (with gradient) with `return_latents`.
         `draws` = dict(patch_mask=, time_indices=, noise=) injects the random draws (parity runs; a missing entry is drawn); otherwise they
-        come from `generator` on the device.  More than 64 tokens per frame need `train_wide_frames=True`."""
+        come from `generator` on the device.  More than 64 tokens per frame need `train_wide_frames=True`.  The training forward is fp32:
+        `matmul_dtype='bf16'` changes `decode` and `tokenize` only."""
         from dreamer4_amd import trunk_ops
         for name, val in (('time_lens', time_lens), ('time_cache', time_cache), ('byol_target_latents', byol_target_latents)):
             if val is not None:

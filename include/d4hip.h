@@ -60,7 +60,8 @@ typedef struct d4_config {
                                                    csrc/gemm_x3.hip) — the Python mirror's default; 1: bf16 MFMA (bf16-rounded weights +
                                                    activations, fp32 accumulate, fp32 norms / softmax / residual stream); 3: opt-in fp32-class mode on
                                                    the fp16 matrix cores (two fp16 planes per operand under exact row scales, three products:
-                                                   csrc/gemm_h2.hip, see d4_gemm_split2) */
+                                                   csrc/gemm_h2.hip, see d4_gemm_split2).  Decoder / encoder mode: 0 or 1 (the trunk's Linears; the
+                                                   four end projections stay fp32), 2 and 3 are refused */
     int32_t head_mlp_recipe;                    /* D4_MLP_PRE_RMS / D4_MLP_POST_LAYER: layer recipe of the policy / value / terminal MLPs (engine.h) */
     int32_t continuous_beta_param;              /* D4_BETA_SOFTPLUS_P1 / D4_BETA_EXP_P1: link of the Beta head's raw parameters (csrc/beta.h) */
     int32_t pool_heads, pool_dim_head;          /* AttentionPool defaults 4 x 64 (D4:2147-2148) */
@@ -893,6 +894,12 @@ int d4_mask_rows_fwd(const float* x, const uint8_t* mask, const float* token, fl
 int d4_mask_rows_bwd(const float* dy, const uint8_t* mask, float* dx, float* dtoken, float* part, size_t part_floats, int rows, int dim, void* stream);
 int d4_recon_loss_fwd_bwd(const float* recon_rows, const float* video, const float* noise, const float* t, int B, int C, int T, int nh, int nw, int ps, int v_space,
                           float* loss, float* d_rows, float* part, size_t part_floats, void* stream);
+/* d4_pack_tokens that also writes the bf16 image of the token rows (the bf16 tokenizer engine's slab 0, VideoTokenizer(matmul_dtype='bf16');
+ * DESIGN.md 27): tokens and compact carry d4_pack_tokens' bits, tokens_b [frames * (P + n_lat)][D] their round-to-nearest-even bf16 values, written
+ * by the same pass (16-byte stores at D % 8 == 0 with 32-byte aligned fp32 buffers and a 16-byte aligned image, 8-byte stores at D % 4 == 0,
+ * element stores otherwise).  compact_b (may be null): the bf16 image of `compact`, same layout, likewise.  Nothing past the rows named is written. */
+int d4_pack_tokens_bf16(int which, float* tokens, uint16_t* tokens_b, float* compact, uint16_t* compact_b, const float* pos, const float* img, const float* lat,
+                        int frames, int P, int n_lat, int n_total, int D, void* stream);
 
 #ifdef __cplusplus
 }
