@@ -8,6 +8,7 @@ from dreamer4_amd.experience import Actions, Experience, combine_experiences
 from dreamer4_amd.world_model import DynamicsWorldModel, TimeCache
 from dreamer4_amd.trainer import DreamTrainer
 from dreamer4_amd.tokenizer import VideoTokenizer
+from dreamer4_amd.optim import MuonAdamAtan2
 from dreamer4_amd import ops  # noqa: F401  (registers torch.ops.d4hip.*)
 
-__all__ = ['Actions', 'Experience', 'combine_experiences', 'DynamicsWorldModel', 'TimeCache', 'DreamTrainer', 'VideoTokenizer']
+__all__ = ['Actions', 'Experience', 'combine_experiences', 'DynamicsWorldModel', 'TimeCache', 'DreamTrainer', 'VideoTokenizer', 'MuonAdamAtan2']

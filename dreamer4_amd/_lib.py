@@ -129,7 +129,7 @@ class ValueLossDesc(C.Structure):
 
 
 # every symbol include/d4hip.h declares: (restype, argtypes)
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
+_P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_double
 SYMBOLS = {
     'd4_last_error': (C.c_char_p, []),
     'd4_version': (_I, []),
@@ -283,6 +283,16 @@ SYMBOLS = {
     'd4_mask_rows_bwd': (_I, [_P] * 5 + [C.c_size_t, _I, _I, _P]),
     'd4_recon_loss_fwd_bwd': (_I, [_P] * 4 + [_I] * 7 + [_P, _P, _P, C.c_size_t, _P]),
     'd4_pack_tokens_bf16': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'd4_muon_plan_create': (_I, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(_P)]),
+    'd4_muon_plan_destroy': (None, [_P]),
+    'd4_muon_plan_workspace_bytes': (C.c_size_t, [_P]),
+    'd4_muon_plan_passes': (_I, [_P]),
+    'd4_muon_step': (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_F), _P, C.c_size_t, _D, _D, _D, _I, _I, _F, _F, _F, _F, _P, _F, _P]),
+    'd4_newton_schulz': (_I, [_P, C.POINTER(_P), C.POINTER(_P), _P, C.c_size_t, _I, _F, _F, _F, _F, _P]),
+    'd4_multi_table_bytes': (C.c_size_t, [_I, C.POINTER(_L)]),
+    'd4_sumsq_multi': (_I, [_I, C.POINTER(_L), C.POINTER(_P), _P, C.c_size_t, _I, _P, _P]),
+    'd4_adam_atan2_multi': (_I, [_I, C.POINTER(_L), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, C.c_size_t, _I, _I,
+                                 _D, _D, _D, _D, _D, _D, _P, _F, _P]),
 }
 
 _lib = None

@@ -26,7 +26,7 @@ from torch import nn
 
 from dreamer4_amd import _lib
 from dreamer4_amd.checkpoint import SaveLoad
-from dreamer4_amd.world_model import MLP_RECIPES, _linear_b, _linear_w, _register, mlp_param_specs, mlp_widths
+from dreamer4_amd.world_model import MLP_RECIPES, _linear_b, _linear_w, _register, mlp_param_specs, mlp_widths, transformer_muon_parameters
 
 TokenizerLosses = namedtuple('TokenizerLosses', ('recon', 'flow_recon', 'lpips', 'time_decorr', 'space_decorr', 'latent_ortho', 'latent_ar', 'latent_ar_sigreg',
                                                  'latent_consistency', 'latent_sigreg', 'h_net', 'byol'))       # dreamer4.py:118
@@ -175,6 +175,10 @@ class VideoTokenizer(SaveLoad, nn.Module):
         # state_dict stays the parameter set the inference paths load; load_state_dict still takes the key from a reference checkpoint
         if self.use_loss_normalization:
             _register(self, _NORMALIZER_KEY, torch.ones(1), buffer=True, persistent=False)
+
+    def muon_parameters(self):
+        """dreamer4.py:4096-4105: the encoder transformer's and the decoder transformer's Muon parameters (no separate flow decoder in the subset)."""
+        return [*transformer_muon_parameters(self.encoder_transformer), *transformer_muon_parameters(self.decoder.transformer)]
 
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         if _NORMALIZER_KEY in state_dict:

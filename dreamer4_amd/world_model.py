@@ -43,6 +43,21 @@ def _register(root: nn.Module, key: str, tensor: torch.Tensor, buffer=False, per
         m.register_parameter(parts[-1], nn.Parameter(tensor))
 
 
+def transformer_muon_parameters(trunk: nn.Module):
+    """AxialSpaceTimeTransformer.muon_parameters (dreamer4.py:2918-2925) on the mirrored module tree: for every Attention under `trunk` (a node
+    that holds to_v and to_out: the layers' own, attn_pools.*.fn.attn, final_attn_pool.fn.attn, final_special_cross_attn.fn) to_v.weight and
+    to_out.weight (dreamer4.py:1960-1966; queries and keys stay with Adam), for every FeedForward (proj_in and proj_out; final_special_ff.fn
+    included) both projection weights (dreamer4.py:2099-2103)."""
+    out = []
+    for m in trunk.modules():
+        kids = m._modules
+        if 'to_v' in kids and 'to_out' in kids:
+            out += [kids['to_v'].weight, kids['to_out'].weight]
+        if 'proj_in' in kids and 'proj_out' in kids:
+            out += [kids['proj_in'].weight, kids['proj_out'].weight]
+    return out
+
+
 def _linear_w(out_f, in_f):
     w = torch.empty(out_f, in_f)
     nn.init.kaiming_uniform_(w, a=math.sqrt(5))
@@ -543,6 +558,11 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
     def value_head_parameters(self):
         """dreamer4.py:5357-5363"""
         return list(self.value_head.parameters())
+
+    def muon_parameters(self):
+        """dreamer4.py:5335-5341: the transformer's Muon parameters (the latent pools outside it are not the transformer's); the supported subset
+        has no separate actor / critic transformer."""
+        return transformer_muon_parameters(self.transformer)
 
     # ------------------------------------------------------------------------------ engine plumbing
     def _stream(self):

@@ -901,6 +901,47 @@ int d4_recon_loss_fwd_bwd(const float* recon_rows, const float* video, const flo
 int d4_pack_tokens_bf16(int which, float* tokens, uint16_t* tokens_b, float* compact, uint16_t* compact_b, const float* pos, const float* img, const float* lat,
                         int frames, int P, int n_lat, int n_total, int D, void* stream);
 
+/* ---- MuonAdamAtan2 (csrc/muon.hip) ------------------------------------------------------------------------------------
+ * A plan describes a group of 2-D fp32 matrices (rows[i] x cols[i], contiguous) and owns the device tables of its launches: per pass one
+ * table of prepare / finish workgroups and two tile tables (matrix, tile row, tile col) of the grouped products.  Matrices are taken in
+ * order into passes whose work buffers (X, X', A, B per matrix, every dimension padded to 128) fit `workspace_bytes`; one matrix that
+ * does not fit alone is refused by name.  The caller provides the workspace (256-byte aligned, at least workspace_bytes(plan): the work
+ * buffers of the largest pass plus the strip partials of the Frobenius norms).
+ *   d4_muon_step        per matrix W with gradient g and momentum m (g read as g * min(1, max_grad_norm / (sqrt(*grad_norm_sq) + 1e-6))
+ *                       when grad_norm_sq is given and max_grad_norm > 0):
+ *                         m <- lerp(m, g, 1 - beta);  u = nesterov ? lerp(g, m, beta) : m;  X = NS(u);
+ *                         W <- W (1 - lr weight_decay) - lr update_scale[i] X
+ *                       params / grads / exp_avg / update_scale: HOST arrays of the plan's length (device pointers; host floats).
+ *                       The device pointer table is uploaded only when a pointer or a scale changed since the last call.
+ *   d4_newton_schulz    out[i] = NS(in[i]) alone, through the same launchers (in / out: host arrays of device pointers):
+ *                         X = u / max(|u|_F, eps), oriented rows <= cols;  `steps` times  A = X X^T, B = b A + c A A, X <- a X + B X.
+ * Launches per call: passes * (2 + 3 * steps).  Fixed-order reductions, no float atomics: equal inputs and state give equal bits, and the
+ * pass partition does not change them.  Learning rates, betas and weight decay are doubles: the lerp weights 1 - beta, the decay factor
+ * 1 - lr wd and the bias corrections are formed in double and rounded once (1 - 0.99f is 1e-6 off 0.01).
+ *   d4_multi_table_bytes / d4_sumsq_multi / d4_adam_atan2_multi   multi-tensor kernels over a device table of n tensors (numel[i] >= 1
+ *                       elements each; host arrays).  `table`: caller-owned device memory of d4_multi_table_bytes(n, numel) bytes, 16-byte
+ *                       aligned; upload != 0 (re)writes it from the host pointer arrays (needed at first use and whenever a pointer
+ *                       changed), upload == 0 reuses it and ignores the pointer arrays.
+ *                         d4_sumsq_multi       out[0] = sum over all tensors of x^2 (per-4096-element partials, then one block).
+ *                         d4_adam_atan2_multi  m <- lerp(m, g, 1 - beta1); v <- lerp(v, g^2, 1 - beta2);
+ *                                              W <- W (1 - lr wd) - lr a atan2(m / (1 - beta1^step), b sqrt(v / (1 - beta2^step)))
+ *                                              with g clipped as in d4_muon_step.  One launch. */
+typedef struct d4_muon_plan d4_muon_plan;
+int d4_muon_plan_create(int n, const int32_t* rows, const int32_t* cols, size_t workspace_bytes, d4_muon_plan** out);
+void d4_muon_plan_destroy(d4_muon_plan* plan);
+size_t d4_muon_plan_workspace_bytes(const d4_muon_plan* plan);
+int d4_muon_plan_passes(const d4_muon_plan* plan);
+int d4_muon_step(d4_muon_plan* plan, void* const* params, const void* const* grads, void* const* exp_avg, const float* update_scale, void* workspace,
+                 size_t workspace_bytes, double lr, double weight_decay, double beta, int nesterov, int steps, float a, float b, float c, float eps,
+                 const float* grad_norm_sq, float max_grad_norm, void* stream);
+int d4_newton_schulz(d4_muon_plan* plan, const void* const* in, void* const* out, void* workspace, size_t workspace_bytes, int steps, float a, float b,
+                     float c, float eps, void* stream);
+size_t d4_multi_table_bytes(int n, const int64_t* numel);
+int d4_sumsq_multi(int n, const int64_t* numel, const void* const* x, void* table, size_t table_bytes, int upload, float* out, void* stream);
+int d4_adam_atan2_multi(int n, const int64_t* numel, void* const* params, const void* const* grads, void* const* exp_avg, void* const* exp_avg_sq, void* table,
+                        size_t table_bytes, int upload, int step, double lr, double beta1, double beta2, double weight_decay, double a, double b,
+                        const float* grad_norm_sq, float max_grad_norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
