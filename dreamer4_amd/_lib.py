@@ -214,6 +214,7 @@ SYMBOLS = {
     'd4_pool_mix_deep': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'd4_time_attn_decode': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P] + [_I] * 8 + [_P, _F, _I, _I, _P]),
     'd4_gemm_family_configs': (_I, [_I]),
+    'd4_gemm_route': (_I, [C.POINTER(GemmDesc), _I]),
     'd4_gemm_run': (_I, [C.POINTER(GemmDesc), _I, _I, _P]),
     'd4_gemm_run_rowmap': (_I, [C.POINTER(GemmDesc), _I, _I, _I, _I, _I, _I, _P]),
     'd4_gemm_run_pair': (_I, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _I, _I, _P]),

@@ -354,6 +354,13 @@ int d4_gemm_family_configs(int family) {
     }
     return -1;
 }
+int d4_gemm_route(const d4_gemm_desc* d, int rule_M) {
+    if (gemm_desc_check("d4_gemm_route", d)) return -1;
+    d4::GemmArgs g = gemm_args_of(*d);
+    g.rule_M = rule_M;
+    int family = -1;
+    return d4::gemm_route_checked(g, &family) ? -1 : family;
+}
 static int gemm_run_args(const d4::GemmArgs& g, int family, int config, void* stream);
 int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream) {
     if (int rc = gemm_desc_check("d4_gemm_run", d)) return rc;

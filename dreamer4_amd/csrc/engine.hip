@@ -1917,20 +1917,7 @@ int d4_debug_switch(const char* name, int value) {
     *sw = value;
     return old;
 }
-int d4_gemm_force_config(int id) {
-    // one family is forced at a time; every call first clears the hooks of the other families, and returns the number of configurations of the family
-    // it addressed (id < 0: everything back to the rules / the tuner, returns the first family's count)
-    d4::gemm_bf16a_force_config(-1);
-    d4::gemm_bf16_force_config(-1);
-    const int n_main = d4::gemm_force_config(-1);
-    if (id < 0) return n_main;
-    if (id >= 500) { d4::gemm_bf16a_force_config(id - 500); return d4::gemm_bf16a_configs(); }     // tile c of the bf16-activation kernel (gemm_bf16a.hip)
-    if (id >= 400) { d4::gemm_force_config(id); return d4::gemm_h2_configs(); }                     // tile c of the fp16x2 family (gemm_h2.hip)
-    if (id >= 300) { d4::gemm_force_config(id); return d4::gemm_x3_configs(); }                     // tile c of the split-operand fp32 family (gemm_x3.hip)
-    if (id >= 200) return d4::gemm_bf16_force_config(id - 200);                                     // configuration c of the fp32-activation bf16 kernel
-    d4::gemm_force_config(id);                                                                      // < 100 first fp32 family, 100 + c second (gemm2.hip)
-    return id >= 100 ? d4::gemm2_configs() : n_main;
-}
+int d4_gemm_force_config(int id) { return d4::gemm_force_config(id); }      // gemm.hip decodes the code
 
 int d4_debug_buffer(d4_engine* e, const char* name, float** ptr) {
     D4_REQUIRE(e && name && ptr, "null argument");

@@ -20,10 +20,14 @@
 // The MFMA consumes k in the order lanes<32: {8q+e}, lanes>=32: {8q+4+e} so that each lane's
 // operand for four consecutive k-steps is one ds_read_b128 (summation order inside a k-tile is a
 // fixed permutation; results are deterministic).
+//
+// Below the kernel sits the dispatcher every dense product passes through: ONE route function (which family runs a call: route), ONE table of the
+// families that are tuned (kFamilies) with ONE tuner and ONE tuned launch over it, and ONE timed launch for the profile classes (timed_launch).
 #include "common.h"
 #include <string.h>
 #include <hip/hip_ext.h>
 #include "kernels.h"
+#include "../../include/d4hip.h"     // the D4_GEMM_* family codes
 #include <mutex>
 #include <math.h>
 #include <stdio.h>
@@ -335,7 +339,7 @@ __global__ __launch_bounds__(WGM * WGN * 64 * KS) void gemm_kernel(GemmArgs p) {
 
 // ---- optional per-launch timing (bench.py roofline leg): HIP events on the launch stream --------------------
 struct ProfRec { hipEvent_t a, b; int cls; double flops; int M, N, K, flags, batch, bm, bn; };
-static int g_prof_mask = 0;            // bit c set: time launches of tile configuration c
+static int g_prof_mask = 0;            // bit c set: time launches of profile class c
 static int g_prof_stride = 1;          // ... every g_prof_stride-th of them
 static int g_prof_tick = 0;
 static std::vector<ProfRec> g_prof;
@@ -352,19 +356,24 @@ bool gemm_bf16_profile_active();
 bool glue_profile_active();            // prof.cpp: event-timed launches cannot be captured into a graph either
 bool gemm_profile_active() { return g_prof_mask != 0 || gemm_bf16_profile_active() || glue_profile_active(); }
 
-static std::recursive_mutex& gemm_mutex();
+// The dispatcher's process-global state (tile choices per shape, the tuning-cache file, the profiling log and its event pool, the static
+// per-instantiation attribute flags) is guarded by ONE recursive mutex taken at its entries (gemm, gemm_pair, gemm_x3sk_fill): ctypes releases the
+// GIL, and two engines may be driven from two host threads (tools/two_stream_rollout.py).  Launches are asynchronous, so the lock is held for
+// microseconds except while a shape is being timed for the first time.
+static std::recursive_mutex g_gemm_mu;
+
 int gemm_profile_enable(int mask) {
-    std::lock_guard<std::recursive_mutex> lock(gemm_mutex());
-    g_prof_stride = (mask >> 27) > 0 ? (mask >> 27) : 1;          // bits 27..30: stride; bits 0..26: configurations (27 classes since round 6)
+    std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
+    g_prof_stride = (mask >> 27) > 0 ? (mask >> 27) : 1;          // bits 27..30: stride; bits 0..26: profile classes (27 of them)
     mask &= 0x7FFFFFF;
     g_prof_tick = 0;
     g_prof_mask = mask;
     return 0;
 }
 
-// Sums elapsed time / algorithmic flops / launch count per tile class (0: 128x128, 1: 64x128, 2: 64x64) and clears the log.
+// Sums elapsed time / algorithmic flops / launch count per profile class and clears the log.
 int gemm_profile_read(double* ms, double* flops, int64_t* count, int nclass) {
-    std::lock_guard<std::recursive_mutex> lock(gemm_mutex());
+    std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
     for (int i = 0; i < nclass; ++i) { ms[i] = 0; flops[i] = 0; count[i] = 0; }
     // D4_GEMM_LOG=1: also print a per-shape table (launches, total ms, TFLOP/s) to stderr
     static const bool log_shapes = getenv("D4_GEMM_LOG") != nullptr;
@@ -395,6 +404,21 @@ int gemm_profile_read(double* ms, double* flops, int64_t* count, int nclass) {
     return 0;
 }
 
+static inline double gemm_flops(const GemmArgs& p) { return p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1); }
+
+// THE timed launch: every launch of the dispatcher goes through here.  `launch(ea, eb)` enqueues the kernel; when profile class `cls` is enabled and this
+// launch is due by the stride it gets an event pair from the pool and a log record (`shape`: what the per-shape table prints; bm x bn: the tile).  The two
+// events ride on the dispatch itself (hipExtLaunchKernelGGL: its begin / end timestamps): no extra barrier packets on the stream, and the elapsed time is
+// the kernel's own duration (what rocprofv3 --kernel-trace reports).
+template <class Launch>
+static int timed_launch(int cls, const GemmArgs& shape, int bm, int bn, double flops, Launch&& launch) {
+    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
+    if (!timed) return launch(nullptr, nullptr);
+    const ProfRec rec{prof_event(), prof_event(), cls, flops, shape.M, shape.N, shape.K, shape.flags, shape.batch, bm, bn};
+    if (int rc = launch(rec.a, rec.b)) return rc;
+    g_prof.push_back(rec);
+    return 0;
+}
 
 static inline double tile_cost(const GemmArgs& p, int BM, int BN, int slots) {
     // co-resident blocks share a CU's matrix pipes: a CU's time ~ (blocks it hosts) x (tile area)
@@ -403,7 +427,7 @@ static inline double tile_cost(const GemmArgs& p, int BM, int BN, int slots) {
 }
 
 template <int BM, int BN, int WGM, int WGN, int BK, int KS, bool TA, bool TB>
-static int launch_cfg(const GemmArgs& p, hipStream_t stream, int cls) {
+static int launch_cfg(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
     constexpr int LDS_LD = BK + 4;
     const int nblk = cdiv(p.M, BM) * cdiv(p.N, BN);
     const size_t lds = (size_t)(2 * BM * LDS_LD + 2 * BN * LDS_LD + BM) * sizeof(float);
@@ -414,43 +438,23 @@ static int launch_cfg(const GemmArgs& p, hipStream_t stream, int cls) {
         D4_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set[ktail].done();
     }
-    ProfRec rec{};
-    const bool g_prof_on = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (g_prof_on) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-        rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch; rec.bm = BM; rec.bn = BN;
-        rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1);
-        // the two events ride on the dispatch itself (its begin / end timestamps): no extra barrier packets on the stream,
-        // and the elapsed time is the kernel's own duration (what rocprofv3 --kernel-trace reports)
-        hipExtLaunchKernelGGL(k, dim3(nblk, p.batch > 0 ? p.batch : 1), dim3(WGM * WGN * 64 * KS), (uint32_t)lds, stream, rec.a, rec.b, 0, p);
-        g_prof.push_back(rec);
-    } else {
-        hipLaunchKernelGGL(k, dim3(nblk, p.batch > 0 ? p.batch : 1), dim3(WGM * WGN * 64 * KS), lds, stream, p);
-    }
+    const dim3 grid(nblk, p.batch > 0 ? p.batch : 1), block(WGM * WGN * 64 * KS);
+    if (ea) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)lds, stream, ea, eb, 0, p);
+    else hipLaunchKernelGGL(k, grid, block, lds, stream, p);
     D4_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- tile configurations and their selection ---------------------------------------------------------------
+// ---- the first family's tile configurations ------------------------------------------------------------------
 // All configurations walk k in the same order with the same MFMA, so every output element is the same
 // bit pattern whichever one runs: the choice is a pure performance decision.
 enum TileCfg { T128x128_2x4 = 0, T128x128_4x2, T128x96_4x1, T64x128_2x2, T64x64_2x2, T256x128_4x4, T64x128_k16, T64x64_k16, N_TILE_CFG };
 static const char* const kTileName[N_TILE_CFG] = {"128x128/2x4", "128x128/4x2", "128x96/4x1", "64x128/2x2", "64x64/2x2", "256x128/4x4", "64x128/2x2/k16", "64x64/2x2/k16"};
-
+static const int kTileBM[N_TILE_CFG] = {128, 128, 128, 64, 64, 256, 64, 64}, kTileBN[N_TILE_CFG] = {128, 128, 96, 128, 64, 128, 128, 64};
 // rocprofv3 shows the instantiation as d4::gemm_kernel<BM, BN, WGM, WGN, BK, 1, transA, transB, ktail>
 static const char* const kTileKernel[N_TILE_CFG] = {
     "gemm_kernel<128, 128, 2, 4, 32, 1", "gemm_kernel<128, 128, 4, 2, 32, 1", "gemm_kernel<128, 96, 4, 1, 32, 1", "gemm_kernel<64, 128, 2, 2, 32, 1",
     "gemm_kernel<64, 64, 2, 2, 32, 1", "gemm_kernel<256, 128, 4, 4, 32, 1", "gemm_kernel<64, 128, 2, 2, 16, 1", "gemm_kernel<64, 64, 2, 2, 16, 1"};
-// profile classes: the N_TILE_CFG configurations of this family, then the configurations of the second family (gemm2.hip)
-int gemm_profile_classes() { return N_TILE_CFG + gemm2_configs() + gemm_x3_configs() + 3; }     // + the persistent split-operand form (gemm_x3sk.hip) + the fp16x2 family (gemm_h2.hip, one class) + the few-row k-split form (gemm2.hip)
-const char* gemm_profile_class_name(int c) {
-    if (c == N_TILE_CFG + gemm2_configs() + gemm_x3_configs() + 2) return "gemm2_ksplit_kernel";
-    if (c == N_TILE_CFG + gemm2_configs() + gemm_x3_configs() + 1) return "gemm_h2_kernel";
-    if (c == N_TILE_CFG + gemm2_configs() + gemm_x3_configs()) return gemm_x3sk_name();
-    if (c >= N_TILE_CFG + gemm2_configs()) return gemm_x3_config_name(c - N_TILE_CFG - gemm2_configs());
-    if (c >= N_TILE_CFG) return gemm2_config_name(c - N_TILE_CFG);
-    return c >= 0 ? kTileKernel[c] : "";
-}
 
 template <bool TA, bool TB>
 static bool cfg_valid(int id, const GemmArgs& p) {
@@ -469,25 +473,25 @@ static bool cfg_valid(int id, const GemmArgs& p) {
 }
 
 template <bool TA, bool TB>
-static int launch_id(int id, const GemmArgs& p, hipStream_t stream) {
+static int launch_id(int id, const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
     switch (id) {
         // 8 waves (2 x 4, wave tile 64 x 32): two co-resident blocks put 4 waves on every SIMD
-        case T128x128_2x4: return launch_cfg<128, 128, 2, 4, 32, 1, TA, TB>(p, stream, id);
+        case T128x128_2x4: return launch_cfg<128, 128, 2, 4, 32, 1, TA, TB>(p, stream, ea, eb);
         // (the SiLU-GLU epilogue pairs two N sub-tiles inside one wave -> 4 x 2 waves, wave tile 32 x 64)
-        case T128x128_4x2: return launch_cfg<128, 128, 4, 2, 32, 1, TA, TB>(p, stream, id);
+        case T128x128_4x2: return launch_cfg<128, 128, 4, 2, 32, 1, TA, TB>(p, stream, ea, eb);
         case T128x96_4x1:
-            if constexpr (!TA && !TB) return launch_cfg<128, 96, 4, 1, 32, 1, TA, TB>(p, stream, id);
+            if constexpr (!TA && !TB) return launch_cfg<128, 96, 4, 1, 32, 1, TA, TB>(p, stream, ea, eb);
             break;
-        case T64x128_2x2: return launch_cfg<64, 128, 2, 2, 32, 1, TA, TB>(p, stream, id);
-        case T64x64_2x2: return launch_cfg<64, 64, 2, 2, 32, 1, TA, TB>(p, stream, id);
+        case T64x128_2x2: return launch_cfg<64, 128, 2, 2, 32, 1, TA, TB>(p, stream, ea, eb);
+        case T64x64_2x2: return launch_cfg<64, 64, 2, 2, 32, 1, TA, TB>(p, stream, ea, eb);
         case T256x128_4x4:
-            if constexpr (!TA && !TB) return launch_cfg<256, 128, 4, 4, 32, 1, TA, TB>(p, stream, id);
+            if constexpr (!TA && !TB) return launch_cfg<256, 128, 4, 4, 32, 1, TA, TB>(p, stream, ea, eb);
             break;
         case T64x128_k16:
-            if constexpr (!TA && !TB) return launch_cfg<64, 128, 2, 2, 16, 1, TA, TB>(p, stream, id);
+            if constexpr (!TA && !TB) return launch_cfg<64, 128, 2, 2, 16, 1, TA, TB>(p, stream, ea, eb);
             break;
         case T64x64_k16:
-            if constexpr (!TA && !TB) return launch_cfg<64, 64, 2, 2, 16, 1, TA, TB>(p, stream, id);
+            if constexpr (!TA && !TB) return launch_cfg<64, 64, 2, 2, 16, 1, TA, TB>(p, stream, ea, eb);
             break;
     }
     D4_REQUIRE(false, "gemm: tile configuration %d not available for this operand layout", id);
@@ -512,22 +516,114 @@ static int heuristic_cfg(const GemmArgs& p) {
     return T64x64_2x2;
 }
 
-// Shape -> configuration, filled by timing every valid configuration the first time a shape is seen (the engine's
+// The first family as the family table sees it: plain functions that pick the (transA, transB) instantiation inside.
+#define D4_TILE_BY_LAYOUT(fn, ...)                                                          \
+    const bool ta = p.flags & GEMM_TRANS_A, tb = p.flags & GEMM_TRANS_B;                    \
+    if (!ta && !tb) return fn<false, false>(__VA_ARGS__);                                   \
+    if (!ta && tb) return fn<false, true>(__VA_ARGS__);                                     \
+    if (ta && tb) return fn<true, true>(__VA_ARGS__);                                       \
+    return fn<true, false>(__VA_ARGS__)
+static int tile_configs() { return N_TILE_CFG; }
+static bool tile_config_valid(int c, const GemmArgs& p) { D4_TILE_BY_LAYOUT(cfg_valid, c, p); }
+static int tile_launch(int c, const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) { D4_TILE_BY_LAYOUT(launch_id, c, p, stream, ea, eb); }
+static const char* tile_config_name(int c) { return kTileName[c]; }
+static void tile_config_tile(int c, int* bm, int* bn) { *bm = kTileBM[c]; *bn = kTileBN[c]; }
+static int tile_heuristic(const GemmArgs& p) { D4_TILE_BY_LAYOUT(heuristic_cfg, p); }
+// the tuner leaves the 128-row tiles out under 64 tiles of 128 x 128
+static bool tile_tune_skip(int c, const GemmArgs& p) {
+    return (c == T256x128_4x4 || c == T128x128_2x4 || c == T128x128_4x2) && (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128) * (p.batch > 0 ? p.batch : 1) < 64;
+}
+#undef D4_TILE_BY_LAYOUT
+
+int gemm_configs() { return N_TILE_CFG; }
+// would gemm() under gemm_force_config(c) run configuration c of THIS family on the call?  (The few-row kernel and the mirror-weight families come first there.)
+bool gemm_config_valid(int c, const GemmArgs& p) {
+    if (c < 0 || c >= N_TILE_CFG || p.Wb || p.M < 1 || gemm_skinny_applicable(p)) return false;
+    return tile_config_valid(c, p);
+}
+
+// ---- profile classes: the tuned families' configurations in table order, then the single-form kernels ---------------------------------------
+static const int kClsTile = 0, kClsV2 = N_TILE_CFG, kClsX3 = kClsV2 + gemm2_configs();
+static const int kClsX3SK = kClsX3 + gemm_x3_configs();       // the persistent split-operand form (gemm_x3sk.hip), plain and filled
+static const int kClsH2 = kClsX3SK + 1;                       // the fp16x2 family (gemm_h2.hip): ONE class for all its tiles
+static const int kClsKsplit = kClsX3SK + 2;                   // the few-row k-split form (gemm2.hip)
+int gemm_profile_classes() { return kClsKsplit + 1; }
+const char* gemm_profile_class_name(int c) {
+    if (c == kClsKsplit) return "gemm2_ksplit_kernel";
+    if (c == kClsH2) return "gemm_h2_kernel";
+    if (c == kClsX3SK) return gemm_x3sk_name();
+    if (c >= kClsX3) return gemm_x3_config_name(c - kClsX3);
+    if (c >= kClsV2) return gemm2_config_name(c - kClsV2);
+    return c >= 0 ? kTileKernel[c] : "";
+}
+
+// ---- the tuned families ------------------------------------------------------------------------------------------------------------------------
+// Shape -> configuration, per family, filled by timing every valid configuration the first time a shape is seen (the engine's
 // shapes are fixed by (batch, frames, config), a few dozen in all).  D4_GEMM_AUTOTUNE=0 keeps the static choice.
 struct TuneKey {
     int M, N, K, flags, batch;
     bool operator<(const TuneKey& o) const { return std::tie(M, N, K, flags, batch) < std::tie(o.M, o.N, o.K, o.flags, o.batch); }
 };
-static std::map<TuneKey, int> g_tuned, g_tuned2, g_tuned3, g_tuned4;
-static int g_forced_cfg = -1;          // test hook (d4_gemm_force_config): run this configuration wherever it is valid;
-                                       // 100 + c: configuration c of the second family (gemm2.hip)
-int gemm_force_config(int id) { g_forced_cfg = id; return N_TILE_CFG; }
-int gemm_configs() { return N_TILE_CFG; }
-// would gemm() under gemm_force_config(c) run configuration c of THIS family on the call?  (The few-row kernel and the mirror-weight families come first there.)
-bool gemm_config_valid(int c, const GemmArgs& p) {
-    if (c < 0 || c >= N_TILE_CFG || p.Wb || p.M < 1 || gemm_skinny_applicable(p)) return false;
-    const bool ta = p.flags & GEMM_TRANS_A, tb = p.flags & GEMM_TRANS_B;
-    return ta ? (tb ? cfg_valid<true, true>(c, p) : cfg_valid<true, false>(c, p)) : (tb ? cfg_valid<false, true>(c, p) : cfg_valid<false, false>(c, p));
+static std::map<TuneKey, int> g_tuned[4];
+
+// One row per family whose configurations all give the same bits, so that the choice among them is free: what the tuner, the tuning-cache file, the
+// force hook and the timed launch need to know about it.
+struct Family {
+    int code;                                  // D4_GEMM_*
+    const char* tag;                           // D4_GEMM_LOG: "[d4 <tag>] tuned ..."
+    int (*configs)();
+    bool (*config_valid)(int, const GemmArgs&);
+    int (*launch)(int, const GemmArgs&, hipStream_t, hipEvent_t, hipEvent_t);
+    const char* (*config_name)(int);
+    void (*config_tile)(int, int*, int*);
+    int (*heuristic)(const GemmArgs&);         // the static choice, for a shape that cannot be timed
+    bool (*tune_skip)(int, const GemmArgs&);   // configurations the tuner leaves out (null: none)
+    int id_base;                               // configuration c is id_base + c in the tuning-cache files
+    int first_class;                           // profile class of configuration 0 ...
+    bool class_per_config;                     // ... one class per configuration, or that one for the family
+    bool strict_few_rows;                      // D4_GEMM_AUTOTUNE=strict: a product of <= 512 rows missing from the table takes the static choice
+    std::map<TuneKey, int>* tuned;
+};
+enum { FAM_TILE = 0, FAM_V2, FAM_X3, FAM_H2, N_FAMILIES };
+static const Family kFamilies[N_FAMILIES] = {
+    {D4_GEMM_TILE, "gemm", tile_configs, tile_config_valid, tile_launch, tile_config_name, tile_config_tile, tile_heuristic, tile_tune_skip, 0, kClsTile, true, true, &g_tuned[FAM_TILE]},
+    {D4_GEMM_V2, "gemm2", gemm2_configs, gemm2_config_valid, gemm2_launch, gemm2_config_name, gemm2_config_tile, gemm2_heuristic, nullptr, 100, kClsV2, true, true, &g_tuned[FAM_V2]},
+    {D4_GEMM_X3, "gemm_x3", gemm_x3_configs, gemm_x3_config_valid, gemm_x3_launch, gemm_x3_config_name, gemm_x3_config_tile, gemm_x3_heuristic, nullptr, 300, kClsX3, true, false, &g_tuned[FAM_X3]},
+    {D4_GEMM_H2, "gemm_h2", gemm_h2_configs, gemm_h2_config_valid, gemm_h2_launch, gemm_h2_config_name, gemm_h2_config_tile, gemm_h2_heuristic, nullptr, 400, kClsH2, false, false, &g_tuned[FAM_H2]},
+};
+
+// ---- the test hook (d4_gemm_force_config): THE decoding of its codes --------------------------------------------------------------------------
+//   < 0 nothing forced | c < 100 configuration c of the first family | 100 + c of gemm2.hip | 199 the few-row k-split form on any shape it can run |
+//   200 + c of gemm_bf16.hip | 300 + c of gemm_x3.hip | 400 + c of gemm_h2.hip | 500 + c of gemm_bf16a.hip
+struct Forced { int family = -1, config = -1; };       // family: a D4_GEMM_* code; -1: the rules and the tuner decide
+static Forced forced_decode(int code) {
+    if (code < 0) return {};
+    if (code < 100) return {D4_GEMM_TILE, code};
+    if (code == 199) return {D4_GEMM_V2_KSPLIT, 0};
+    if (code < 200) return {D4_GEMM_V2, code - 100};
+    if (code < 300) return {D4_GEMM_BF16, code - 200};
+    if (code < 400) return {D4_GEMM_X3, code - 300};
+    if (code < 500) return {D4_GEMM_H2, code - 400};
+    return {D4_GEMM_BF16A, code - 500};
+}
+// the two bf16 kernels keep their hooks in gemm_bf16.hip (they have one form per call, chosen there); to the fp32 families such a code forces nothing
+static Forced forced_fp32(const Forced& f) { return f.family == D4_GEMM_BF16 || f.family == D4_GEMM_BF16A ? Forced{} : f; }
+static Forced g_forced;
+// One family is forced at a time: every call first clears the hooks of the other families.  Returns the number of configurations of the family addressed
+// (nothing forced: the first family's).
+int gemm_force_config(int code) {
+    const Forced f = forced_decode(code);
+    gemm_bf16a_force_config(f.family == D4_GEMM_BF16A ? f.config : -1);
+    const int n_bf16 = gemm_bf16_force_config(f.family == D4_GEMM_BF16 ? f.config : -1);
+    g_forced = forced_fp32(f);
+    switch (f.family) {
+        case D4_GEMM_V2: case D4_GEMM_V2_KSPLIT: return gemm2_configs();
+        case D4_GEMM_BF16: return n_bf16;
+        case D4_GEMM_X3: return gemm_x3_configs();
+        case D4_GEMM_H2: return gemm_h2_configs();
+        case D4_GEMM_BF16A: return gemm_bf16a_configs();
+    }
+    return N_TILE_CFG;
 }
 
 // D4_GEMM_TUNE_CACHE=<file>: the shape -> configuration table is read at first use and every new entry is appended, so a
@@ -543,10 +639,8 @@ static void tune_cache_read(const char* path) {
         while (fgets(line, sizeof(line), f)) {
             TuneKey k; int id;
             if (line[0] == '#' || sscanf(line, "%d %d %d %d %d %d", &k.M, &k.N, &k.K, &k.flags, &k.batch, &id) != 6) continue;
-            if (id >= 0 && id < N_TILE_CFG) g_tuned[k] = id;
-            else if (id >= 100 && id < 100 + gemm2_configs()) g_tuned2[k] = id - 100;      // second family (gemm2.hip)
-            else if (id >= 300 && id < 300 + gemm_x3_configs()) g_tuned3[k] = id - 300;    // split-operand family (gemm_x3.hip)
-            else if (id >= 400 && id < 400 + gemm_h2_configs()) g_tuned4[k] = id - 400;    // fp16x2 split-operand family (gemm_h2.hip)
+            for (const Family& F : kFamilies)
+                if (id >= F.id_base && id < F.id_base + F.configs()) (*F.tuned)[k] = id - F.id_base;
         }
         fclose(f);
     }
@@ -581,389 +675,96 @@ static int tune_mode() {
     }();
     return mode;
 }
-#define D4_TUNE_STRICT_CHECK(p, nb)                                                                                                            \
-    D4_REQUIRE(tune_mode() != 2, "gemm: shape M=%d N=%d K=%d flags=%d batch=%d is not in the shipped tile table (dreamer4_amd/gemm_tune_default.txt) and " \
-               "D4_GEMM_AUTOTUNE=strict forbids timing it here: run the workload once on one GPU with D4_GEMM_TUNE_CACHE=<file> and merge the new lines",  \
-               (p).M, (p).N, (p).K, (p).flags, (nb))
+static int tune_strict_check(const GemmArgs& p) {
+    D4_REQUIRE(tune_mode() != 2, "gemm: shape M=%d N=%d K=%d flags=%d batch=%d is not in the shipped tile table (dreamer4_amd/gemm_tune_default.txt) and "
+               "D4_GEMM_AUTOTUNE=strict forbids timing it here: run the workload once on one GPU with D4_GEMM_TUNE_CACHE=<file> and merge the new lines",
+               p.M, p.N, p.K, p.flags, p.batch > 0 ? p.batch : 1);
+    return 0;
+}
 
-template <bool TA, bool TB>
-static int autotune(const GemmArgs& p, hipStream_t stream, int* best_out) {
+// One launch of configuration c of a family, under its profile class.
+static int family_launch(const Family& F, int c, const GemmArgs& p, hipStream_t stream) {
+    int bm, bn;
+    F.config_tile(c, &bm, &bn);
+    return timed_launch(F.first_class + (F.class_per_config ? c : 0), p, bm, bn, gemm_flops(p), [&](hipEvent_t ea, hipEvent_t eb) { return F.launch(c, p, stream, ea, eb); });
+}
+
+// THE tuner: one warm launch, then the best of two timed pairs, for every valid configuration.
+static int autotune(const Family& F, const GemmArgs& p, hipStream_t stream, int* best_out) {
     hipEvent_t e0 = prof_event(), e1 = prof_event();
-    const int saved_mask = g_prof_mask;
-    g_prof_mask = 0;
     int best = -1, rc = 0;
     float best_ms = 0.f;
-    for (int id = 0; id < N_TILE_CFG && !rc; ++id) {
-        if (!cfg_valid<TA, TB>(id, p)) continue;
-        if ((id == T256x128_4x4 || id == T128x128_2x4 || id == T128x128_4x2) && (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128) * (p.batch > 0 ? p.batch : 1) < 64) continue;
-        if ((rc = launch_id<TA, TB>(id, p, stream))) break;              // warm (attribute set, code resident)
+    for (int c = 0; c < F.configs() && !rc; ++c) {
+        if (!F.config_valid(c, p) || (F.tune_skip && F.tune_skip(c, p))) continue;
+        if ((rc = F.launch(c, p, stream, nullptr, nullptr))) break;              // warm (attribute set, code resident)
         float ms = 1e30f;
-        for (int rep = 0; rep < 2 && !rc; ++rep) {                       // best of two timed pairs
+        for (int rep = 0; rep < 2 && !rc; ++rep) {
             (void)hipEventRecord(e0, stream);
-            if ((rc = launch_id<TA, TB>(id, p, stream))) break;
-            if ((rc = launch_id<TA, TB>(id, p, stream))) break;
+            if ((rc = F.launch(c, p, stream, nullptr, nullptr))) break;
+            if ((rc = F.launch(c, p, stream, nullptr, nullptr))) break;
             (void)hipEventRecord(e1, stream);
             if (hipEventSynchronize(e1) != hipSuccess) { rc = 1; break; }
             float t = 0.f;
             (void)hipEventElapsedTime(&t, e0, e1);
             ms = t < ms ? t : ms;
         }
-        if (!rc && (best < 0 || ms < best_ms)) { best = id; best_ms = ms; }
+        if (!rc && (best < 0 || ms < best_ms)) { best = c; best_ms = ms; }
     }
-    g_prof_mask = saved_mask;
     g_event_pool.push_back(e0);
     g_event_pool.push_back(e1);
     if (rc) return rc;
-    D4_REQUIRE(best >= 0, "gemm: no tile configuration for M=%d N=%d K=%d flags=%d", p.M, p.N, p.K, p.flags);
+    D4_REQUIRE(best >= 0, "%s: no configuration for M=%d N=%d K=%d flags=%d", F.tag, p.M, p.N, p.K, p.flags);
     if (getenv("D4_GEMM_LOG"))
-        fprintf(stderr, "[d4 gemm] tuned M %6d N %5d K %5d batch %2d flags %3d -> %s (%.1f us)\n", p.M, p.N, p.K, p.batch, p.flags, kTileName[best], 500.f * best_ms);
+        fprintf(stderr, "[d4 %s] tuned M %6d N %5d K %5d batch %2d flags %3d -> %s (%.1f us)\n", F.tag, p.M, p.N, p.K, p.batch, p.flags, F.config_name(best), 500.f * best_ms);
     *best_out = best;
     return 0;
 }
 
-template <bool TA, bool TB>
-static int launch_t(const GemmArgs& p, hipStream_t stream) {
-    const bool tune_on = tune_mode() != 0;
-    const int nb = p.batch > 0 ? p.batch : 1;
+// THE tuned launch of a family: the forced configuration where it is valid, else the table's, else — for a call that can be timed — the tuner's, which is
+// remembered and appended to the cache file; every other call takes the static choice.
+static int tuned_launch(const Family& F, const GemmArgs& p, hipStream_t stream) {
+    if (g_forced.family == F.code && F.config_valid(g_forced.config, p)) return family_launch(F, g_forced.config, p, stream);
     const TuneKey key{p.M, p.N, p.K, p.flags, p.batch};
-    if (g_forced_cfg >= 0 && g_forced_cfg < N_TILE_CFG && cfg_valid<TA, TB>(g_forced_cfg, p)) return launch_id<TA, TB>(g_forced_cfg, p, stream);
     tune_cache_load();
-    auto it = g_tuned.find(key);
-    if (it != g_tuned.end() && cfg_valid<TA, TB>(it->second, p)) return launch_id<TA, TB>(it->second, p, stream);
+    auto it = F.tuned->find(key);
+    if (it != F.tuned->end() && F.config_valid(it->second, p)) return family_launch(F, it->second, p, stream);
     // timing repeats the launch, so the call must be idempotent (no accumulate, no in-place residual), worth it
     // (>= 0.1 GFLOP), and the stream must not be capturing
     const bool idempotent = !(p.flags & GEMM_ACCUMULATE) && p.R != p.C && p.A != p.C;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &cap);
-    if (!tune_on || !idempotent || cap != hipStreamCaptureStatusNone || 2.0 * p.M * p.N * p.K * nb < 1e8)
-        return launch_id<TA, TB>(heuristic_cfg<TA, TB>(p), p, stream);
+    if (tune_mode() == 0 || !idempotent || cap != hipStreamCaptureStatusNone || 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1) < 1e8)
+        return family_launch(F, F.heuristic(p), p, stream);
     // strict mode: a FEW-ROW product missing from the table (the heads' MLPs at a per-rank batch other than the shipped 256: M = the batch) takes the static
     // choice — a rule on the shape, so every rank still makes the same one without a clock; anything larger must be in the table
-    if (tune_mode() == 2 && p.M <= 512) return launch_id<TA, TB>(heuristic_cfg<TA, TB>(p), p, stream);
-    D4_TUNE_STRICT_CHECK(p, nb);
+    if (tune_mode() == 2 && F.strict_few_rows && p.M <= 512) return family_launch(F, F.heuristic(p), p, stream);
+    if (int rc = tune_strict_check(p)) return rc;
     int best = 0;
-    if (int rc = autotune<TA, TB>(p, stream, &best)) return rc;
-    g_tuned[key] = best;
-    tune_cache_append(key, best);
-    return launch_id<TA, TB>(best, p, stream);
+    if (int rc = autotune(F, p, stream, &best)) return rc;
+    (*F.tuned)[key] = best;
+    tune_cache_append(key, F.id_base + best);
+    return family_launch(F, best, p, stream);
 }
 
-// ---- second family: launch (with the optional event pair), per-shape choice among its configurations by timing ----
-static int launch_v2(int c, const GemmArgs& p, hipStream_t stream) {
-    const int cls = N_TILE_CFG + c;
-    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (!timed) return gemm2_launch(c, p, stream);
-    ProfRec rec{};
-    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
-    gemm2_config_tile(c, &rec.bm, &rec.bn);
-    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1);
-    if (int rc = gemm2_launch(c, p, stream, rec.a, rec.b)) return rc;
-    g_prof.push_back(rec);
-    return 0;
+// ---- the single-form kernels under their profile classes ----------------------------------------------------------------------------------------
+static int launch_ksplit(const GemmArgs& p, hipStream_t stream) {
+    return timed_launch(kClsKsplit, p, 32, 64, gemm_flops(p), [&](hipEvent_t ea, hipEvent_t eb) { return gemm2_ksplit_launch(p, stream, ea, eb); });
 }
-
-static int launch_v2ks(const GemmArgs& p, hipStream_t stream) {
-    const int cls = N_TILE_CFG + gemm2_configs() + gemm_x3_configs() + 2;
-    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (!timed) return gemm2_ksplit_launch(p, stream);
-    ProfRec rec{};
-    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
-    rec.bm = 32; rec.bn = 64;
-    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K;
-    if (int rc = gemm2_ksplit_launch(p, stream, rec.a, rec.b)) return rc;
-    g_prof.push_back(rec);
-    return 0;
+static int launch_x3sk(const GemmArgs& p, hipStream_t stream) {
+    return timed_launch(kClsX3SK, p, 128, 128, gemm_flops(p), [&](hipEvent_t ea, hipEvent_t eb) { return gemm_x3sk_launch(p, stream, ea, eb); });
 }
-
-static int heuristic_v2(const GemmArgs& p) {
-    // (gemm2.hip's enum) 0 = 64x64 with three blocks per CU, 1 = its SiLU-GLU capable form: the best or within a few per cent
-    // of it on every shape measured; the timed choice refines this where a call can be repeated
-    return (p.flags & GEMM_SWIGLU) ? 1 : 0;
-}
-
-static int autotune_v2(const GemmArgs& p, hipStream_t stream, int* best_out) {
-    hipEvent_t e0 = prof_event(), e1 = prof_event();
-    const int saved_mask = g_prof_mask;
-    g_prof_mask = 0;
-    int best = -1, rc = 0;
-    float best_ms = 0.f;
-    for (int c = 0; c < gemm2_configs() && !rc; ++c) {
-        if (!gemm2_config_valid(c, p)) continue;
-        if ((rc = gemm2_launch(c, p, stream))) break;
-        float ms = 1e30f;
-        for (int rep = 0; rep < 2 && !rc; ++rep) {
-            (void)hipEventRecord(e0, stream);
-            if ((rc = gemm2_launch(c, p, stream))) break;
-            if ((rc = gemm2_launch(c, p, stream))) break;
-            (void)hipEventRecord(e1, stream);
-            if (hipEventSynchronize(e1) != hipSuccess) { rc = 1; break; }
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, e0, e1);
-            ms = t < ms ? t : ms;
-        }
-        if (!rc && (best < 0 || ms < best_ms)) { best = c; best_ms = ms; }
-    }
-    g_prof_mask = saved_mask;
-    g_event_pool.push_back(e0);
-    g_event_pool.push_back(e1);
-    if (rc) return rc;
-    D4_REQUIRE(best >= 0, "gemm2: no configuration for M=%d N=%d K=%d flags=%d", p.M, p.N, p.K, p.flags);
-    if (getenv("D4_GEMM_LOG"))
-        fprintf(stderr, "[d4 gemm2] tuned M %6d N %5d K %5d batch %2d flags %3d -> %s (%.1f us)\n", p.M, p.N, p.K, p.batch, p.flags, gemm2_config_name(best), 500.f * best_ms);
-    *best_out = best;
-    return 0;
-}
-
-// Which family runs a call is a RULE on the call's shape / layout (never a timing): the two families sum k in different orders,
-// so a timing-dependent choice between them would make results depend on the tuner.
-static bool use_v2(const GemmArgs& p) { return gemm2_applicable(p); }
-
-static int gemm_v2(const GemmArgs& p, hipStream_t stream) {
-    const bool tune_on = tune_mode() != 0;
-    const int nb = p.batch > 0 ? p.batch : 1;
-    const TuneKey key{p.M, p.N, p.K, p.flags, p.batch};
-    tune_cache_load();
-    auto it = g_tuned2.find(key);
-    if (it != g_tuned2.end() && gemm2_config_valid(it->second, p)) return launch_v2(it->second, p, stream);
-    const bool idempotent = !(p.flags & GEMM_ACCUMULATE) && p.R != p.C && p.A != p.C;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    if (!tune_on || !idempotent || cap != hipStreamCaptureStatusNone || 2.0 * p.M * p.N * p.K * nb < 1e8)
-        return launch_v2(heuristic_v2(p), p, stream);
-    if (tune_mode() == 2 && p.M <= 512) return launch_v2(heuristic_v2(p), p, stream);      // strict mode, few-row product missing from the table: the static rule (see launch_t)
-    D4_TUNE_STRICT_CHECK(p, nb);
-    int best = 0;
-    if (int rc = autotune_v2(p, stream, &best)) return rc;
-    g_tuned2[key] = best;
-    tune_cache_append(key, 100 + best);
-    return launch_v2(best, p, stream);
-}
-
-// ---- third family (split operands on the bf16 matrix cores): launch with the optional event pair, timed choice among its tiles ----
-static int launch_v3(int c, const GemmArgs& p, hipStream_t stream) {
-    const int cls = N_TILE_CFG + gemm2_configs() + c;
-    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (!timed) return gemm_x3_launch(c, p, stream);
-    ProfRec rec{};
-    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
-    gemm_x3_config_tile(c, &rec.bm, &rec.bn);
-    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1);
-    if (int rc = gemm_x3_launch(c, p, stream, rec.a, rec.b)) return rc;
-    g_prof.push_back(rec);
-    return 0;
-}
-
-static int launch_v3sk(const GemmArgs& p, hipStream_t stream) {
-    const int cls = N_TILE_CFG + gemm2_configs() + gemm_x3_configs();
-    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (!timed) return gemm_x3sk_launch(p, stream);
-    ProfRec rec{};
-    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
-    rec.bm = 128; rec.bn = 128;
-    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K;
-    if (int rc = gemm_x3sk_launch(p, stream, rec.a, rec.b)) return rc;
-    g_prof.push_back(rec);
-    return 0;
-}
-
 // The filled form of the persistent kernel (gemm_x3sk.hip): accounted under the SAME profile class as the plain form, with the flops of both problems —
 // the class list does not grow (gemm_profile_enable keeps its stride field at bit 27).
 int gemm_x3sk_fill(const GemmArgs& p, const GemmArgs& fill, int fill_tiles, hipStream_t stream) {
-    std::lock_guard<std::recursive_mutex> lock(gemm_mutex());
-    const int cls = N_TILE_CFG + gemm2_configs() + gemm_x3_configs();
-    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (!timed) return gemm_x3sk_fill_launch(p, fill, fill_tiles, stream);
-    ProfRec rec{};
-    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
-    rec.bm = 128; rec.bn = 128;
-    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K;
-    if (fill_tiles > 0) rec.flops += 2.0 * fill.M * fill.N * fill.K * fill_tiles / (double)gemm_x3sk_fill_tiles(fill);
-    if (int rc = gemm_x3sk_fill_launch(p, fill, fill_tiles, stream, rec.a, rec.b)) return rc;
-    g_prof.push_back(rec);
-    return 0;
+    std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
+    const double fill_flops = fill_tiles > 0 ? 2.0 * fill.M * fill.N * fill.K * fill_tiles / (double)gemm_x3sk_fill_tiles(fill) : 0.0;
+    return timed_launch(kClsX3SK, p, 128, 128, gemm_flops(p) + fill_flops,
+                        [&](hipEvent_t ea, hipEvent_t eb) { return gemm_x3sk_fill_launch(p, fill, fill_tiles, stream, ea, eb); });
 }
 
-static int autotune_v3(const GemmArgs& p, hipStream_t stream, int* best_out) {
-    hipEvent_t e0 = prof_event(), e1 = prof_event();
-    const int saved_mask = g_prof_mask;
-    g_prof_mask = 0;
-    int best = -1, rc = 0;
-    float best_ms = 0.f;
-    for (int c = 0; c < gemm_x3_configs() && !rc; ++c) {
-        if (!gemm_x3_config_valid(c, p)) continue;
-        if ((rc = gemm_x3_launch(c, p, stream))) break;
-        float ms = 1e30f;
-        for (int rep = 0; rep < 2 && !rc; ++rep) {
-            (void)hipEventRecord(e0, stream);
-            if ((rc = gemm_x3_launch(c, p, stream))) break;
-            if ((rc = gemm_x3_launch(c, p, stream))) break;
-            (void)hipEventRecord(e1, stream);
-            if (hipEventSynchronize(e1) != hipSuccess) { rc = 1; break; }
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, e0, e1);
-            ms = t < ms ? t : ms;
-        }
-        if (!rc && (best < 0 || ms < best_ms)) { best = c; best_ms = ms; }
-    }
-    g_prof_mask = saved_mask;
-    g_event_pool.push_back(e0);
-    g_event_pool.push_back(e1);
-    if (rc) return rc;
-    D4_REQUIRE(best >= 0, "gemm_x3: no configuration for M=%d N=%d K=%d flags=%d", p.M, p.N, p.K, p.flags);
-    if (getenv("D4_GEMM_LOG"))
-        fprintf(stderr, "[d4 gemm_x3] tuned M %6d N %5d K %5d batch %2d flags %3d -> %s (%.1f us)\n", p.M, p.N, p.K, p.batch, p.flags, gemm_x3_config_name(best), 500.f * best_ms);
-    *best_out = best;
-    return 0;
-}
-
-static int gemm_v3(const GemmArgs& p, hipStream_t stream) {
-    const bool tune_on = tune_mode() != 0;
-    const int nb = p.batch > 0 ? p.batch : 1;
-    if (g_forced_cfg >= 300 && gemm_x3_config_valid(g_forced_cfg - 300, p)) return launch_v3(g_forced_cfg - 300, p, stream);
-    const TuneKey key{p.M, p.N, p.K, p.flags, p.batch};
-    tune_cache_load();
-    auto it = g_tuned3.find(key);
-    if (it != g_tuned3.end() && gemm_x3_config_valid(it->second, p)) return launch_v3(it->second, p, stream);
-    const bool idempotent = !(p.flags & GEMM_ACCUMULATE) && p.R != p.C && p.A != p.C;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    if (!tune_on || !idempotent || cap != hipStreamCaptureStatusNone || 2.0 * p.M * p.N * p.K * nb < 1e8)
-        return launch_v3(gemm_x3_heuristic(p), p, stream);
-    D4_TUNE_STRICT_CHECK(p, nb);
-    int best = 0;
-    if (int rc = autotune_v3(p, stream, &best)) return rc;
-    g_tuned3[key] = best;
-    tune_cache_append(key, 300 + best);
-    return launch_v3(best, p, stream);
-}
-
-// ---- fp16x2 split-operand family (gemm_h2.hip; the opt-in `fp32_fp16x2` engine mode): launch with the optional event pair (ONE profile class for
-// all its tiles), timed choice among its tiles (every tile gives the same bits) ----
-static int launch_v4(int c, const GemmArgs& p, hipStream_t stream) {
-    const int cls = N_TILE_CFG + gemm2_configs() + gemm_x3_configs() + 1;
-    const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-    if (!timed) return gemm_h2_launch(c, p, stream);
-    ProfRec rec{};
-    rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-    rec.M = p.M; rec.N = p.N; rec.K = p.K; rec.flags = p.flags; rec.batch = p.batch;
-    gemm_h2_config_tile(c, &rec.bm, &rec.bn);
-    rec.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1);
-    if (int rc = gemm_h2_launch(c, p, stream, rec.a, rec.b)) return rc;
-    g_prof.push_back(rec);
-    return 0;
-}
-
-static int autotune_v4(const GemmArgs& p, hipStream_t stream, int* best_out) {
-    hipEvent_t e0 = prof_event(), e1 = prof_event();
-    const int saved_mask = g_prof_mask;
-    g_prof_mask = 0;
-    int best = -1, rc = 0;
-    float best_ms = 0.f;
-    for (int c = 0; c < gemm_h2_configs() && !rc; ++c) {
-        if (!gemm_h2_config_valid(c, p)) continue;
-        if ((rc = gemm_h2_launch(c, p, stream))) break;
-        float ms = 1e30f;
-        for (int rep = 0; rep < 2 && !rc; ++rep) {
-            (void)hipEventRecord(e0, stream);
-            if ((rc = gemm_h2_launch(c, p, stream))) break;
-            if ((rc = gemm_h2_launch(c, p, stream))) break;
-            (void)hipEventRecord(e1, stream);
-            if (hipEventSynchronize(e1) != hipSuccess) { rc = 1; break; }
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, e0, e1);
-            ms = t < ms ? t : ms;
-        }
-        if (!rc && (best < 0 || ms < best_ms)) { best = c; best_ms = ms; }
-    }
-    g_prof_mask = saved_mask;
-    g_event_pool.push_back(e0);
-    g_event_pool.push_back(e1);
-    if (rc) return rc;
-    D4_REQUIRE(best >= 0, "gemm_h2: no configuration for M=%d N=%d K=%d flags=%d", p.M, p.N, p.K, p.flags);
-    if (getenv("D4_GEMM_LOG"))
-        fprintf(stderr, "[d4 gemm_h2] tuned M %6d N %5d K %5d batch %2d flags %3d -> %s (%.1f us)\n", p.M, p.N, p.K, p.batch, p.flags, gemm_h2_config_name(best), 500.f * best_ms);
-    *best_out = best;
-    return 0;
-}
-
-static int gemm_v4(const GemmArgs& p, hipStream_t stream) {
-    const bool tune_on = tune_mode() != 0;
-    const int nb = p.batch > 0 ? p.batch : 1;
-    if (g_forced_cfg >= 400 && gemm_h2_config_valid(g_forced_cfg - 400, p)) return launch_v4(g_forced_cfg - 400, p, stream);
-    const TuneKey key{p.M, p.N, p.K, p.flags, p.batch};
-    tune_cache_load();
-    auto it = g_tuned4.find(key);
-    if (it != g_tuned4.end() && gemm_h2_config_valid(it->second, p)) return launch_v4(it->second, p, stream);
-    const bool idempotent = !(p.flags & GEMM_ACCUMULATE) && p.R != p.C && p.A != p.C;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    if (!tune_on || !idempotent || cap != hipStreamCaptureStatusNone || 2.0 * p.M * p.N * p.K * nb < 1e8)
-        return launch_v4(gemm_h2_heuristic(p), p, stream);
-    D4_TUNE_STRICT_CHECK(p, nb);
-    int best = 0;
-    if (int rc = autotune_v4(p, stream, &best)) return rc;
-    g_tuned4[key] = best;
-    tune_cache_append(key, 400 + best);
-    return launch_v4(best, p, stream);
-}
-
-// Which calls of an fp16x2 engine the family takes is a RULE on the call's shape (never a timing): the families differ in their bits.  Measured on
-// MI355X (tools/gemm_h2_bench.py, profiles/r05c_*): x1.2-2.0 the f32-input MFMA kernels wherever a launch has a few hundred rows, N >= 256 and a k
-// loop of some length; level or behind on launches of under ~1.2 G multiply-adds (the 512 x 512 / 256 x 512 projections at 3584 rows) and at
-// K < 128; few-row calls stay on the few-row kernel.
-bool gemm_h2_takes(const GemmArgs& p) {
-    if (!p.Wb || p.wplane <= 0 || !p.wscale || !gemm_h2_applicable(p) || gemm_skinny_applicable(p)) return false;
-    if (g_forced_cfg >= 0 && g_forced_cfg < 400) return false;       // a forced tile of another family
-    if (g_forced_cfg >= 400) return true;
-    return p.M >= 256 && p.K >= 128 && p.N >= 64 && (double)p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1) >= 1.2e9;
-}
-
-// Two independent non-transposed fp32 GEMMs (the attention pool's query and key projections): ONE grid on the LDS-DMA family when both calls
-// would have run there anyway (same family, same k order, same bits as the two separate launches), else one after the other.  The tile
-// configuration is the one chosen for the larger problem.
-int gemm_pair(const GemmArgs& a_in, const GemmArgs& b_in, hipStream_t stream) {
-    std::lock_guard<std::recursive_mutex> lock(gemm_mutex());
-    GemmArgs a = a_in, b = b_in;
-    if (int rc = gemm_rowmap_refused(a, "gemm_pair")) return rc;
-    if (int rc = gemm_rowmap_refused(b, "gemm_pair")) return rc;
-    const bool fp32_rule = (!a.Wb || (a.wplane > 0 && a.N < 2048)) && (!b.Wb || (b.wplane > 0 && b.N < 2048)) &&     // neither goes to a bf16 / split-operand kernel
-                           !gemm_h2_takes(a) && !gemm_h2_takes(b);
-    if (fp32_rule && g_forced_cfg < 0 && a.M > 0 && b.M > 0 && a.K == b.K && use_v2(a) && use_v2(b) && !gemm_skinny_applicable(a) &&
-        !gemm_skinny_applicable(b) && gemm2_pair_applicable(a, b)) {
-        a.Wb = nullptr; a.wplane = 0; a.wscale = nullptr; b.Wb = nullptr; b.wplane = 0; b.wscale = nullptr;
-        const GemmArgs& big = (double)a.M * a.N >= (double)b.M * b.N ? a : b;
-        tune_cache_load();
-        auto it = g_tuned2.find(TuneKey{big.M, big.N, big.K, big.flags, big.batch});
-        const int c = it != g_tuned2.end() ? it->second : heuristic_v2(big);
-        if (gemm2_pair_config_ok(c) && gemm2_config_valid(c, a) && gemm2_config_valid(c, b)) {
-            const int cls = N_TILE_CFG + c;
-            const bool timed = ((g_prof_mask >> cls) & 1) && (g_prof_tick++ % g_prof_stride) == 0;
-            if (!timed) return gemm2_pair_launch(c, a, b, stream);
-            ProfRec rec{};
-            rec.a = prof_event(); rec.b = prof_event(); rec.cls = cls;
-            rec.M = a.M + b.M; rec.N = big.N; rec.K = big.K; rec.flags = big.flags; rec.batch = 2;
-            gemm2_config_tile(c, &rec.bm, &rec.bn);
-            rec.flops = 2.0 * a.M * a.N * a.K + 2.0 * b.M * b.N * b.K;
-            if (int rc = gemm2_pair_launch(c, a, b, stream, rec.a, rec.b)) return rc;
-            g_prof.push_back(rec);
-            return 0;
-        }
-    }
-    if (int rc = gemm(a_in, stream)) return rc;
-    return gemm(b_in, stream);
-}
-
-// The dispatcher's process-global state (tile choices per shape, the tuning-cache file, the profiling log and its event pool, the static
-// per-instantiation attribute flags) is guarded by ONE recursive mutex taken at this entry: ctypes releases the GIL, and two engines may be
-// driven from two host threads (tools/two_stream_rollout.py).  Launches are asynchronous, so the lock is held for microseconds except
-// while a shape is being timed for the first time.
-static std::recursive_mutex g_gemm_mu;
-static std::recursive_mutex& gemm_mutex() { return g_gemm_mu; }
+// ---- THE route: which family runs a call --------------------------------------------------------------------------------------------------------
+// A RULE on the call's shape and layout, never a timing: the families sum k in different orders, so a timing-dependent choice between them would make
+// results depend on the tuner.  (DESIGN.md 29 has the table.)
 
 // The output row map (GemmArgs::rm_*): well formed, and on a call whose epilogue the two mapped kernels implement (bias and row scale only).
 bool gemm_rowmap_ok(const GemmArgs& p) {
@@ -977,91 +778,129 @@ int gemm_rowmap_refused(const GemmArgs& p, const char* who) {
     return 0;
 }
 
-// Would gemm() below run this call on the persistent split-operand kernel (gemm_x3sk.hip)?  The same tests in the same order as gemm().
-bool gemm_rule_takes_x3sk(const GemmArgs& p) {
-    if (p.M < 1 || g_forced_cfg >= 0 || (p.flags & (GEMM_TRANS_A | GEMM_TRANS_B)) || !p.Wb || p.wplane <= 0 || p.wscale) return false;
-    const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
-    return wide && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && (p.rule_M > 0 ? p.rule_M : p.M) >= 1024));
+// Which calls of an fp16x2 engine that family takes.  Measured on MI355X (tools/gemm_h2_bench.py, profiles/r05c_*): x1.2-2.0 the f32-input MFMA kernels
+// wherever a launch has a few hundred rows, N >= 256 and a k loop of some length; level or behind on launches of under ~1.2 G multiply-adds (the
+// 512 x 512 / 256 x 512 projections at 3584 rows) and at K < 128; few-row calls stay on the few-row kernel.
+static bool h2_rule(const GemmArgs& p, const Forced& f) {
+    if (!gemm_h2_applicable(p) || gemm_skinny_applicable(p)) return false;
+    if (f.family >= 0) return f.family == D4_GEMM_H2;       // a forced tile of this family: every call it can run; of another family: none
+    return p.M >= 256 && p.K >= 128 && p.N >= 64 && (double)p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1) >= 1.2e9;
 }
 
-// Would gemm() below run this call — these exact arguments, weight planes and rule_M included — on the LDS-DMA f32 family (gemm2.hip through gemm_v2)?
-// The same tests in the same order as gemm(); a forced configuration answers false (a forced call is not taken by rule).  The engine asks this before
-// it replaces a product by a kernel that carries that family's bits (engine.hip: the latent-token ends, the last layer's split projection).
-bool gemm_rule_takes_v2(const GemmArgs& p) {
-    if (p.M < 1 || g_forced_cfg >= 0) return false;
-    const bool ta = p.flags & GEMM_TRANS_A, tb = p.flags & GEMM_TRANS_B;
-    if (ta || tb) return false;
-    if (p.Wb && p.wplane > 0 && p.wscale) {
-        if (gemm_h2_takes(p)) return false;
-        GemmArgs q = p;
+static GemmRoute route(const GemmArgs& p, const Forced& f) {
+    GemmRoute r{D4_GEMM_TILE, p};
+    GemmArgs& q = r.args;
+    const bool by_rule = f.family < 0;
+    // fp16x2 engine mode (two fp16 planes of W + row scales, gemm_h2.hip): every call the rule does not name drops the planes and runs on the f32-input kernels
+    if (q.Wb && q.wplane > 0 && q.wscale) {
+        if (h2_rule(q, f)) { r.family = D4_GEMM_H2; return r; }
         q.Wb = nullptr; q.wplane = 0; q.wscale = nullptr; q.aexp = nullptr;
-        return gemm_rule_takes_v2(q);
     }
-    if (p.Wb && p.wplane > 0) {
-        const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
-        const int rm = p.rule_M > 0 ? p.rule_M : p.M;
-        if (wide && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && rm >= 1024))) return false;
-        if (wide && rm >= 256 && gemm_x3_applicable(p)) return false;
-        GemmArgs q = p;
+    // split-operand fp32 (three bf16 planes of W).  Measured on MI355X (tools/gemm_x3_bench.py, profiles/r02_gemm_split_operands.txt): it wins where a
+    // launch has enough wide tiles to hide its heavier staging — the SiLU-GLU input projections (N = 2 x 1376 ... 5504: 1.2-1.35x the f32-input MFMA
+    // kernels) and other N >= 2048 projections (level to 1.3x) — and loses on the N <= 1552 shapes (0.8-0.95x; with the whole rollout as the clock
+    // +3 .. +6 ms: profiles/r05b_x3_every_call_ab.txt); few-row calls stay on the few-row kernel.  Every such call of >= 1024 rows runs on the PERSISTENT
+    // form (gemm_x3sk.hip: whole rounds as plain tiles, a last round that is at most half full as 128 x 64 half tiles — bit-identical to the plain kernel;
+    // same-box A/B pairs, profiles/r03l_ab_late_changes.txt: 188.8 vs 191.8-192.4 (half-tile calls only) vs 199.3-200.0 ms (never) per step on a
+    // mid-speed box, level on the fastest one).  Every other call drops the planes.
+    if (q.Wb && q.wplane > 0) {
+        const bool wide = ((q.flags & GEMM_SWIGLU) || q.N >= 2048) && !gemm_skinny_applicable(q);
+        const int rm = q.rule_M > 0 ? q.rule_M : q.M;       // (rule_M: a caller that runs a subset of a product's rows keeps the family of the whole product)
+        if (wide && by_rule && (gemm_x3sk_rule(q) || (gemm_x3sk_applicable(q) && rm >= 1024))) { r.family = D4_GEMM_X3SK; return r; }
+        if (wide && rm >= 256 && gemm_x3_applicable(q)) { r.family = D4_GEMM_X3; return r; }
         q.Wb = nullptr; q.wplane = 0;
-        return gemm_rule_takes_v2(q);
     }
-    if (p.Wb) return false;
-    if (gemm_skinny_applicable(p) || gemm2_ksplit_rule(p)) return false;
-    return use_v2(p);
+    // bf16 engine: with a bf16 image of the activation both operands come by LDS-DMA
+    if (q.Wb) { r.family = q.Ab && gemm_bf16a_applicable(q) ? D4_GEMM_BF16A : D4_GEMM_BF16; return r; }
+    // f32 operands.  A forced configuration of the LDS-DMA family runs wherever it is valid, ahead of the few-row kernel
+    if (f.family == D4_GEMM_V2 && gemm2_config_valid(f.config, q)) r.family = D4_GEMM_V2;
+    else if (gemm_skinny_applicable(q)) r.family = D4_GEMM_SKINNY;
+    // few rows x long K (the heads' hidden layers at rollout batch): the contraction cut four ways inside the workgroup
+    else if (by_rule ? gemm2_ksplit_rule(q) : (f.family == D4_GEMM_V2_KSPLIT && gemm2_ksplit_applicable(q))) r.family = D4_GEMM_V2_KSPLIT;
+    // (a forced tile of a mirror-weight family leaves the f32 calls to the rule)
+    else if ((by_rule || f.family == D4_GEMM_X3 || f.family == D4_GEMM_H2) && gemm2_applicable(q)) r.family = D4_GEMM_V2;
+    return r;
 }
+GemmRoute gemm_route(const GemmArgs& p, int forced) { return route(p, forced_fp32(forced_decode(forced))); }
 
-int gemm(const GemmArgs& p, hipStream_t stream) {
-    std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
-    D4_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad sizes M=%d N=%d K=%d", p.M, p.N, p.K);
-    if (p.M == 0) return 0;
+// The engine asks these before it replaces a product by a kernel that carries a family's bits (engine.hip: the latent-token ends, the last layer's
+// split projection, the FF fill): would gemm() run this call — these exact arguments, weight planes and rule_M included — there BY ITS RULES?  A forced
+// configuration answers false to the first two (a forced call is not taken by rule).
+bool gemm_rule_takes_x3sk(const GemmArgs& p) { return route(p, g_forced).family == D4_GEMM_X3SK; }
+bool gemm_rule_takes_v2(const GemmArgs& p) { return g_forced.family < 0 && route(p, g_forced).family == D4_GEMM_V2; }
+bool gemm_h2_takes(const GemmArgs& p) { return route(p, g_forced).family == D4_GEMM_H2; }
+
+static int gemm_check(const GemmArgs& p) {
     const bool ta = p.flags & GEMM_TRANS_A, tb = p.flags & GEMM_TRANS_B;
+    D4_REQUIRE(p.M >= 0 && p.N > 0 && p.K > 0, "gemm: bad sizes M=%d N=%d K=%d", p.M, p.N, p.K);
+    if (p.M == 0) return 0;                      // nothing to run, nothing else to check
     D4_REQUIRE((p.lda % 4) == 0 && (p.ldw % 4) == 0, "gemm: lda/ldw must be multiples of 4 (got %d, %d)", p.lda, p.ldw);
     D4_REQUIRE(((uintptr_t)p.A % 16) == 0 && ((uintptr_t)p.W % 16) == 0, "gemm: operands must be 16-byte aligned");
     D4_REQUIRE(!((p.flags & GEMM_RMS_ROWSCALE) && ta), "gemm: rms rowscale needs a non-transposed A");
     D4_REQUIRE(!((p.flags & GEMM_SWIGLU) && (p.N % 64) != 0), "gemm: swiglu needs N %% 64 == 0 (packed pairs)");
     D4_REQUIRE(!((p.flags & GEMM_SWIGLU) && (ta || tb)), "gemm: swiglu epilogue is forward-only");
     D4_REQUIRE(gemm_rowmap_ok(p), "gemm: bad output row map (Sc=%d lo=%d nr=%d) or an epilogue it does not cover (flags=%d)", p.rm_Sc, p.rm_lo, p.rm_nr, p.flags);
-    // fp16x2 engine mode (two fp16 planes of W + row scales, gemm_h2.hip): the rule gemm_h2_takes names the calls; every other call drops the
-    // planes and runs on the f32-input kernels
-    if (p.Wb && p.wplane > 0 && p.wscale) {
-        if (gemm_h2_takes(p)) { if (int rc = gemm_rowmap_refused(p, "gemm_h2")) return rc; return gemm_v4(p, stream); }
-        GemmArgs q = p;
-        q.Wb = nullptr; q.wplane = 0; q.wscale = nullptr; q.aexp = nullptr;
-        return gemm(q, stream);
+    return 0;
+}
+// d4_gemm_route: the family gemm() would run the call on under the current hook, after gemm()'s own argument checks
+int gemm_route_checked(const GemmArgs& p, int* family) {
+    if (int rc = gemm_check(p)) return rc;
+    *family = route(p, g_forced).family;
+    return 0;
+}
+
+int gemm(const GemmArgs& p, hipStream_t stream) {
+    std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
+    if (int rc = gemm_check(p)) return rc;
+    if (p.M == 0) return 0;
+    const GemmRoute r = route(p, g_forced);
+    const GemmArgs& q = r.args;
+    switch (r.family) {
+        case D4_GEMM_H2:
+            if (int rc = gemm_rowmap_refused(q, "gemm_h2")) return rc;
+            return tuned_launch(kFamilies[FAM_H2], q, stream);
+        case D4_GEMM_X3SK: return launch_x3sk(q, stream);
+        case D4_GEMM_X3: return tuned_launch(kFamilies[FAM_X3], q, stream);
+        case D4_GEMM_BF16A:
+            if (int rc = gemm_rowmap_refused(q, "gemm_bf16")) return rc;
+            return gemm_bf16a(q, stream);
+        case D4_GEMM_BF16: return gemm_bf16(q, stream);             // (refuses the map itself)
+        case D4_GEMM_SKINNY: return gemm_skinny(q, stream);
+        case D4_GEMM_V2_KSPLIT: return launch_ksplit(q, stream);
+        case D4_GEMM_V2: return tuned_launch(kFamilies[FAM_V2], q, stream);
     }
-    // split-operand fp32 (three bf16 planes of W): few-row calls stay on the few-row kernel (a rule on the shape, like every family choice)
-    if (p.Wb && p.wplane > 0) {
-        // Which calls take it is a RULE on the call's shape (never a timing).  Measured on MI355X (tools/gemm_x3_bench.py,
-        // profiles/r02_gemm_split_operands.txt): it wins where a launch has enough wide tiles to hide its heavier staging — the SiLU-GLU
-        // input projections (N = 2 x 1376 ... 5504: 1.2-1.35x the f32-input MFMA kernels) and other N >= 2048 projections (level to 1.3x) —
-        // and loses on the N <= 1552 shapes (0.8-0.95x; with the whole rollout as the clock +3 .. +6 ms: profiles/r05b_x3_every_call_ab.txt).
-        // Every such call of >= 1024 rows runs on the PERSISTENT form (gemm_x3sk.hip: whole rounds as plain tiles, a last round that is at most
-        // half full as 128 x 64 half tiles — bit-identical to the plain kernel; same-box A/B pairs, profiles/r03l_ab_late_changes.txt: 188.8 vs
-        // 191.8-192.4 (half-tile calls only) vs 199.3-200.0 ms (never) per step on a mid-speed box, level on the fastest one).
-        const bool wide = ((p.flags & GEMM_SWIGLU) || p.N >= 2048) && !gemm_skinny_applicable(p);
-        // (rule_M: a caller that runs a subset of a product's rows keeps the family of the whole product)
-        const int rm = p.rule_M > 0 ? p.rule_M : p.M;
-        if (wide && g_forced_cfg < 0 && (gemm_x3sk_rule(p) || (gemm_x3sk_applicable(p) && rm >= 1024))) return launch_v3sk(p, stream);
-        if (wide && rm >= 256 && gemm_x3_applicable(p)) return gemm_v3(p, stream);
-        GemmArgs q = p;
-        q.Wb = nullptr; q.wplane = 0;
-        return gemm(q, stream);
+    if (int rc = gemm_rowmap_refused(q, "gemm (first fp32 family)")) return rc;
+    return tuned_launch(kFamilies[FAM_TILE], q, stream);
+}
+
+// Two independent non-transposed fp32 GEMMs (the attention pool's query and key projections): ONE grid on the LDS-DMA family when the route sends both
+// calls to gemm2.hip's kernels anyway (same k order, same bits as two launches of that family), else one after the other.  The pair form keeps two
+// limits of its own: nothing forced, and a call that carries mirror weights only below N = 2048.  The tile configuration is the one chosen for the
+// larger problem.
+int gemm_pair(const GemmArgs& a_in, const GemmArgs& b_in, hipStream_t stream) {
+    std::lock_guard<std::recursive_mutex> lock(g_gemm_mu);
+    if (int rc = gemm_rowmap_refused(a_in, "gemm_pair")) return rc;
+    if (int rc = gemm_rowmap_refused(b_in, "gemm_pair")) return rc;
+    const GemmRoute ra = route(a_in, g_forced), rb = route(b_in, g_forced);
+    const GemmArgs &a = ra.args, &b = rb.args;
+    auto lds_dma = [](const GemmArgs& in, const GemmRoute& r) { return (r.family == D4_GEMM_V2 || r.family == D4_GEMM_V2_KSPLIT) && (!in.Wb || in.N < 2048); };
+    if (g_forced.family < 0 && lds_dma(a_in, ra) && lds_dma(b_in, rb) && a.K == b.K && gemm2_pair_applicable(a, b)) {
+        const Family& F = kFamilies[FAM_V2];
+        const GemmArgs& big = (double)a.M * a.N >= (double)b.M * b.N ? a : b;
+        tune_cache_load();
+        auto it = F.tuned->find(TuneKey{big.M, big.N, big.K, big.flags, big.batch});
+        const int c = it != F.tuned->end() ? it->second : F.heuristic(big);
+        if (gemm2_pair_config_ok(c) && gemm2_config_valid(c, a) && gemm2_config_valid(c, b)) {
+            GemmArgs both = big;                  // what the per-shape table shows for the launch
+            both.M = a.M + b.M; both.batch = 2;
+            int bm, bn;
+            F.config_tile(c, &bm, &bn);
+            return timed_launch(F.first_class + c, both, bm, bn, 2.0 * a.M * a.N * a.K + 2.0 * b.M * b.N * b.K,
+                                [&](hipEvent_t ea, hipEvent_t eb) { return gemm2_pair_launch(c, a, b, stream, ea, eb); });
+        }
     }
-    if (p.Wb) if (int rc = gemm_rowmap_refused(p, "gemm_bf16")) return rc;
-    if (p.Wb && p.Ab && gemm_bf16a_applicable(p)) return gemm_bf16a(p, stream);     // bf16 engine, the activation has a bf16 image: both operands by LDS-DMA
-    if (p.Wb) return gemm_bf16(p, stream);
-    // test hook: 100 + c forces configuration c of the second family, 0 .. N_TILE_CFG-1 a configuration of this one
-    if (g_forced_cfg >= 100 && g_forced_cfg != 199 && gemm2_config_valid(g_forced_cfg - 100, p)) return launch_v2(g_forced_cfg - 100, p, stream);
-    if (gemm_skinny_applicable(p)) return gemm_skinny(p, stream);
-    // few rows x long K (the heads' hidden layers at rollout batch): the contraction cut four ways inside the workgroup — a rule on the shape
-    if ((g_forced_cfg < 0 && gemm2_ksplit_rule(p)) || (g_forced_cfg == 199 && gemm2_ksplit_applicable(p))) return launch_v2ks(p, stream);      // (199: test hook, any shape it can run)
-    if ((g_forced_cfg < 0 || g_forced_cfg >= 300) && use_v2(p)) return gemm_v2(p, stream);      // (300 + c forces a tile of the split-operand family only)
-    if (int rc = gemm_rowmap_refused(p, "gemm (first fp32 family)")) return rc;
-    if (!ta && !tb) return launch_t<false, false>(p, stream);
-    if (!ta && tb) return launch_t<false, true>(p, stream);
-    if (ta && tb) return launch_t<true, true>(p, stream);
-    return launch_t<true, false>(p, stream);
+    if (int rc = gemm(a_in, stream)) return rc;
+    return gemm(b_in, stream);
 }
 
 }  // namespace d4

@@ -246,6 +246,10 @@ bool gemm2_config_valid(int c, const GemmArgs& p) {
     return true;
 }
 
+// Static choice, for a shape that cannot be timed: 64x64 with three blocks per CU or its SiLU-GLU capable form — the best or within a few per cent of it on
+// every shape measured; the timed choice refines this where a call can be repeated
+int gemm2_heuristic(const GemmArgs& p) { return (p.flags & GEMM_SWIGLU) ? V2_64x64_s : V2_64x64; }
+
 template <int WGM, int WGN, int TM, int TN, int NS, int BK>
 static int launch2(const GemmArgs& p, hipStream_t stream, hipEvent_t ea, hipEvent_t eb) {
     constexpr int BM = WGM * TM * 16, BN = WGN * TN * 16;

@@ -272,6 +272,19 @@ int gemm_bf16_profile_read(double* ms, double* flops, int64_t* count) {
     return 0;
 }
 
+static inline double bf16_flops(const GemmArgs& p) { return p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1); }
+
+// The timed launch of this file's three launchers: `launch(ea, eb)` enqueues the kernel; every g_bprof_stride-th launch gets an event pair of its own
+// (created here, destroyed by gemm_bf16_profile_read) and the record `r`.
+template <class Launch>
+static int bf16_timed_launch(Bf16Prof r, Launch&& launch) {
+    if (!(g_bprof_stride > 0 && (g_bprof_tick++ % g_bprof_stride) == 0)) return launch(nullptr, nullptr);
+    D4_HIP(hipEventCreate(&r.a)); D4_HIP(hipEventCreate(&r.b));
+    const int rc = launch(r.a, r.b);
+    g_bprof.push_back(r);
+    return rc;
+}
+
 template <int BM, int BN, int WGM, int WGN, int BK>
 static int launch_bf16(const GemmArgs& p, hipStream_t stream) {
     constexpr int LDS_LD = BK + 8;
@@ -283,18 +296,12 @@ static int launch_bf16(const GemmArgs& p, hipStream_t stream) {
         attr_set.done();
     }
     const dim3 grid(cdiv(p.M, BM) * cdiv(p.N, BN), p.batch > 0 ? p.batch : 1), block(WGM * WGN * 64);
-    if (g_bprof_stride > 0 && (g_bprof_tick++ % g_bprof_stride) == 0) {
-        Bf16Prof r{};
-        D4_HIP(hipEventCreate(&r.a)); D4_HIP(hipEventCreate(&r.b));
-        r.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1);
-        r.M = p.M; r.N = p.N; r.K = p.K; r.flags = p.flags; r.batch = p.batch;
-        hipExtLaunchKernelGGL(k, grid, block, (uint32_t)lds, stream, r.a, r.b, 0, p);
-        g_bprof.push_back(r);
-    } else {
-        hipLaunchKernelGGL(k, grid, block, lds, stream, p);
-    }
-    D4_LAUNCH_CHECK();
-    return 0;
+    return bf16_timed_launch(Bf16Prof{nullptr, nullptr, bf16_flops(p), p.M, p.N, p.K, p.flags, p.batch}, [&](hipEvent_t ea, hipEvent_t eb) {
+        if (ea) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)lds, stream, ea, eb, 0, p);
+        else hipLaunchKernelGGL(k, grid, block, lds, stream, p);
+        D4_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // bf16 activations + bf16 weights (gemm_bf16a.hip): tile by shape rule, with this file's optional per-launch event pair
@@ -304,29 +311,13 @@ int gemm_bf16a(const GemmArgs& p, hipStream_t stream) {
     D4_REQUIRE(gemm_bf16a_applicable(p), "gemm_bf16a: call not supported (M=%d N=%d K=%d flags=%d)", p.M, p.N, p.K, p.flags);
     D4_REQUIRE(p.C || p.Cb, "gemm_bf16a: no output");
     const int c = gemm_bf16a_config_valid(g_bf16a_forced, p) ? g_bf16a_forced : gemm_bf16a_rule(p);
-    if (g_bprof_stride > 0 && (g_bprof_tick++ % g_bprof_stride) == 0) {
-        Bf16Prof r{};
-        D4_HIP(hipEventCreate(&r.a)); D4_HIP(hipEventCreate(&r.b));
-        r.flops = p.algo_flops > 0 ? p.algo_flops : 2.0 * p.M * p.N * p.K * (p.batch > 0 ? p.batch : 1);
-        r.M = p.M; r.N = p.N; r.K = p.K; r.flags = p.flags | 1024; r.batch = p.batch;          // (1024 marks the bf16-activation kernel in the shape log)
-        const int rc = gemm_bf16a_launch(c, p, stream, r.a, r.b);
-        g_bprof.push_back(r);
-        return rc;
-    }
-    return gemm_bf16a_launch(c, p, stream, nullptr, nullptr);
+    return bf16_timed_launch(Bf16Prof{nullptr, nullptr, bf16_flops(p), p.M, p.N, p.K, p.flags | 1024, p.batch},          // (1024 marks the bf16-activation kernel in the shape log)
+                             [&](hipEvent_t ea, hipEvent_t eb) { return gemm_bf16a_launch(c, p, stream, ea, eb); });
 }
 
 int gemm_bf16a_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t stream) {
-    if (g_bprof_stride > 0 && (g_bprof_tick++ % g_bprof_stride) == 0) {
-        Bf16Prof r{};
-        D4_HIP(hipEventCreate(&r.a)); D4_HIP(hipEventCreate(&r.b));
-        r.flops = 2.0 * a.M * a.N * a.K + 2.0 * b.M * b.N * b.K;
-        r.M = a.M + b.M; r.N = a.N; r.K = a.K; r.flags = a.flags | 1024 | 2048; r.batch = 2;       // (2048 marks the pair form in the shape log)
-        const int rc = gemm_bf16a_pair_launch(a, b, stream, r.a, r.b);
-        g_bprof.push_back(r);
-        return rc;
-    }
-    return gemm_bf16a_pair_launch(a, b, stream, nullptr, nullptr);
+    return bf16_timed_launch(Bf16Prof{nullptr, nullptr, 2.0 * a.M * a.N * a.K + 2.0 * b.M * b.N * b.K, a.M + b.M, a.N, a.K, a.flags | 1024 | 2048, 2},       // (2048 marks the pair form in the shape log)
+                             [&](hipEvent_t ea, hipEvent_t eb) { return gemm_bf16a_pair_launch(a, b, stream, ea, eb); });
 }
 
 bool gemm_bf16_applicable(const GemmArgs& p) {

@@ -57,10 +57,16 @@ struct GemmArgs {
 static_assert(sizeof(GemmArgs) == 232, "GemmArgs is a kernel argument: the row map lives in its alignment gaps");
 bool gemm_rowmap_ok(const GemmArgs& p);                   // gemm.hip: no map, or a well-formed one on a call whose epilogue the mapped kernels implement
 int gemm_rowmap_refused(const GemmArgs& p, const char* who);   // gemm.hip: 0 when p carries no row map, else the error "who: ... does not implement the output row map"
-bool gemm_rule_takes_x3sk(const GemmArgs& p);             // gemm.hip: would gemm() run exactly this call on the persistent split-operand kernel by its rules?
+// gemm.hip: THE route.  Which family (a D4_GEMM_* code of include/d4hip.h) runs the call under the test-hook code `forced` (< 0: none), and the call as that
+// family sees it (weight planes dropped where the rule drops them).  Pure: no launch, no lock, no tuner state.
+struct GemmRoute { int family; GemmArgs args; };
+GemmRoute gemm_route(const GemmArgs& p, int forced);
+int gemm_route_checked(const GemmArgs& p, int* family);   // gemm()'s argument checks, then the route's family under the current hook (d4_gemm_route)
+// ... asked about one family under the current hook (the engine passes these as function pointers):
+bool gemm_rule_takes_x3sk(const GemmArgs& p);             // would gemm() run exactly this call on the persistent split-operand kernel by its rules?
+bool gemm_rule_takes_v2(const GemmArgs& p);               // ... on the LDS-DMA f32 family (gemm2.hip) by its rules?
 
 int gemm(const GemmArgs& p, hipStream_t stream);
-bool gemm_rule_takes_v2(const GemmArgs& p);               // gemm.hip: would gemm() run exactly this call on the LDS-DMA f32 family (gemm2.hip) by its rules?
 // bf16 MFMA path (gemm_bf16.hip): A fp32 rounded to bf16 on the way into LDS, W pre-converted, fp32 accumulate / epilogue
 bool gemm_bf16_applicable(const GemmArgs& p);
 int gemm_bf16(const GemmArgs& p, hipStream_t stream);
@@ -122,6 +128,7 @@ bool gemm2_config_valid(int c, const GemmArgs& p);
 int gemm2_configs();
 const char* gemm2_config_name(int c);
 void gemm2_config_tile(int c, int* bm, int* bn);
+int gemm2_heuristic(const GemmArgs& p);
 int gemm2_launch(int c, const GemmArgs& p, hipStream_t stream, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
 bool gemm2_ksplit_applicable(const GemmArgs& p);
 bool gemm2_ksplit_rule(const GemmArgs& p);               // few rows x long K: the contraction cut four ways inside the workgroup (gemm2_ksplit_kernel)
@@ -145,7 +152,8 @@ extern int g_time_attn_tiled;            // attn_tiled.hip: 0 (default) the tile
 extern int g_space_attn_tiled;           // attn_tiled.hip: 1 the within-frame attention of the training path takes the tiled core at any size (test hook; default 0: above 64 tokens with d4_train_wide_set(1))
 extern int g_cross_attn_tiled;           // attn_tiled.hip: the same for the cross attentions
 extern int g_small_attn_wide;            // attn_wide_mfma.hip: 1 a small_attn call with `wide` set takes the wide core at any size (test hook; default 0: above 64 items per side)
-int gemm_force_config(int id);                             // test hook; returns the number of configurations
+int gemm_force_config(int code);                           // test hook (d4_gemm_force_config): decodes the code, sets one family's hook and clears the others; returns
+                                                           // the number of configurations of the family addressed
 int gemm_configs();                                        // first fp32 family (gemm.hip)
 bool gemm_config_valid(int c, const GemmArgs& p);          // gemm() under gemm_force_config(c) runs configuration c of the first family on this call
 const char* gemm_profile_class_name(int c);

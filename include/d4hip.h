@@ -627,6 +627,9 @@ typedef struct d4_gemm_desc {
 #define D4_GEMM_FAMILIES 9
 /* Number of configurations of a family (1 for the single-form targets, -1 for an unknown family). */
 int d4_gemm_family_configs(int family);
+/* The family the dispatcher (d4::gemm) would run `d` on, under the current d4_gemm_force_config hook and with GemmArgs::rule_M = rule_M (0: the call's own
+ * row count); -1 with d4_last_error set for a call the dispatcher rejects.  Host logic only: nothing is launched and no GPU is needed. */
+int d4_gemm_route(const d4_gemm_desc* d, int rule_M);
 /* Runs `d` on exactly the family / configuration named.  A call the family's `*_applicable` / `*_config_valid` refuses fails with an error that
  * starts "d4_gemm_run: call not supported" and names the reason; nothing falls through to another family. */
 int d4_gemm_run(const d4_gemm_desc* d, int family, int config, void* stream);
