@@ -285,6 +285,8 @@ SYMBOLS = {
     'd4_recon_loss_fwd_bwd': (_I, [_P] * 4 + [_I] * 7 + [_P, _P, _P, C.c_size_t, _P]),
     'd4_pack_tokens_bf16': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'd4_muon_plan_create': (_I, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(_P)]),
+    'd4_muon_plan_create_products': (_I, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, _I, C.POINTER(_P)]),
+    'd4_muon_plan_products': (_I, [_P]),
     'd4_muon_plan_destroy': (None, [_P]),
     'd4_muon_plan_workspace_bytes': (C.c_size_t, [_P]),
     'd4_muon_plan_passes': (_I, [_P]),

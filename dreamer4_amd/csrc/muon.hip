@@ -14,35 +14,21 @@
 //   Adam-atan2      multi-tensor kernel over a device pointer table, one launch for the group.
 //   gradient norm   multi-tensor partial sums (one per 4096-element chunk) and a one-block final sum: fixed order, no float atomics.
 // Equal inputs and state give equal bits, whatever the pass partition: a matrix's arithmetic never depends on its neighbours in a launch.
+// A plan created with products = 1 keeps prepare and this file's launch sequence and takes normalise, the products and finish from csrc/muon_bf16.hip
+// (DESIGN.md 30); the description of a matrix, the plan and its table builder are in muon_plan.h for both.
 #include <math.h>
 #include <string.h>
 #include <vector>
 
 #include "../../include/d4hip.h"
 #include "common.h"
+#include "muon_plan.h"                // MuonMat, the plan and its table builder: shared with the bf16 form (csrc/muon_bf16.hip)
 
 namespace d4 {
 
-constexpr int MU_T = 128;             // output tile of a workgroup, and the padding unit of every work-buffer dimension
 constexpr int MU_BK = 16;             // k-tile
 constexpr int MU_LD = MU_T + 4;       // LDS row stride (floats): 16-byte aligned rows, transposing writes spread over all banks
-constexpr int MU_STRIP = 32;          // rows of the original matrix per prepare / finish workgroup
 constexpr int MT_CHUNK = 4096;        // elements per workgroup of the multi-tensor kernels
-
-struct MuonMat {                      // one matrix of a pass (device table)
-    float* w;                         // parameter (null: d4_newton_schulz, `out` is written without a read)
-    const float* g;                   // gradient / input
-    float* m;                         // momentum (null: u = g)
-    float* out;                       // destination of finish (== w for the optimiser)
-    int r, c;                         // shape as given
-    int R, C;                         // oriented: R = min(r, c) rows
-    int Rp, Cp;                       // padded to MU_T
-    int transposed;                   // r > c
-    int part0;                        // first partial of this matrix
-    int nparts;                       // strips (partials) of this matrix
-    float coef;                       // finish: out = decay * w + coef * X
-    int64_t x0, x1, a, b;             // float offsets of X, X', A, B in the pass's work buffer
-};
 
 __device__ __forceinline__ float lerp_t(float s, float e, float w) {          // torch.lerp's two-sided form
     return w < 0.5f ? s + w * (e - s) : e - (e - s) * (1.f - w);
@@ -344,23 +330,7 @@ static int mt_check(const char* who, int n, const int64_t* numel, const void* ta
 
 }  // namespace d4
 
-// ================================================================================================ plan
-struct d4_muon_plan {
-    struct Pass {
-        int first, count;                            // matrices [first, first + count)
-        int n_prep, n_sym, n_full;                   // workgroups of prepare / finish, of the symmetric stages, of the apply stage
-        size_t prep_off, sym_off, full_off;          // byte offsets in `tables`
-        size_t work_floats;
-    };
-    std::vector<d4::MuonMat> mats;                   // host image (pointers filled per call)
-    std::vector<Pass> passes;
-    std::vector<const void*> last;                   // pointers of the last upload (4 per matrix)
-    std::vector<float> last_coef;
-    char* tables = nullptr;                          // device: [MuonMat x n][per pass: prepare blocks, symmetric tiles, apply tiles]
-    size_t work_bytes = 0, part_floats = 0;
-    bool uploaded = false;
-};
-
+// ================================================================================================ plan (muon_plan.h)
 namespace d4 {
 
 static int muon_upload(d4_muon_plan* pl, hipStream_t s) {
@@ -370,7 +340,7 @@ static int muon_upload(d4_muon_plan* pl, hipStream_t s) {
     return 0;
 }
 
-// the fixed launch sequence of one call: per pass  prepare, steps x (gram, poly, apply), finish
+// the fixed launch sequence of one call: per pass  prepare, [bf16 products: normalise,] steps x (gram, poly, apply), finish
 static int muon_run(d4_muon_plan* pl, float* ws, const float* gnorm_sq, float max_norm, double beta, int nesterov, int steps, float a, float b, float c,
                     float eps, float decay, hipStream_t s) {
     const MuonMat* mats = reinterpret_cast<const MuonMat*>(pl->tables);
@@ -383,6 +353,17 @@ static int muon_run(d4_muon_plan* pl, float* ws, const float* gnorm_sq, float ma
         hipLaunchKernelGGL(muon_prepare_kernel, dim3(ps.n_prep), dim3(256), 0, s, mats, prep, work, partials, gnorm_sq, max_norm, (float)beta, (float)(1. - beta), nesterov);
         D4_LAUNCH_CHECK();
         int cur = 0;
+        if (pl->products == 1) {          // bf16 products: prepare wrote the fp32 u, normalise rounds X0 once, every buffer after it is bf16
+            if (int rc = muon_bf16_normalise(mats, prep, ps.n_prep, work, partials, eps, s)) return rc;
+            for (int it = 0; it < steps; ++it) {
+                if (int rc = muon_bf16_product(mats, sym, ps.n_sym, work, 0, cur, 0.f, 1.f, s)) return rc;
+                if (int rc = muon_bf16_product(mats, sym, ps.n_sym, work, 1, cur, b, c, s)) return rc;
+                if (int rc = muon_bf16_product(mats, full, ps.n_full, work, 2, cur, a, 1.f, s)) return rc;
+                cur ^= 1;
+            }
+            if (int rc = muon_bf16_finish(mats, prep, ps.n_prep, work, cur, decay, s)) return rc;
+            continue;
+        }
         for (int it = 0; it < steps; ++it) {
             const int first = it == 0;
             hipLaunchKernelGGL(muon_gemm_kernel<false>, dim3(ps.n_sym), dim3(256), 0, s, mats, sym, work, partials, 0, cur, 0.f, 1.f, first, eps);
@@ -423,86 +404,14 @@ static int muon_bind(d4_muon_plan* pl, const char* who, void* const* w, const vo
 extern "C" {
 
 int d4_muon_plan_create(int n, const int32_t* rows, const int32_t* cols, size_t workspace_bytes, d4_muon_plan** out) {
-    using namespace d4;
-    D4_REQUIRE(out, "d4_muon_plan_create: out is null");
-    *out = nullptr;
-    D4_REQUIRE(n >= 1 && rows && cols, "d4_muon_plan_create: n >= 1, rows and cols");
-    auto* pl = new d4_muon_plan;
-    pl->mats.resize(n);
-    pl->last.assign(4 * (size_t)n, nullptr);
-    pl->last_coef.assign(n, 0.f);
-    auto fail = [&]() { delete pl; return 2; };
-    auto pad = [](int v) { return (v + MU_T - 1) / MU_T * MU_T; };
-    int part = 0;
-    d4_muon_plan::Pass cur{0, 0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<int2> prep;
-    std::vector<int4> sym, full;
-    struct Built { std::vector<int2> prep; std::vector<int4> sym, full; };
-    std::vector<Built> built;
-    auto close = [&]() {
-        cur.n_prep = (int)prep.size(); cur.n_sym = (int)sym.size(); cur.n_full = (int)full.size();
-        pl->passes.push_back(cur);
-        built.push_back(Built{prep, sym, full});
-        if (cur.work_floats * 4 > pl->work_bytes) pl->work_bytes = cur.work_floats * 4;
-        prep.clear(); sym.clear(); full.clear();
-    };
-    for (int i = 0; i < n; ++i) {
-        if (!(rows[i] >= 1 && cols[i] >= 1)) { set_error("d4_muon_plan_create: matrix %d has rows = %d, cols = %d (both must be >= 1)", i, rows[i], cols[i]); return fail(); }
-        if (!(rows[i] <= (1 << 20) && cols[i] <= (1 << 20))) { set_error("d4_muon_plan_create: matrix %d: rows = %d, cols = %d exceed 2^20", i, rows[i], cols[i]); return fail(); }
-        MuonMat& d = pl->mats[i];
-        memset(&d, 0, sizeof(d));
-        d.r = rows[i]; d.c = cols[i];
-        d.transposed = d.r > d.c;
-        d.R = d.transposed ? d.c : d.r; d.C = d.transposed ? d.r : d.c;
-        d.Rp = pad(d.R); d.Cp = pad(d.C);
-        const int rp_o = d.transposed ? d.Cp : d.Rp;                     // padded rows of the original orientation
-        d.nparts = rp_o / MU_STRIP; d.part0 = part; part += d.nparts;
-        const size_t need = 2 * (size_t)d.Rp * d.Cp + 2 * (size_t)d.Rp * d.Rp;
-        if (need * 4 > workspace_bytes) {
-            set_error("d4_muon_plan_create: matrix %d (%d x %d) needs %zu bytes of work buffers, workspace_bytes is %zu", i, d.r, d.c, need * 4, workspace_bytes);
-            return fail();
-        }
-        if (cur.count > 0 && (cur.work_floats + need) * 4 > workspace_bytes) { close(); cur = d4_muon_plan::Pass{i, 0, 0, 0, 0, 0, 0, 0, 0}; }
-        size_t at = cur.work_floats;
-        d.x0 = (int64_t)at; at += (size_t)d.Rp * d.Cp;
-        d.x1 = (int64_t)at; at += (size_t)d.Rp * d.Cp;
-        d.a = (int64_t)at; at += (size_t)d.Rp * d.Rp;
-        d.b = (int64_t)at; at += (size_t)d.Rp * d.Rp;
-        cur.work_floats = at; cur.count++;
-        for (int sidx = 0; sidx < d.nparts; ++sidx) prep.push_back(make_int2(i, sidx));
-        const int tm = d.Rp / MU_T, tn = d.Cp / MU_T;
-        for (int y = 0; y < tm; ++y)
-            for (int x = y; x < tm; ++x) sym.push_back(make_int4(i, y, x, 0));
-        for (int y = 0; y < tm; ++y)
-            for (int x = 0; x < tn; ++x) full.push_back(make_int4(i, y, x, 0));
-    }
-    close();
-    pl->part_floats = (size_t)part;
-    // device tables
-    size_t bytes = (sizeof(MuonMat) * (size_t)n + 15) & ~(size_t)15;
-    for (size_t k = 0; k < built.size(); ++k) {
-        auto& ps = pl->passes[k];
-        ps.prep_off = bytes; bytes += (built[k].prep.size() * sizeof(int2) + 15) & ~(size_t)15;
-        ps.sym_off = bytes; bytes += built[k].sym.size() * sizeof(int4);
-        ps.full_off = bytes; bytes += built[k].full.size() * sizeof(int4);
-    }
-    std::vector<char> host(bytes, 0);
-    for (size_t k = 0; k < built.size(); ++k) {
-        const auto& ps = pl->passes[k];
-        memcpy(host.data() + ps.prep_off, built[k].prep.data(), built[k].prep.size() * sizeof(int2));
-        memcpy(host.data() + ps.sym_off, built[k].sym.data(), built[k].sym.size() * sizeof(int4));
-        memcpy(host.data() + ps.full_off, built[k].full.data(), built[k].full.size() * sizeof(int4));
-    }
-    hipError_t e = hipMalloc((void**)&pl->tables, bytes);
-    if (e == hipSuccess) e = hipMemcpy(pl->tables, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (pl->tables) (void)hipFree(pl->tables);
-        delete pl;
-        return hip_fail(e, "d4_muon_plan_create: device tile table");
-    }
-    *out = pl;
-    return 0;
+    return d4::muon_plan_build("d4_muon_plan_create", n, rows, cols, workspace_bytes, 0, out);
 }
+
+int d4_muon_plan_create_products(int n, const int32_t* rows, const int32_t* cols, size_t workspace_bytes, int products, d4_muon_plan** out) {
+    return d4::muon_plan_build("d4_muon_plan_create_products", n, rows, cols, workspace_bytes, products, out);
+}
+
+int d4_muon_plan_products(const d4_muon_plan* plan) { return plan ? plan->products : 0; }
 
 void d4_muon_plan_destroy(d4_muon_plan* plan) {
     if (!plan) return;

@@ -3,6 +3,7 @@
 Muon (momentum, Nesterov, five Newton-Schulz iterations, scaled update, decoupled weight decay) on the 2-D trunk weights a model names with
 `muon_parameters()`, Adam-atan2 on everything else.  Both groups step on the kernels of csrc/muon.hip: the whole Muon group in
 passes * (2 + 3 * muon_steps) launches whatever the depth, the Adam-atan2 group and the gradient norm as multi-tensor kernels.
+`muon_products='bf16'` (opt-in) takes the Newton-Schulz products from csrc/muon_bf16.hip, one more launch per pass.
 
 `adam_atan2_pytorch` is third-party and absent here, so the contract is the arithmetic written in the class docstring, pinned in float64 by
 tests/muon_ref.py.  Two things differ between published Muon variants and are constructor arguments: the momentum form (`muon_nesterov`) and the
@@ -17,6 +18,7 @@ import torch
 from dreamer4_amd import _lib
 
 UPDATE_SCALES = ('spectral', 'match_rms_adam', 'none')
+PRODUCTS = {'fp32': 0, 'bf16': 1}             # muon_products -> the plan's `products` (d4_muon_plan_create_products)
 
 
 def update_scale(kind, rows, cols):
@@ -31,9 +33,12 @@ def _ptr_array(ptrs):
     return (C.c_void_p * len(ptrs))(*ptrs)
 
 
-def newton_schulz(matrices, steps=5, coefs=(3.4445, -4.7750, 2.0315), eps=1e-7, workspace_bytes=256 << 20):
+def newton_schulz(matrices, steps=5, coefs=(3.4445, -4.7750, 2.0315), eps=1e-7, workspace_bytes=256 << 20, products='fp32'):
     """The Newton-Schulz iteration of the Muon step alone (d4_newton_schulz: the optimiser's own launchers) on a list of 2-D fp32 HIP tensors:
-    X = u / max(|u|_F, eps) oriented rows <= cols, `steps` times A = X X^T, B = b A + c A A, X <- a X + B X.  -> (outputs, passes)."""
+    X = u / max(|u|_F, eps) oriented rows <= cols, `steps` times A = X X^T, B = b A + c A A, X <- a X + B X.  -> (outputs, passes).
+    products='bf16': the products on the bf16 matrix pipe, under the contract of MuonAdamAtan2's `muon_products`."""
+    if products not in PRODUCTS:
+        raise ValueError(f'products must be one of {tuple(PRODUCTS)}, not {products!r}')
     lib = _lib.load()
     matrices = list(matrices)
     for u in matrices:
@@ -45,7 +50,7 @@ def newton_schulz(matrices, steps=5, coefs=(3.4445, -4.7750, 2.0315), eps=1e-7, 
     rows = (C.c_int32 * len(matrices))(*[u.shape[0] for u in matrices])
     cols = (C.c_int32 * len(matrices))(*[u.shape[1] for u in matrices])
     plan = C.c_void_p()
-    _lib.check(lib.d4_muon_plan_create(len(matrices), rows, cols, int(workspace_bytes), C.byref(plan)))
+    _lib.check(lib.d4_muon_plan_create_products(len(matrices), rows, cols, int(workspace_bytes), PRODUCTS[products], C.byref(plan)))
     try:
         with torch.cuda.device(device):
             ws = torch.empty(lib.d4_muon_plan_workspace_bytes(plan), dtype=torch.uint8, device=device)
@@ -82,7 +87,7 @@ class _Table:
 class MuonAdamAtan2(torch.optim.Optimizer):
     """MuonAdamAtan2(muon_params, params, lr=1e-4, muon_lr=None, betas=(0.9, 0.99), weight_decay=0., a=1.27, b=1., muon_beta=0.95, muon_steps=5,
     muon_coefs=(3.4445, -4.7750, 2.0315), muon_eps=1e-7, muon_nesterov=True, muon_update_scale='spectral', remove_muon_params_from_params=True,
-    *, max_grad_norm=None, workspace_bytes=256 << 20)
+    *, max_grad_norm=None, workspace_bytes=256 << 20, muon_products='fp32')
 
     Muon group: every tensor of `muon_params` (2-D).  Per W [r][c] with gradient g:
         m <- lerp(m, g, 1 - muon_beta);  u = lerp(g, m, muon_beta) if muon_nesterov else m;  transposed if r > c;
@@ -98,6 +103,18 @@ class MuonAdamAtan2(torch.optim.Optimizer):
     stands wherever g appears above; `.grad` itself is left untouched.
     `workspace_bytes` bounds the work buffers of one Muon pass (X, X', A, B per matrix): a group that needs more runs in several passes, with the
     same bits; one matrix that does not fit alone is an error that names it.
+    `muon_products='bf16'` (opt-in; anything but 'fp32' / 'bf16' raises ValueError) runs the Newton-Schulz products on the bf16 matrix pipe
+    (csrc/muon_bf16.hip).  Per matrix, oriented rows <= cols:
+        m, u and the strip partials of sum u^2 are the unchanged fp32 arithmetic: `exp_avg` holds the same bits in both modes;
+        X0 = bf16(u * 1 / max(|u|_F, muon_eps)): scaled in fp32 with the scale formed as above, rounded once (nearest even) after normalising,
+             in one extra launch per pass;
+        muon_steps times  A = bf16(X X^T),  B = bf16(b A + c (A A)),  X <- bf16(a X + B X):  every product takes bf16 operands with fp32
+             accumulation in a fixed k order, its alpha E + beta acc epilogue is fp32 on the widened bf16 E and is rounded once on the store;
+        every work buffer is bf16 (the workspace is not larger than the fp32 form's); X X^T is symmetric bit for bit, so the two symmetric
+             stages still compute upper tiles only, and A A is computed as A A^T;
+        finish reads the bf16 X and does the unchanged fp32 update of W.
+    Equal inputs and state give equal bits, whatever the pass partition.  The mode is an attribute like `max_grad_norm`, not in `param_groups`:
+    a state_dict written in one mode loads in the other (the state is the same fp32 `exp_avg`).
 
     Parameters whose `.grad` is None are skipped.  fp32, contiguous, HIP device only: CPU tensors raise D4Error (no CPU fallback).  State per
     parameter: `exp_avg`, `exp_avg_sq` (Adam-atan2 group) and `step`; state_dict() / load_state_dict() are torch.optim.Optimizer's own.
@@ -106,7 +123,7 @@ class MuonAdamAtan2(torch.optim.Optimizer):
 
     def __init__(self, muon_params, params, lr=1e-4, muon_lr=None, betas=(0.9, 0.99), weight_decay=0., a=1.27, b=1., muon_beta=0.95, muon_steps=5,
                  muon_coefs=(3.4445, -4.7750, 2.0315), muon_eps=1e-7, muon_nesterov=True, muon_update_scale='spectral',
-                 remove_muon_params_from_params=True, *, max_grad_norm=None, workspace_bytes=256 << 20):
+                 remove_muon_params_from_params=True, *, max_grad_norm=None, workspace_bytes=256 << 20, muon_products='fp32'):
         if muon_update_scale not in UPDATE_SCALES:
             raise ValueError(f'muon_update_scale must be one of {UPDATE_SCALES}, not {muon_update_scale!r}')
         if not lr > 0. or (muon_lr is not None and not muon_lr > 0.):
@@ -117,6 +134,8 @@ class MuonAdamAtan2(torch.optim.Optimizer):
             raise ValueError('muon_steps must be an integer in 1 .. 64')
         if len(muon_coefs) != 3:
             raise ValueError('muon_coefs is the triple (a, b, c) of the Newton-Schulz polynomial')
+        if muon_products not in PRODUCTS:
+            raise ValueError(f'muon_products must be one of {tuple(PRODUCTS)}, not {muon_products!r}')
         if max_grad_norm is not None and not max_grad_norm > 0.:
             raise ValueError('max_grad_norm must be positive (None: no clipping)')
         muon_params, params = list(muon_params), list(params)
@@ -139,6 +158,7 @@ class MuonAdamAtan2(torch.optim.Optimizer):
         super().__init__(groups, defaults)
         self.max_grad_norm = max_grad_norm
         self.workspace_bytes = int(workspace_bytes)
+        self.muon_products = muon_products
         self._plans = {}                    # (device, shapes) -> (plan handle, workspace tensor)
         self._norm_table = _Table()
         self._adam_tables = {}              # (group index, step) order slot -> _Table
@@ -172,7 +192,7 @@ class MuonAdamAtan2(torch.optim.Optimizer):
             rows = (C.c_int32 * len(shapes))(*[s[0] for s in shapes])
             cols = (C.c_int32 * len(shapes))(*[s[1] for s in shapes])
             plan = C.c_void_p()
-            _lib.check(lib.d4_muon_plan_create(len(shapes), rows, cols, self.workspace_bytes, C.byref(plan)))
+            _lib.check(lib.d4_muon_plan_create_products(len(shapes), rows, cols, self.workspace_bytes, PRODUCTS[self.muon_products], C.byref(plan)))
             ws = torch.empty(lib.d4_muon_plan_workspace_bytes(plan), dtype=torch.uint8, device=device)
             hit = self._plans[key] = (plan, ws)
         return hit
@@ -233,7 +253,7 @@ class MuonAdamAtan2(torch.optim.Optimizer):
                                                 _ptr_array([self.state[p]['exp_avg'].data_ptr() for p in ps]), scales, C.c_void_p(ws.data_ptr()), ws.numel(),
                                                 lr, group['weight_decay'], group['muon_beta'], int(group['muon_nesterov']), group['muon_steps'],
                                                 ca, cb, cc, group['muon_eps'], norm, max_norm, stream))
-                    launches += lib.d4_muon_plan_passes(plan) * (2 + 3 * group['muon_steps'])
+                    launches += lib.d4_muon_plan_passes(plan) * (2 + lib.d4_muon_plan_products(plan) + 3 * group['muon_steps'])     # bf16: + normalise
                     continue
                 by_step = {}
                 for p in ps:

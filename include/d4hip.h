@@ -928,9 +928,18 @@ int d4_pack_tokens_bf16(int which, float* tokens, uint16_t* tokens_b, float* com
  *                         d4_sumsq_multi       out[0] = sum over all tensors of x^2 (per-4096-element partials, then one block).
  *                         d4_adam_atan2_multi  m <- lerp(m, g, 1 - beta1); v <- lerp(v, g^2, 1 - beta2);
  *                                              W <- W (1 - lr wd) - lr a atan2(m / (1 - beta1^step), b sqrt(v / (1 - beta2^step)))
- *                                              with g clipped as in d4_muon_step.  One launch. */
+ *                                              with g clipped as in d4_muon_step.  One launch.
+ *   d4_muon_plan_create_products   the plan with its product form chosen.  products 0: exactly d4_muon_plan_create.  products 1: the
+ *                       Newton-Schulz products on the bf16 matrix pipe (csrc/muon_bf16.hip): prepare and finish stay fp32 (the momentum holds the
+ *                       same bits), X0 = bf16(u / max(|u|_F, eps)) is rounded once after the fp32 scaling, every product takes bf16 operands with
+ *                       fp32 accumulation and rounds its fp32 epilogue once; all work buffers are bf16 and the workspace is not larger than the
+ *                       fp32 plan's.  Launches per call: passes * (3 + 3 * steps).  Any other value is refused.  The mode belongs to the plan:
+ *                       d4_muon_step, d4_newton_schulz, d4_muon_plan_workspace_bytes and d4_muon_plan_passes follow it.
+ *   d4_muon_plan_products          the plan's product form (0 or 1). */
 typedef struct d4_muon_plan d4_muon_plan;
 int d4_muon_plan_create(int n, const int32_t* rows, const int32_t* cols, size_t workspace_bytes, d4_muon_plan** out);
+int d4_muon_plan_create_products(int n, const int32_t* rows, const int32_t* cols, size_t workspace_bytes, int products, d4_muon_plan** out);
+int d4_muon_plan_products(const d4_muon_plan* plan);
 void d4_muon_plan_destroy(d4_muon_plan* plan);
 size_t d4_muon_plan_workspace_bytes(const d4_muon_plan* plan);
 int d4_muon_plan_passes(const d4_muon_plan* plan);
