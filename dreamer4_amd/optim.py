@@ -29,6 +29,15 @@ def update_scale(kind, rows, cols):
     return 1.
 
 
+def mark_mutated(tensors):
+    """Tell autograd's version counters that `tensors` were written.  The kernels of this package write parameters through raw pointers, which no
+    counter sees; the engines of DynamicsWorldModel and VideoTokenizer decide from `Tensor._version` when to rebuild the images they keep of the
+    trunk weights, and autograd itself uses it to refuse a backward over a tensor saved before the write.  Host only: no launch,
+    no synchronisation; views share their base's counter."""
+    for t in tensors:
+        torch.autograd.graph.increment_version(t)
+
+
 def _ptr_array(ptrs):
     return (C.c_void_p * len(ptrs))(*ptrs)
 
@@ -268,5 +277,6 @@ class MuonAdamAtan2(torch.optim.Optimizer):
                     _lib.check(lib.d4_adam_atan2_multi(len(tp), numel, *[_ptr_array(x) for x in ptrs], C.c_void_p(table.data_ptr()), table.numel(), upload, t,
                                                        group['lr'], b1, b2, group['weight_decay'], group['a'], group['b'], norm, max_norm, stream))
                     launches += 1
+        mark_mutated(flat)
         self.last_launches = launches
         return loss

@@ -281,6 +281,10 @@ class VideoTokenizer(SaveLoad, nn.Module):
         return st['engine']
 
     def invalidate_prepared(self):
+        """Force both engines' weight images to be rebuilt on the next `decode` / `tokenize`.  Needed only after a write autograd's version
+        counter cannot see (`p.data.copy_(...)`, `dist.broadcast(p.data)`, a third party's raw pointer).  Every call looks at the parameters
+        the module holds then, so in-place updates, torch optimisers, MuonAdamAtan2 (it marks what it stepped as mutated), `load_state_dict`
+        copying or with `assign=True` and replaced Parameter objects are detected with no call."""
         for st in self._engines.values():
             st['prep_version'] = None
 

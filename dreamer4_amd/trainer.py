@@ -15,6 +15,7 @@ import torch
 
 from dreamer4_amd import _lib, parallel
 from dreamer4_amd.learner import run_learner
+from dreamer4_amd.optim import mark_mutated
 
 
 class DreamTrainer:
@@ -72,6 +73,7 @@ class DreamTrainer:
                                      self.betas[1], self.adam_eps, self.weight_decay,
                                      self.max_grad_norm if self.max_grad_norm is not None else 0., grad_scale,
                                      P(st['scratch']), m._stream()))
+        mark_mutated((g['flat'], *g['params']))          # the kernel wrote through raw pointers: every writer of this package is visible
         return st['scratch'][0]
 
     def generate(self):

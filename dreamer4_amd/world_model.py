@@ -131,6 +131,47 @@ _NOT_BOUND = {'zero', 'ema_returns_mean', 'ema_returns_var', 'reward_loss_weight
 _LOSS_NORMALIZERS = ('flow_loss_normalizer', 'shortcut_flow_loss_normalizer', 'reward_loss_normalizer', 'state_terminal_loss_normalizer',
                      'discrete_actions_loss_normalizer', 'continuous_actions_loss_normalizer')
 
+
+def engine_slots(model):
+    """The places the dynamics engine's tensors live in, read off the module tree as it is NOW: a list of (holder dict, key, object, name, head).
+    One entry per submodule on the way (name None: `parent._modules[key]`) and one per bound parameter or buffer (`owner._parameters[key]` /
+    `owner._buffers[key]`, name = its state_dict key, head = it is a parameter of the policy or the value head).  A swapped Parameter object, a
+    `load_state_dict(assign=True)` or a replaced submodule puts another object into one of these places.  The nested tokenizer owns its
+    engines and is left out."""
+    out = []
+    heads = {id(p) for p in (*model.policy_head_parameters(), *model.value_head_parameters())}
+
+    def walk(mod, prefix):             # (named_parameters() + named_buffers() by hand, with the places they were found in)
+        for holder in (mod._parameters, mod._buffers):
+            for n, t in holder.items():
+                if t is not None and not (prefix == '' and n in _NOT_BOUND):
+                    out.append((holder, n, t, prefix + n, id(t) in heads))
+        for n, child in mod._modules.items():
+            if child is not None and not (prefix == '' and n in _LOSS_NORMALIZERS + ('video_tokenizer',)):
+                out.append((mod._modules, n, child, None, False))
+                walk(child, prefix + n + '.')
+
+    walk(model, '')
+    return out
+
+
+def engine_tensors(model, slots=None):
+    """name -> tensor for everything the dynamics engine binds"""
+    return {name: t for _, _, t, name, _ in (engine_slots(model) if slots is None else slots) if name is not None}
+
+
+def bind_signature(model, slots=None):
+    """What `DynamicsWorldModel._bind` compares to decide whether the engine has to rebind or re-prepare: per bound tensor its name, object
+    identity, address, size and — for the trunk, whose weights the engine keeps derived images of — autograd's version counter.  The two heads
+    are read through their pointers on every call, so a write to them needs no re-preparation: their version is left out (-1).  Host only:
+    no device is touched, a CPU model answers too (tests/test_coherence_host.py).  `slots` is an earlier `engine_slots(model)`: while every
+    place still holds the object it held then (dictionary look-ups), the tree is not walked again; the answer is the same either way.
+    Identities mean something only while the tensors of the look one compares with are alive (`_bind` keeps them)."""
+    if slots is None or any(holder.get(key) is not obj for holder, key, obj, _, _ in slots):
+        slots = engine_slots(model)
+    return tuple((name, id(t), t.data_ptr(), t.numel(), -1 if head else t._version) for _, _, t, name, head in slots if name is not None)
+
+
 _UNSUPPORTED_DEFAULTS = dict(
     aux_image_encoder=None, num_agents=1, num_video_views=1, mot_temporal=False,
     dim_proprio=None, dim_state=None, dim_critic_state=None, critic_state_embedder=None,
@@ -365,17 +406,40 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
 
         self._build_parameters()
 
-        # engine state (created lazily on the parameters' device)
-        self._engine = None
-        self._engine_caps = None
-        self._ws = None
-        self._bound_sig = None
-        self._trunk_version = None
-        self._cache_serial = 0
-        self._live_cache = None
-        self._slot_serial = []           # per KV-ring slot: serial of the call that last wrote it
-        self._engine_generation = 0      # bumped whenever the engine (and with it the ring) is rebuilt
-        self._groups = {}
+        self.__dict__.update(self._no_engine_state())
+
+    @staticmethod
+    def _no_engine_state():
+        """The per-instance engine state of a model that has none yet (created lazily on the parameters' device): what the constructor
+        sets and what a deep copy starts from."""
+        return dict(_engine=None, _engine_caps=None, _ws=None, _ws_off=0,
+                    _bind_cache=None,          # (bind_signature, engine_slots) of the last bind
+                    _cache_serial=0, _live_cache=None,
+                    _slot_serial=[],           # per KV-ring slot: serial of the call that last wrote it
+                    _engine_generation=0,      # bumped whenever the engine (and with it the ring) is rebuilt
+                    _groups={},
+                    _coin_generator=None)      # (_shortcut_coin's companion of a caller's generator OBJECT: it restarts for another object anyway)
+
+    def __deepcopy__(self, memo):
+        # the engine handle, its workspace, the bind cache, the flat head groups and the time-cache book are per-instance device state: a copy
+        # starts without any and builds its own on first use (VideoTokenizer.__deepcopy__ does the same); its head parameters own their memory
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        fresh = self._no_engine_state()
+        for k, v in self.__dict__.items():
+            if k not in fresh:
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        new.__dict__.update(fresh)
+        return new
+
+    def __del__(self):
+        try:
+            if self._engine is not None:
+                _lib.load().d4_engine_destroy(self._engine)
+                self._engine = None
+        except Exception:
+            pass
 
     # ------------------------------------------------------------------------------ parameters
     def _build_parameters(self):
@@ -617,6 +681,7 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             caps = (max(batch, old[0]), max(frames, old[1]), max(parallel, old[2]), max(learn_rows, old[3]))
             if self._engine is not None:
                 lib.d4_engine_destroy(self._engine)
+                self._engine, self._engine_caps = None, None        # (a failed create below must not leave a dead handle for __del__)
             eng = C.c_void_p()
             cfg = self._make_config(caps)
             _lib.check(lib.d4_engine_create(C.byref(cfg), C.byref(eng)))
@@ -628,8 +693,6 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             base = self._ws.data_ptr()
             self._ws_off = (-base) % 256
             _lib.check(lib.d4_engine_set_workspace(eng, C.c_void_p(base + self._ws_off), nbytes))
-            self._bound_sig = None
-            self._trunk_version = None
             self._bind_cache = None
             if keep is not None:
                 tc, kv = keep
@@ -669,12 +732,11 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
 
     def _bind(self):
         lib = _lib.load()
-        # fast path (every call): nothing moved and no trunk weight was written since the last bind/prepare
-        cached = getattr(self, '_bind_cache', None)
-        if cached is not None and self._bound_sig is not None:
-            tensors, trunk = cached
-            if all(t.data_ptr() == p for t, p in tensors) and tuple(t._version for t in trunk) == self._trunk_version:
-                return
+        # fast path (every call, host only): the module holds the tensor objects of the last bind, none of them moved and no trunk weight was
+        # written since the last prepare.  The question is asked of what the module holds NOW, not of the objects seen last time
+        last = self._bind_cache               # (signature, slots) of the last bind; None: nothing is bound
+        if last is not None and last[0] == bind_signature(self, last[1]):
+            return
         groups = dict(policy=self._flatten_group('policy', self.policy_head_parameters()),
                       value=self._flatten_group('value', self.value_head_parameters()))
         grads = {}
@@ -683,25 +745,21 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
             for p in g['params']:
                 grads[id(p)] = g['grad'][off:off + p.numel()]
                 off += p.numel()
-        tensors = {k: v for k, v in self.named_parameters() if not k.startswith('video_tokenizer.')}
-        tensors.update({k: v for k, v in self.named_buffers() if k not in _NOT_BOUND and not k.startswith(_LOSS_NORMALIZERS + ('video_tokenizer.',))})
-        sig = tuple((k, t.data_ptr(), t.numel()) for k, t in tensors.items())
-        if sig != self._bound_sig:
-            for k, t in tensors.items():
+        slots = engine_slots(self)
+        sig = bind_signature(self, slots)     # (after the flattening, which moves head parameters)
+        where = lambda s: [entry[:4] for entry in s]
+        if last is None or where(last[0]) != where(sig):
+            # an object or an address is another one: bind again, which also drops the captured graphs (they bake addresses)
+            for k, t in engine_tensors(self, slots).items():
                 if t.numel() == 0:
                     continue
                 assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device, k
                 gr = grads.get(id(t))
                 _lib.check(lib.d4_engine_bind(self._engine, k.encode(), _lib.ptr(t), _lib.ptr(gr), t.numel()))
-            self._bound_sig = sig
-            self._trunk_version = None
-        head_ids = {id(p) for g in groups.values() for p in g['params']}
-        trunk = [t for t in tensors.values() if id(t) not in head_ids]
-        ver = tuple(t._version for t in trunk)
-        if ver != self._trunk_version:
-            _lib.check(lib.d4_engine_prepare(self._engine, self._stream()))
-            self._trunk_version = ver
-        self._bind_cache = ([(t, t.data_ptr()) for t in tensors.values()], trunk)
+        # whatever made the signature differ — a binding, a trunk version, invalidate_prepared() — the images are made again
+        _lib.check(lib.d4_engine_prepare(self._engine, self._stream()))
+        # (the slots keep the tensors alive with the signature: while they live, no other object can take their identity or their memory)
+        self._bind_cache = (sig, slots)
 
     def _mark_slots(self, lo, hi, serial):
         if hi > len(self._slot_serial):
@@ -750,9 +808,14 @@ class DynamicsWorldModel(SaveLoad, nn.Module):
 
     def invalidate_prepared(self):
         """Force the fused / gamma-folded weight images to be rebuilt on the next call.  Needed only after writing a trunk weight
-        in a way autograd's version counter cannot see (`p.data.copy_(...)`, `dist.broadcast(p.data)`, raw pointers); ordinary
-        in-place updates (`p.copy_()` under no_grad, optimiser steps, `load_state_dict`) are detected automatically."""
-        self._trunk_version = None
+        in a way autograd's version counter cannot see: `p.data.copy_(...)`, `dist.broadcast(p.data)`, a third party's kernel that
+        writes through a raw pointer.  Detected automatically, with no call: in-place updates (`p.copy_()` / `p.mul_()` under no_grad),
+        torch optimisers, this package's MuonAdamAtan2 and DreamTrainer steps (they write through raw pointers and mark the tensors
+        they wrote as mutated), `load_state_dict` copying or with `assign=True`, replaced Parameter objects and `.to()` / `.cpu().cuda()`
+        (DESIGN.md 31)."""
+        if self._bind_cache is not None:          # forget the versions, keep the bindings: the next call prepares again and keeps its graphs
+            sig, slots = self._bind_cache
+            self._bind_cache = (tuple(entry[:4] + (None,) for entry in sig), slots)
 
     # ------------------------------------------------------------------------------ forward (inference branch / training branch)
     def forward(self, *, latents, signal_levels=None, step_sizes=None, discrete_actions=None, continuous_actions=None, tasks=None, time_cache=None,
