@@ -283,6 +283,10 @@ SYMBOLS = {
     'd4_mask_rows_fwd': (_I, [_P] * 4 + [_I, _I, _P]),
     'd4_mask_rows_bwd': (_I, [_P] * 5 + [C.c_size_t, _I, _I, _P]),
     'd4_recon_loss_fwd_bwd': (_I, [_P] * 4 + [_I] * 7 + [_P, _P, _P, C.c_size_t, _P]),
+    'd4_sigreg_part_floats': (C.c_size_t, [_I] * 4),
+    'd4_sigreg_fwd_bwd': (_I, [_P, _P] + [_I] * 4 + [_F, _F, _I, _P, _P, _P, C.c_size_t, _P]),
+    'd4_latent_ortho_part_floats': (C.c_size_t, [_I]),
+    'd4_latent_ortho_fwd_bwd': (_I, [_P] + [_I] * 3 + [_P, _P, _P, C.c_size_t, _P]),
     'd4_pack_tokens_bf16': (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'd4_muon_plan_create': (_I, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(_P)]),
     'd4_muon_plan_create_products': (_I, [_I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, _I, C.POINTER(_P)]),

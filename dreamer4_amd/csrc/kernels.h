@@ -418,5 +418,15 @@ int mask_rows_fwd(const float* x, const uint8_t* mask, const float* token, float
 int mask_rows_bwd(const float* dy, const uint8_t* mask, float* dx, float* dtoken, float* part, int rows, int dim, hipStream_t s);
 int recon_loss_fwd_bwd(const float* recon, const float* video, const float* noise, const float* t, int B, int C, int T, int nh, int nw, int ps, int v_space,
                        float* loss, float* d_rows, float* part, hipStream_t s);
+// latent regularisers of the tokenizer's training forward (tok_reg.hip): loss and d loss / d x in one call; every sum that crosses a
+// workgroup goes through partials in `part` and a fixed-order second pass (no float atomics)
+static constexpr int SIGREG_ROWS = 64;                 // rows of x per block: the partial sums of the characteristic function are per (k, block of rows)
+static constexpr int SIGREG_SLICES = 64;               // slices per block (one per lane)
+static constexpr int SIGREG_MAX_DIM = 128, SIGREG_MAX_KNOTS = 64, SIGREG_MAX_SLICES = 4096;
+static constexpr int ORTHO_MAX_ROWS = 1024, ORTHO_MAX_DIM = 128;
+size_t sigreg_part_floats(int K, int N, int M, int knots);
+int sigreg_fwd_bwd(const float* x, const float* projs, int K, int N, int d, int M, float lo, float hi, int knots, float* loss, float* dx, float* part,
+                   hipStream_t s);
+int latent_ortho_fwd_bwd(const float* x, int F, int n, int d, float* loss, float* dx, float* part, hipStream_t s);
 
 }  // namespace d4

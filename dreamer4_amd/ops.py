@@ -9,6 +9,8 @@ current stream.  There is no CPU implementation: on a CPU tensor they raise (the
     ret = torch.ops.d4hip.gae(rewards, values, lens, is_truncated, terminals, gamma, lam)     calc_gae + masks  D4:1566-1600, 5943-5971
     torch.ops.d4hip.{video_to_patches, patches_to_video, flow_noised_patches, layernorm_nobias, mask_rows, recon_loss}
                                                                         the pixel side of VideoTokenizer.forward  (csrc/tok_train.hip)
+    loss, dx = torch.ops.d4hip.sigreg(x, projs, lo, hi, num_knots)      sigreg, forward + backward fused    (d4_sigreg_fwd_bwd)
+    loss, dx = torch.ops.d4hip.latent_ortho(x)                          orthogonal_loss, the same           (d4_latent_ortho_fwd_bwd)
 
 The stateful calls (rollout, learner) keep their engine handle and therefore stay methods of DynamicsWorldModel."""
 from __future__ import annotations
@@ -852,6 +854,81 @@ def _recon_bwd(ctx, d_loss, _d_rows):
 
 
 recon_loss.register_autograd(_recon_bwd, setup_context=_recon_setup)
+
+
+# ------------------------------------------------------------------------------------------------ tokenizer training forward, latent regularisers
+# sigreg (D4:728-767) and orthogonal_loss (D4:389-402) as fused forward + backward operators (csrc/tok_reg.hip): each returns
+# (loss, d loss / d x) and is differentiable in x through the second output, like recon_loss.
+SIGREG_DOMAIN, SIGREG_KNOTS = (-5., 5.), 17                # the defaults of the reference's sigreg
+
+
+def sigreg_impl(x, projs, lo, hi, num_knots):
+    """sigreg(x) without a mask on x (k, ..., d): the axes between the first and the last are the samples of the characteristic function.  `projs`
+    (num_slices, d) is the RAW normal draw (normalised inside, F.normalize).  Knots linspace(lo, hi, num_knots).  Returns (loss, d loss / d x)."""
+    _need_gpu(x, projs)
+    x, projs = _f32c(x, projs)
+    assert x.ndim >= 2 and projs.ndim == 2 and projs.shape[1] == x.shape[-1], 'x (k, ..., d) and projs (num_slices, d)'
+    K, d, M = x.shape[0], x.shape[-1], projs.shape[0]
+    N = x.numel() // max(K * d, 1)
+    lib = _lib.load()
+    n = lib.d4_sigreg_part_floats(K, N, M, num_knots)
+    loss, dx, part = x.new_empty(1), torch.empty_like(x), x.new_empty(max(n, 1))
+    _lib.check(lib.d4_sigreg_fwd_bwd(_lib.ptr(x), _lib.ptr(projs), K, N, d, M, lo, hi, num_knots, _lib.ptr(loss), _lib.ptr(dx), _lib.ptr(part), n, _stream(x)))
+    return loss.view(()), dx
+
+
+@custom_op('d4hip::sigreg', mutates_args=())
+def sigreg(x: torch.Tensor, projs: torch.Tensor, lo: float, hi: float, num_knots: int) -> tuple[torch.Tensor, torch.Tensor]:
+    return sigreg_impl(x, projs, lo, hi, num_knots)
+
+
+@sigreg.register_fake
+def _(x, projs, lo, hi, num_knots):
+    return x.new_empty((), dtype=torch.float32), torch.empty_like(x, dtype=torch.float32)
+
+
+def _loss_dx_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _sigreg_bwd(ctx, d_loss, _dx):
+    (dx,) = ctx.saved_tensors
+    return dx * d_loss, None, None, None, None
+
+
+sigreg.register_autograd(_sigreg_bwd, setup_context=_loss_dx_setup)
+
+
+def latent_ortho_impl(x):
+    """orthogonal_loss(x) on x (..., n, d): per frame centre over n, normalise the rows, sum of the squared off-diagonal Gram entries; mean over the
+    frames.  Returns (loss, d loss / d x); n = 1 gives exactly 0 and a zero gradient."""
+    _need_gpu(x)
+    (x,) = _f32c(x)
+    assert x.ndim >= 2, 'x (..., n, d)'
+    n, d = x.shape[-2:]
+    F = x.numel() // max(n * d, 1)
+    lib = _lib.load()
+    loss, dx, part = x.new_empty(1), torch.empty_like(x), x.new_empty(max(lib.d4_latent_ortho_part_floats(F), 1))
+    _lib.check(lib.d4_latent_ortho_fwd_bwd(_lib.ptr(x), F, n, d, _lib.ptr(loss), _lib.ptr(dx), _lib.ptr(part), part.numel(), _stream(x)))
+    return loss.view(()), dx
+
+
+@custom_op('d4hip::latent_ortho', mutates_args=())
+def latent_ortho(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    return latent_ortho_impl(x)
+
+
+@latent_ortho.register_fake
+def _(x):
+    return x.new_empty((), dtype=torch.float32), torch.empty_like(x, dtype=torch.float32)
+
+
+def _ortho_bwd(ctx, d_loss, _dx):
+    (dx,) = ctx.saved_tensors
+    return dx * d_loss
+
+
+latent_ortho.register_autograd(_ortho_bwd, setup_context=_loss_dx_setup)
 
 
 def attn_pool(x: torch.Tensor, hiddens: torch.Tensor, norm_w: torch.Tensor, norm_ctx_w: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor,

@@ -14,8 +14,11 @@ MOSS, aug conditioning, PoPE, separate flow decoder, BYOL.
 `forward(video_or_image, ...)` is the training forward (dreamer4.py:4239-4603) for the same subset: MAE masking, encoder, tanh bottleneck,
 one flow-decoder step at a drawn time, the v-space or x-space reconstruction loss with the reference's loss normalisation, autograd to
 every parameter the loss reaches.  It runs `trunk_ops.tokenizer_losses`: both trunks on the differentiable HIP blocks, the passes over
-pixels on the operators of csrc/tok_train.hip.  LPIPS (no VGG weights), the auxiliary losses, `time_lens`, time caches,
-aug conditioning and BYOL are outside the subset and raise."""
+pixels on the operators of csrc/tok_train.hip.  Three latent regularisers are optional terms of it, each behind the reference's
+weight argument (default 0.: nothing changes): SIGReg of the latents before the tanh, the orthogonality loss of a frame's latent tokens (both fused
+forward + backward operators of csrc/tok_reg.hip) and the latent consistency loss, a second encoder pass on the decoder's output with the encoder
+frozen.  LPIPS (no VGG weights), the decorrelation and latent-autoregression losses, `time_lens`, time caches, aug conditioning
+and BYOL are outside the subset and raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,6 +29,7 @@ from torch import nn
 
 from dreamer4_amd import _lib
 from dreamer4_amd.checkpoint import SaveLoad
+from dreamer4_amd.trunk_ops import ENCODER_KEYS
 from dreamer4_amd.world_model import MLP_RECIPES, _linear_b, _linear_w, _register, mlp_param_specs, mlp_widths, transformer_muon_parameters
 
 TokenizerLosses = namedtuple('TokenizerLosses', ('recon', 'flow_recon', 'lpips', 'time_decorr', 'space_decorr', 'latent_ortho', 'latent_ar', 'latent_ar_sigreg',
@@ -42,13 +46,17 @@ _UNSUPPORTED = dict(
 
 
 _NORMALIZER_KEY = 'recon_loss_normalizer.exp_avg_sq'
+# the latent regularisers: TokenizerLosses field -> the reference's LossNormalizer buffer; the state exists only when the term's weight is > 0
+_REG_NORMALIZER_KEYS = {f: f'{f}_loss_normalizer.exp_avg_sq' for f in ('latent_sigreg', 'latent_ortho', 'latent_consistency')}
+_SIGREG_KWARGS = ('num_slices', 'domain', 'num_knots')
 
 
 class VideoTokenizer(SaveLoad, nn.Module):
     def __init__(self, dim, dim_latent, patch_size, image_size=None, image_height=None, image_width=None, num_latent_tokens=64,
                  encoder_depth=4, decoder_depth=4, time_block_every=4, attn_dim_head=64, attn_heads=8, decoder_pos_mlp_depth=2,
                  channels=3, decoder_flow_steps=1, head_mlp_recipe='pre_rms', wide_frames=False, attn_products='fp32',
-                 train_wide_frames=False, lpips_loss_weight=0.2, decoder_v_space_loss=True, matmul_dtype='fp32', **kwargs):
+                 train_wide_frames=False, lpips_loss_weight=0.2, decoder_v_space_loss=True, matmul_dtype='fp32', latent_sigreg_loss_weight=0.,
+                 latent_sigreg_loss_kwargs=dict(num_slices=256), latent_ortho_loss_weight=0., latent_consistency_loss_weight=0., **kwargs):
         """`wide_frames` is not a reference argument: False (default) the decoder and encoder engines take at most 160 tokens (patches +
         latents) and 64 latent tokens per frame; True up to 1024 of each, on the tiled attention core of csrc/attn_wide_mfma.hip above 64
         items per side, and encoder / decoder trunks of depth >= 32 (up to 1024 pooled layer hiddens, the chunked pool mix of
@@ -65,7 +73,11 @@ class VideoTokenizer(SaveLoad, nn.Module):
         residual stream, the Euler step and the four end projections (patch rows -> tokens and its LayerNorm, latents -> decoder tokens, tokens ->
         patch rows, latent tokens -> latents and the tanh) stay fp32.  Independent of `wide_frames`, `attn_products`,
         `train_wide_frames` and of a world model's own `matmul_dtype`.  The training `forward` stays fp32 whatever the option says.
-        `lpips_loss_weight` and `decoder_v_space_loss` are the reference's; the first is only stored (any value constructs, `forward` needs 0.)."""
+        `lpips_loss_weight` and `decoder_v_space_loss` are the reference's; the first is only stored (any value constructs, `forward` needs 0.).
+        `latent_sigreg_loss_weight`, `latent_sigreg_loss_kwargs` (keys num_slices, domain, num_knots: the arguments of the reference's sigreg),
+        `latent_ortho_loss_weight` and `latent_consistency_loss_weight` are the reference's (dreamer4.py:3995-4052), with its defaults: a weight > 0 adds
+        that term to the training forward and, under loss normalisation, its normaliser state; at 0 nothing changes."""
+        latent_sigreg_loss_kwargs = dict(latent_sigreg_loss_kwargs or {})       # the recorded config holds its own copy, never the shared default
         config = dict(locals())
         super().__init__()
         self._record_config(config)
@@ -94,6 +106,14 @@ class VideoTokenizer(SaveLoad, nn.Module):
         self.lpips_loss_weight, self.decoder_v_space_loss = float(lpips_loss_weight), bool(decoder_v_space_loss)
         self.use_loss_normalization = bool(kwargs.get('use_loss_normalization', True))
         self.per_image_patch_mask_prob = tuple(kwargs.get('per_image_patch_mask_prob', (0., 0.9)))
+        self.latent_sigreg_loss_kwargs = dict(latent_sigreg_loss_kwargs)
+        for k in self.latent_sigreg_loss_kwargs:
+            if k not in _SIGREG_KWARGS:
+                raise NotImplementedError(f'latent_sigreg_loss_kwargs[{k!r}]: the keys are {_SIGREG_KWARGS}')
+        self.loss_weights = dict(latent_sigreg=float(latent_sigreg_loss_weight), latent_ortho=float(latent_ortho_loss_weight),
+                                 latent_consistency=float(latent_consistency_loss_weight))
+        self.latent_sigreg_loss_weight, self.latent_ortho_loss_weight = self.loss_weights['latent_sigreg'], self.loss_weights['latent_ortho']
+        self.latent_consistency_loss_weight = self.loss_weights['latent_consistency']
         if attn_products not in ('fp32', 'bf16'):
             raise ValueError("attn_products must be 'fp32' or 'bf16'")
         if attn_products == 'bf16' and not self.wide_frames:
@@ -175,18 +195,23 @@ class VideoTokenizer(SaveLoad, nn.Module):
         # state_dict stays the parameter set the inference paths load; load_state_dict still takes the key from a reference checkpoint
         if self.use_loss_normalization:
             _register(self, _NORMALIZER_KEY, torch.ones(1), buffer=True, persistent=False)
+            for f, key in _REG_NORMALIZER_KEYS.items():
+                if self.loss_weights[f] > 0.:
+                    _register(self, key, torch.ones(1), buffer=True, persistent=False)
 
     def muon_parameters(self):
         """dreamer4.py:4096-4105: the encoder transformer's and the decoder transformer's Muon parameters (no separate flow decoder in the subset)."""
         return [*transformer_muon_parameters(self.encoder_transformer), *transformer_muon_parameters(self.decoder.transformer)]
 
     def load_state_dict(self, state_dict, strict=True, **kwargs):
-        if _NORMALIZER_KEY in state_dict:
-            state_dict = dict(state_dict)
-            state = state_dict.pop(_NORMALIZER_KEY)
-            if self.use_loss_normalization:
-                with torch.no_grad():
-                    self.recon_loss_normalizer.exp_avg_sq.copy_(torch.as_tensor(state).reshape(1))
+        own = dict(self.named_buffers())
+        for key in (_NORMALIZER_KEY, *_REG_NORMALIZER_KEYS.values()):
+            if key in state_dict:
+                state_dict = dict(state_dict)
+                state = state_dict.pop(key)
+                if key in own:                                         # a term this tokenizer does not train with: the reference's state is dropped
+                    with torch.no_grad():
+                        own[key].copy_(torch.as_tensor(state).reshape(1))
         return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     @property
@@ -196,12 +221,12 @@ class VideoTokenizer(SaveLoad, nn.Module):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    _ENCODER_KEYS = ('latent_tokens', 'patch_to_tokens.', 'encoder_transformer.', 'encoded_to_latents.')
+    _ENCODER_KEYS = ENCODER_KEYS
 
     def _engine_tensors(self, mode):
         out = {}
         for k, v in list(self.named_parameters()) + list(self.named_buffers()):
-            if k in ('zero', 'mask_token', _NORMALIZER_KEY):
+            if k in ('zero', 'mask_token', _NORMALIZER_KEY, *_REG_NORMALIZER_KEYS.values()):
                 continue
             enc = k.startswith(self._ENCODER_KEYS)
             if mode == 2 and enc:
@@ -356,11 +381,11 @@ class VideoTokenizer(SaveLoad, nn.Module):
     def _is_time(self, depth):
         return [((i + 1) % self.time_block_every) == 0 for i in range(depth)]
 
-    def _normalize_recon(self, loss, update_ema, beta=0.95, eps=1e-6):
-        """LossNormalizer.forward (dreamer4.py:645-669), the arithmetic of DynamicsWorldModel._normalize_loss."""
+    def _normalize_loss(self, loss, update_ema, beta=0.95, eps=1e-6, key=_NORMALIZER_KEY):
+        """LossNormalizer.forward (dreamer4.py:645-669), the arithmetic of DynamicsWorldModel._normalize_loss, on the state buffer `key`."""
         if not self.use_loss_normalization:
             return loss
-        buf = self.recon_loss_normalizer.exp_avg_sq
+        buf = self.get_buffer(key)
         rms = buf.sqrt()
         if update_ema:
             with torch.no_grad():
@@ -372,8 +397,9 @@ class VideoTokenizer(SaveLoad, nn.Module):
                 draws=None, generator=None):
         """VideoTokenizer.forward (dreamer4.py:4239-4603) for the supported subset: video (b, c, t, h, w) or images (b, c, h, w) -> total loss, or
         (total, (TokenizerLosses, reconstruction)) with `return_intermediates`, or the latents (with gradient) with `return_latents`.
-        `draws` = dict(patch_mask=, time_indices=, noise=) injects the random draws (parity runs; a missing entry is drawn); otherwise they
-        come from `generator` on the device.  More than 64 tokens per frame need `train_wide_frames=True`.  The training forward is fp32:
+        `draws` = dict(patch_mask=, time_indices=, noise=, sigreg_projs=) injects the random draws (parity runs; a missing entry is drawn); otherwise
+        they come from `generator` on the device.  `sigreg_projs` is the raw (num_slices, dim_latent) normal draw of the SIGReg term, read only when its
+        weight is > 0 (the reference draws it a second time inside the consistency term's nested forward and discards that value: not imitated).  More than 64 tokens per frame need `train_wide_frames=True`.  The training forward is fp32:
         `matmul_dtype='bf16'` changes `decode` and `tokenize` only."""
         from dreamer4_amd import trunk_ops
         for name, val in (('time_lens', time_lens), ('time_cache', time_cache), ('byol_target_latents', byol_target_latents)):
@@ -420,15 +446,34 @@ class VideoTokenizer(SaveLoad, nn.Module):
         if noise is None:
             noise = torch.randn(video.shape, device=dev, generator=generator)
         noise = noise.to(dev).float().reshape(video.shape).contiguous()
-        recon, latents, recon_video = trunk_ops.tokenizer_losses(
-            Wt, video, draws=dict(patch_mask=patch_mask, time_indices=time_indices.to(dev).long(), noise=noise), decoder_is_time=self._is_time(self.decoder_depth),
+        used = {f for f, w in self.loss_weights.items() if w > 0.}
+        reg_kw, tdraws = {}, dict(patch_mask=patch_mask, time_indices=time_indices.to(dev).long(), noise=noise)
+        if 'latent_sigreg' in used:
+            sk = dict(self.latent_sigreg_loss_kwargs)
+            shape = (int(sk.pop('num_slices', 1024)), self.dim_latent)          # sigreg's own default number of slices
+            projs = draws.get('sigreg_projs')
+            if projs is None:
+                projs = torch.randn(shape, device=dev, generator=generator)
+            tdraws['sigreg_projs'] = projs.to(dev).float().reshape(shape).contiguous()
+            reg_kw['sigreg_kwargs'] = sk
+        recon, latents, recon_video, regs = trunk_ops.tokenizer_losses(
+            Wt, video, draws=tdraws, decoder_is_time=self._is_time(self.decoder_depth),
             decoder_flow_steps=self.decoder_flow_steps, decoder_pos_mlp_depth=self.decoder_pos_mlp_depth, head_mlp_recipe=self.head_mlp_recipe,
-            v_space=self.decoder_v_space_loss, return_recon_video=return_intermediates, **cfg)
-        recon = self._normalize_recon(recon, self.training if update_loss_ema is None else update_loss_ema)
-        total = recon                                                          # every other term of dreamer4.py:4576-4589 is zero in the subset
+            v_space=self.decoder_v_space_loss, return_recon_video=return_intermediates, ortho='latent_ortho' in used,
+            consistency='latent_consistency' in used, **reg_kw, **cfg)
+        update = self.training if update_loss_ema is None else update_loss_ema
+        recon = self._normalize_loss(recon, update)
+        total = recon                                                          # the terms of dreamer4.py:4576-4589 the subset has, in its order
+        terms = dict(latent_ortho=regs['ortho'], latent_consistency=regs['consistency'], latent_sigreg=regs['sigreg'])
+        for f in ('latent_ortho', 'latent_consistency', 'latent_sigreg'):
+            if f in used:
+                terms[f] = self._normalize_loss(terms[f], update, key=_REG_NORMALIZER_KEYS[f])
+                total = total + terms[f] * self.loss_weights[f]
         if not return_intermediates:
             return total
         z = self.zero
         if is_image:
             recon_video = recon_video.squeeze(2)
-        return total, VideoTokenizerIntermediates(TokenizerLosses(recon, z, z, z, z, z, z, z, z, z, z, z), recon_video)
+        t = {f: (v if f in used else z) for f, v in terms.items()}
+        return total, VideoTokenizerIntermediates(TokenizerLosses(recon, z, z, z, z, t['latent_ortho'], z, z, t['latent_consistency'], t['latent_sigreg'], z, z),
+                                                  recon_video)

@@ -644,6 +644,33 @@ def recon_loss(recon_rows, video, noise, times, patch_size, v_space=True):
     return _ReconLoss.apply(recon_rows, video, noise, times, patch_size, bool(v_space))
 
 
+class _LossWithGrad(torch.autograd.Function):
+    """An operator that returns (loss, d loss / d x) for a unit upstream gradient: the gradient is saved and scaled by the incoming one."""
+    @staticmethod
+    def forward(ctx, x, impl, *args):
+        loss, dx = impl(x, *args)
+        ctx.save_for_backward(dx)
+        ctx.n_args = len(args)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        return (ctx.saved_tensors[0] * d_loss, None) + (None,) * ctx.n_args
+
+
+def sigreg(x, projs, domain=_ops.SIGREG_DOMAIN, num_knots=_ops.SIGREG_KNOTS):
+    """sigreg(x) without a mask (dreamer4.py:728-767) on x (k, ..., d) with the raw normal draw `projs` (num_slices, d), differentiable in x."""
+    lo, hi = float(domain[0]), float(domain[1])
+    if via_dispatcher():
+        return torch.ops.d4hip.sigreg(x, projs, lo, hi, int(num_knots))[0]
+    return _LossWithGrad.apply(x, _ops.sigreg_impl, projs, lo, hi, int(num_knots))
+
+
+def latent_ortho(x):
+    """orthogonal_loss(x) (dreamer4.py:389-402) on x (..., n, d), differentiable in x."""
+    return torch.ops.d4hip.latent_ortho(x)[0] if via_dispatcher() else _LossWithGrad.apply(x, _ops.latent_ortho_impl)
+
+
 def _decoder_pos_embedding(W, nh, nw, n_layers, recipe, dev):
     """to_decoder_pos_emb on the linspace(-1, 1) grid of patch coordinates (dreamer4.py:3617-3625): (nh * nw, dim).  Parameter-sized work: the
     2-wide input of the first layer is normalised elementwise and zero-padded to the 4-float granularity of the HIP Linear."""
@@ -669,31 +696,51 @@ def _decoder_pos_embedding(W, nh, nw, n_layers, recipe, dev):
     return x
 
 
-def tokenizer_latents(W, video, *, patch_size, num_latent_tokens, encoder_is_time, patch_mask=None, wide=False):
+def tokenizer_latents(W, video, *, patch_size, num_latent_tokens, encoder_is_time, patch_mask=None, wide=False, rows=None, return_pre_tanh=False):
     """The encoder half of VideoTokenizer.forward (dreamer4.py:4309-4425) for training: video (b, c, t, H, W) -> latents (b, t, n, dim_latent) in
-    (-1, 1), differentiable in every encoder parameter.  `patch_mask` (b, t, nh, nw) bool: those patch tokens are replaced by `mask_token`."""
-    b, _, t = video.shape[:3]
-    rows = video_to_patches(video, patch_size)
+    (-1, 1), differentiable in every encoder parameter.  `patch_mask` (b, t, nh, nw) bool: those patch tokens are replaced by `mask_token`.
+    `rows` (b, t, nh, nw, p1 p2 c), with `video` None: the patch rows themselves, which may carry a gradient (the consistency pass feeds the decoder's
+    rows: the patch permutation of their un-patchified video gives them back bit for bit).  `return_pre_tanh`: (latents, encoded_to_latents' output
+    before the tanh), what the SIGReg term reads (dreamer4.py:4416-4425)."""
+    if rows is None:
+        rows = video_to_patches(video, patch_size)
+    b, t = rows.shape[:2]
     x = layernorm_nobias(_lin(rows, W['patch_to_tokens.1.weight'], W['patch_to_tokens.1.bias']), W['patch_to_tokens.2.weight'], 1e-5)
     if patch_mask is not None:
         x = mask_rows(x, patch_mask, W['mask_token'])
     d = x.shape[-1]
     tokens = torch.cat((x.reshape(b, t, -1, d), W['latent_tokens'].expand(b, t, -1, -1)), dim=2)                 # [patches | latents]  dreamer4.py:4375
     tokens = transformer(W, tokens, is_time=encoder_is_time, num_special=num_latent_tokens, pre='encoder_transformer.', wide=wide)
-    return _lin(tokens[:, :, -num_latent_tokens:], W['encoded_to_latents.weight']).tanh()
+    pre = _lin(tokens[:, :, -num_latent_tokens:], W['encoded_to_latents.weight'])
+    return (pre.tanh(), pre) if return_pre_tanh else pre.tanh()
+
+
+# the encoder's parameters by state_dict key prefix (what the encoder engine binds); with the training-only mask token, encoder_parameters() of dreamer4.py:4060-4067
+ENCODER_KEYS = ('latent_tokens', 'patch_to_tokens.', 'encoder_transformer.', 'encoded_to_latents.')
 
 
 def tokenizer_losses(W, video, *, draws, patch_size, num_latent_tokens, encoder_is_time, decoder_is_time, decoder_flow_steps, decoder_pos_mlp_depth,
-                     head_mlp_recipe='pre_rms', v_space=True, wide=False, return_recon_video=False):
-    """The reconstruction loss of VideoTokenizer.forward (dreamer4.py:4309-4516: flow decoder, no LPIPS / auxiliary losses) with backward through both
-    trunks.  W: the tokenizer's parameters by reference state_dict key; video (b, c, t, H, W); draws = dict(patch_mask (b, t, nh, nw) bool or None,
-    time_indices (b,) in [0, decoder_flow_steps), noise like the video).  The passes over pixels are the operators of csrc/tok_train.hip: patch rows of
-    the video and of noise.lerp(video, t), the LayerNorm of both patch embeddings, the mask rows, and the fused loss, which reads the video through the
-    patch permutation (nothing is un-patchified).  Returns (recon_loss, latents, recon_video or None)."""
+                     head_mlp_recipe='pre_rms', v_space=True, wide=False, return_recon_video=False, sigreg_kwargs=None, ortho=False, consistency=False):
+    """The losses of VideoTokenizer.forward (dreamer4.py:4309-4542: flow decoder, no LPIPS) with backward through both trunks.  W: the tokenizer's
+    parameters by reference state_dict key; video (b, c, t, H, W); draws = dict(patch_mask (b, t, nh, nw) bool or None, time_indices (b,) in
+    [0, decoder_flow_steps), noise like the video; with `sigreg_kwargs`, sigreg_projs (num_slices, dim_latent), the raw normal draw).  The passes over
+    pixels are the operators of csrc/tok_train.hip: patch rows of the video and of noise.lerp(video, t), the LayerNorm of both patch embeddings, the mask
+    rows, and the fused loss, which reads the video through the patch permutation (nothing is un-patchified).
+    The latent regularisers, each only when asked for (none of them: the launches of the reconstruction loss alone):
+      sigreg_kwargs = dict(domain=, num_knots=)   sigreg of encoded_to_latents' output before the tanh, per clip over (frames, latents)   dreamer4.py:4416-4423
+      ortho                                       orthogonal_loss of the tanh'ed latents of every frame                                  dreamer4.py:4541
+      consistency                                 mse(encoder(decoder output), latents.detach()) with the encoder's parameters frozen: a second encoder pass
+                                                  on the decoder's patch rows under the same patch mask                               dreamer4.py:4493-4507
+    Returns (recon_loss, latents, recon_video or None, dict(sigreg=, ortho=, consistency=) with None for a term that was not asked for)."""
     b, c, t, H, Wd = video.shape
     nh, nw = H // patch_size, Wd // patch_size
-    latents = tokenizer_latents(W, video, patch_size=patch_size, num_latent_tokens=num_latent_tokens, encoder_is_time=encoder_is_time,
-                                patch_mask=draws.get('patch_mask'), wide=wide)
+    enc = dict(patch_size=patch_size, num_latent_tokens=num_latent_tokens, encoder_is_time=encoder_is_time, patch_mask=draws.get('patch_mask'), wide=wide)
+    regs = dict(sigreg=None, ortho=None, consistency=None)
+    if sigreg_kwargs is not None:
+        latents, pre = tokenizer_latents(W, video, return_pre_tanh=True, **enc)
+        regs['sigreg'] = sigreg(pre, draws['sigreg_projs'], **sigreg_kwargs)
+    else:
+        latents = tokenizer_latents(W, video, **enc)
     time_indices, noise = draws['time_indices'], draws['noise']
     times = time_indices.float() / decoder_flow_steps
     lat = _lin(latents, W['latents_to_decoder.weight']) + W['time_embed.weight'][time_indices][:, None, None]      # dreamer4.py:4151-4157
@@ -706,8 +753,13 @@ def tokenizer_losses(W, video, *, draws, patch_size, num_latent_tokens, encoder_
     tokens = transformer(W, tokens, is_time=decoder_is_time, num_special=1, pre='decoder.transformer.', wide=wide)
     recon_rows = _lin(tokens[:, :, :nh * nw], W['decoder.tokens_to_patch.0.weight'], W['decoder.tokens_to_patch.0.bias']).reshape(b, t, nh, nw, -1)
     loss = recon_loss(recon_rows, video, noise, times, patch_size, v_space)
+    if consistency:
+        frozen = {k: (v.detach() if k.startswith(ENCODER_KEYS + ('mask_token',)) else v) for k, v in W.items()}
+        regs['consistency'] = (tokenizer_latents(frozen, None, rows=recon_rows, **enc) - latents.detach()).square().mean()
+    if ortho:
+        regs['ortho'] = latent_ortho(latents)
     recon_video = _ops.patches_to_video_impl(recon_rows.detach(), c, patch_size) if return_recon_video else None
-    return loss, latents, recon_video
+    return loss, latents, recon_video, regs
 
 
 # ------------------------------------------------------------------------------------------------ agent-token losses of the training forward

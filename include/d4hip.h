@@ -897,6 +897,21 @@ int d4_mask_rows_fwd(const float* x, const uint8_t* mask, const float* token, fl
 int d4_mask_rows_bwd(const float* dy, const uint8_t* mask, float* dx, float* dtoken, float* part, size_t part_floats, int rows, int dim, void* stream);
 int d4_recon_loss_fwd_bwd(const float* recon_rows, const float* video, const float* noise, const float* t, int B, int C, int T, int nh, int nw, int ps, int v_space,
                           float* loss, float* d_rows, float* part, size_t part_floats, void* stream);
+/* Latent regularisers of the VideoTokenizer training forward (dreamer4.py:728-767, 389-402; csrc/tok_reg.hip).  Each call writes the loss and
+ * d loss / d x for a unit upstream gradient.  No allocation, no host synchronisation, no float atomics: equal inputs give equal bits.
+ *   d4_sigreg_fwd_bwd        sigreg(x) without a mask on x [K][N][d], projs [M][d] the RAW normal draw (each row is normalised as F.normalize does, eps
+ *                            1e-12): the empirical characteristic function per (k, slice, knot) as the mean over N at the knots linspace(lo, hi,
+ *                            num_knots), squared distance to exp(-t^2 / 2) weighted by exp(-t^2 / 2), trapezoid over the knots, mean over (K, M).
+ *                            d <= 128, 2 <= num_knots <= 64, M <= 4096, K <= 65535; anything else is an error.  Nothing of size N * M is written.
+ *   d4_sigreg_part_floats    floats of `part` it needs: 2 K M num_knots per block of 64 rows of N, plus ceil(K M num_knots / 256).
+ *   d4_latent_ortho_fwd_bwd  orthogonal_loss(x) on x [F][n][d]: per frame centre over n, F.normalize the rows, sum of the squared off-diagonal entries
+ *                            of the n x n Gram; mean over F.  n <= 1024, d <= 128.  n = 1 gives exactly 0 and a zero gradient.
+ *   d4_latent_ortho_part_floats  floats of `part` it needs (F). */
+size_t d4_sigreg_part_floats(int K, int N, int M, int num_knots);
+int d4_sigreg_fwd_bwd(const float* x, const float* projs, int K, int N, int d, int M, float lo, float hi, int num_knots, float* loss, float* dx, float* part,
+                      size_t part_floats, void* stream);
+size_t d4_latent_ortho_part_floats(int F);
+int d4_latent_ortho_fwd_bwd(const float* x, int F, int n, int d, float* loss, float* dx, float* part, size_t part_floats, void* stream);
 /* d4_pack_tokens that also writes the bf16 image of the token rows (the bf16 tokenizer engine's slab 0, VideoTokenizer(matmul_dtype='bf16');
  * DESIGN.md 27): tokens and compact carry d4_pack_tokens' bits, tokens_b [frames * (P + n_lat)][D] their round-to-nearest-even bf16 values, written
  * by the same pass (16-byte stores at D % 8 == 0 with 32-byte aligned fp32 buffers and a 16-byte aligned image, 8-byte stores at D % 4 == 0,
